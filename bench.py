@@ -25,6 +25,12 @@ Extra objects on the JSON line:
   config.loss_curve_rel_err[_fp32] -- 20 AdamW steps of DiT-S/2 against the reference's own fp32 loss curve (committed fixture): the
                   largest / mean per-step relative error of the bf16 regime (the timed one) and of the fp32 regime (precision_type="no",
                   the reference's default; north_star's 1e-4 bar) -- N=1, outside the timed region.
+
+--dump-outputs DIR writes what the LAST timed step computed, right after the timed region and before anything else touches the model
+(rank 0): DIR/loss.npy (the step's loss), DIR/params.npy (the parameters after its AdamW update), DIR/grads.npy (its gradients) and,
+with --trainer-mode, DIR/ema_params.npy (the EMA copy), all float32.  The parameter-sized arrays are the same DUMP_SAMPLE positions of
+the parameters concatenated in name order, drawn from a fixed seed (64 MB at most in all).  Model, data, timesteps, noise and label
+drops are seeded, so the same arguments give the same inputs: two builds of the project can be compared array for array.
 """
 
 from __future__ import annotations
@@ -50,6 +56,7 @@ if ROOT not in sys.path:
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md; AMD's 5 PF figure is 2:1 sparse)
 S2 = dict(simple_dit=True, input_channels=4, output_channels=4, inner_dim=384, embedding_dim=384, num_heads=6,
           mlp_ratio=4, patch_size=2, depth=12, n_classes=1000, classifier_free=True)
+DUMP_SAMPLE = 4_000_000  # --dump-outputs: sampled values per parameter-sized array (16 MB of float32; three arrays at most)
 
 
 def train_flops_per_image(D=384, E=384, L=12, N=256, pC=16) -> float:
@@ -437,6 +444,33 @@ def roofline_replay(step, model, images_per_s_per_gpu: float) -> dict:
             "hbm_bound_kernels": hbm_kernels, "dominant_kernel_alone": alone, "floors": floors}
 
 
+def dump_outputs(path: str, loss: float, model, ema=None) -> None:
+    """--dump-outputs: the last timed step's loss and a fixed, seeded sample of the parameters, gradients (and EMA parameters)
+    it left behind, as float32 .npy files under `path`"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    named = sorted(model.named_parameters())  # name order: independent of the arena layout of a build
+    n = sum(p.numel() for _, p in named)
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(named[0][1].device)
+
+    def sample(ts) -> np.ndarray:
+        flat = torch.cat([t.detach().reshape(-1).float() for t in ts])
+        return (flat if idx is None else flat[idx]).cpu().numpy()
+
+    arrays = {"loss": np.array([loss], dtype=np.float32),
+              "params": sample(p for _, p in named),
+              "grads": sample(p.grad if p.grad is not None else torch.zeros_like(p) for _, p in named)}
+    if ema is not None:
+        ema_named = dict(ema.ema_model.named_parameters())
+        arrays["ema_params"] = sample(ema_named[k] for k, _ in named)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    print(f"dumped {', '.join(arrays)} ({sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MB) to {path}", file=sys.stderr, flush=True)
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` without an external launcher: the parent starts N fresh child processes of this script (one rank
     per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1), relays their output -- rank 0 prints the JSON
@@ -495,7 +529,11 @@ def main() -> None:
                     "(loss meter, fused EMA) instead of the bare zero_grad / loss / backward / AdamW sequence")
     ap.add_argument("--launch-check", action="store_true", help="print this rank's launch environment and exit before any GPU "
                     "call (tests/test_host_logic.py checks the self-launch path on the CPU container with it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed region, write what the last timed step computed to "
+                    "DIR/*.npy (float32): its loss and a fixed sample of the parameters and gradients it left")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))  # plain `python bench.py --gpus N`: this process becomes the launcher (never touches a GPU)
@@ -559,7 +597,14 @@ def main() -> None:
 
         trainer = BaseTrainer(n_epoch=1, precision_type="bf16", save_path=tempfile.mkdtemp(prefix="bench_trainer_"), use_ema=True)
         ema = EMA(model, beta=0.999, update_after_step=0, update_every=10)
-        meter = AverageMeter()
+
+        class LossKeepingMeter(AverageMeter):  # --dump-outputs: the step's loss also lands in loss_host (no host synchronisation)
+            def update(self, val, key, n=1):
+                if key == "train/loss":
+                    loss_host.copy_(val, non_blocking=True)
+                super().update(val, key, n)
+
+        meter = LossKeepingMeter() if args.dump_outputs else AverageMeter()
         batch = {"model_inputs": {"x": x_data, "y": y_data}, "extra": {}}
 
         def step() -> None:  # noqa: F811
@@ -592,6 +637,8 @@ def main() -> None:
     ms = dt / args.steps * 1e3
     value = world * B * args.steps / dt
     final_loss = float(loss_host)
+    if rank == 0 and args.dump_outputs:  # before the dp / roofline steps below move the model on
+        dump_outputs(args.dump_outputs, final_loss, model, ema)
 
     dp = None
     if world > 1:  # a few extra steps with the reducer's wait instrumented: how much of the all-reduce is NOT hidden under backward

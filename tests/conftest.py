@@ -65,6 +65,24 @@ def golden():
 
 
 @pytest.fixture(scope="session")
+def host_exact():
+    """Bit-exact comparison with a reference fixture whose values pass through torch's CPU sqrt / log / exp / sin / cos.  Those run
+    through MKL's vector math, whose last bits depend on the CPU (an Intel and an AMD host differ by an ulp and more), so on another
+    host the reference itself computes other bits than the ones recorded.  `restated` is the same reference formula evaluated on
+    THIS host from the fixture's own (host-independent) inputs: where it reproduces the recorded values -- on the host that wrote the
+    fixtures -- `got` must equal those; elsewhere it must equal the formula on this host's math.  Either way bit for bit."""
+
+    def as_np(x):
+        return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+    def check(got, fixture, restated) -> bool:
+        fixture, restated = as_np(fixture), as_np(restated)
+        return np.array_equal(as_np(got), fixture if np.array_equal(restated, fixture) else restated)
+
+    return check
+
+
+@pytest.fixture(scope="session")
 def probe_lib():
     """libdiffulab_probe.so (include/diffulab_probe.h): LAB instrumentation, not part of the product ABI -- the GPU tests use its two
     instruction-semantics probes to pin the operand layouts the product kernels rely on"""

@@ -44,15 +44,21 @@ def test_flow_grid_and_draws_match_reference(golden):
         Flow(n_steps=4, prediction_type="eps")
 
 
-def test_gaussian_tables_and_respacing_match_reference(golden):
+def test_gaussian_tables_and_respacing_match_reference(golden, host_exact):
+    from oracle import diffusion as od
+
     g = golden("schedules")
     for sched in ("linear", "cosine"):
         d = GaussianDiffusion(n_steps=1000, schedule=sched)
-        for nm in ("betas", "alphas_bar", "sqrt_alphas_bar"):
+        # (tables behind a sqrt / log: the oracle -- the reference's formulas, test_oracle_golden.py -- on this host's math)
+        T = od.GaussianTables(1000, schedule=sched)
+        for nm in ("betas", "alphas_bar"):
             assert np.array_equal(t2n(getattr(d, nm)), g[f"gd_{sched}_{nm}"]), nm
-        for nm in ("alphas_bar_prev", "posterior_variance", "posterior_log_variance_clipped", "posterior_mean_coef1",
-                   "posterior_mean_coef2"):
+        assert host_exact(d.sqrt_alphas_bar, g[f"gd_{sched}_sqrt_alphas_bar"], T.sqrt_alphas_bar)
+        for nm in ("alphas_bar_prev", "posterior_variance"):
             assert np.array_equal(t2n(getattr(d.sampler, nm)), g[f"gd_{sched}_{nm}"]), nm
+        for nm in ("posterior_log_variance_clipped", "posterior_mean_coef1", "posterior_mean_coef2"):
+            assert host_exact(getattr(d.sampler, nm), g[f"gd_{sched}_{nm}"], getattr(T, nm)), nm
     for n in (50, 100, 250):
         d = GaussianDiffusion(n_steps=1000)
         d.set_steps(n)
@@ -151,6 +157,42 @@ def test_bench_launches_its_own_ranks_without_touching_a_gpu():
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--launch-check", "--steps", "x"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert bad.returncode != 0
+
+
+def test_bench_dump_outputs_is_a_fixed_float32_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the last step's loss and the same seeded positions of its parameters, gradients and EMA copy
+    (parameters concatenated in name order) as float32 .npy files, identical from call to call and under 64 MB at full size;
+    `--steps` below 1 is refused before anything runs."""
+    import subprocess
+    import sys
+    import types
+
+    import bench
+
+    assert 3 * bench.DUMP_SAMPLE * 4 + 4 <= 64 * 2**20
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(16, 32), torch.nn.Linear(32, 8))
+    m(torch.randn(4, 16)).square().mean().backward()
+    ema = types.SimpleNamespace(ema_model=copy.deepcopy(m))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    bench.dump_outputs(str(tmp_path / "a"), 0.25, m, ema)
+    bench.dump_outputs(str(tmp_path / "b"), 0.25, m, ema)
+    assert sorted(os.listdir(tmp_path / "a")) == ["ema_params.npy", "grads.npy", "loss.npy", "params.npy"]
+    got = {}
+    for name in os.listdir(tmp_path / "a"):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        got[name[:-4]] = a
+    named = sorted(m.named_parameters())
+    idx = torch.randperm(sum(p.numel() for _, p in named), generator=torch.Generator().manual_seed(0))[:100].sort().values
+    assert np.array_equal(got["params"], torch.cat([p.detach().reshape(-1) for _, p in named])[idx].numpy())
+    assert np.array_equal(got["grads"], torch.cat([p.grad.reshape(-1) for _, p in named])[idx].numpy())
+    assert np.array_equal(got["ema_params"], got["params"]) and got["loss"].tolist() == [0.25]
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0", "--launch-check"], capture_output=True,
+                         text=True, timeout=300)
+    assert bad.returncode == 2 and "--steps" in bad.stderr
 
 
 def test_fused_adamw_flat_arena_detection_is_cached_and_revalidated():

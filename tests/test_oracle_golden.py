@@ -5,6 +5,7 @@ Tolerances: integer / index data bit-exact; fp64 tables bit-exact (same torch op
 fp32 tensors <= 2e-6 relative-L2 (different-but-equivalent op order, e.g. explicit softmax vs SDPA).
 """
 
+import math
 import os
 
 import numpy as np
@@ -72,13 +73,19 @@ def test_draw_timesteps_bit_exact(golden):
             assert got.dtype == torch.int32 and np.array_equal(t2n(got), g[f"draw_ddpm_s{seed}_b{B}"])
 
 
-def test_gaussian_tables_bit_exact(golden):
+def test_gaussian_tables_bit_exact(golden, host_exact):
     g = golden("schedules")
     for sched in ("linear", "cosine"):
         T = od.GaussianTables(1000, schedule=sched)
-        for nm in ("betas", "alphas_bar", "sqrt_alphas_bar", "alphas_bar_prev", "posterior_variance",
-                   "posterior_log_variance_clipped", "posterior_mean_coef1", "posterior_mean_coef2"):
+        for nm in ("betas", "alphas_bar", "alphas_bar_prev", "posterior_variance"):
             assert np.array_equal(t2n(getattr(T, nm)), g[f"gd_{sched}_{nm}"]), (sched, nm)
+        # the tables behind a sqrt / log: the reference's formulas (gd.py:87-133, ddpm.py:49-85) on the recorded fp64 inputs
+        b, ab, abp, pv = (torch.from_numpy(g[f"gd_{sched}_{k}"]) for k in ("betas", "alphas_bar", "alphas_bar_prev", "posterior_variance"))
+        one = torch.ones_like(b)
+        restated = {"sqrt_alphas_bar": ab.sqrt(), "posterior_log_variance_clipped": torch.log(torch.cat([pv[1:2], pv[1:]])),
+                    "posterior_mean_coef1": b * abp.sqrt() / (one - ab), "posterior_mean_coef2": (one - abp) * (one - b).sqrt() / (one - ab)}
+        for nm, r in restated.items():
+            assert host_exact(getattr(T, nm), g[f"gd_{sched}_{nm}"], r), (sched, nm)
 
 
 def test_respacing_bit_exact(golden):
@@ -98,13 +105,20 @@ def test_respacing_bit_exact(golden):
 
 
 # ------------------------------------------------------------------ primitives
-def test_embeddings_and_rope(golden):
+def test_embeddings_and_rope(golden, host_exact):
     g = golden("prims")
     t = synth.uniform("prims.t", (8,), lo=0.0, hi=1.0)
     ti = torch.tensor([0, 1, 17, 500, 999], dtype=torch.int32)
-    assert np.array_equal(t2n(odit.timestep_embedding(t, 256)), g["temb_f"])
-    assert np.array_equal(t2n(odit.timestep_embedding(ti, 128)), g["temb_i"])
-    assert np.array_equal(t2n(odit.timestep_embedding(t, 9)), g["temb_odd"])
+
+    def temb(ts, dim):  # the reference's formula (nn.py:106-114) on this host's exp / cos / sin
+        freqs = torch.exp(-math.log(10000) * torch.arange(start=0, end=dim // 2, dtype=torch.float32) / (dim // 2))
+        args = ts[:, None].float() * freqs[None]
+        emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
+        return torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1) if dim % 2 else emb
+
+    assert host_exact(odit.timestep_embedding(t, 256), g["temb_f"], temb(t, 256))
+    assert host_exact(odit.timestep_embedding(ti, 128), g["temb_i"], temb(ti, 128))
+    assert host_exact(odit.timestep_embedding(t, 9), g["temb_odd"], temb(t, 9))
     c, s = odit.rope_tables(16, 16, [32, 32], 10_000)
     assert np.array_equal(t2n(c), g["rope_cos_16x16"]) and np.array_equal(t2n(s), g["rope_sin_16x16"])
     c, s = odit.rope_tables(3, 5, [8, 24], 2000)

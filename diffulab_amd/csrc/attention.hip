@@ -1428,3 +1428,232 @@ bool launch_attn_small_mfma_bwd(const void* q, const void* k, const void* v, int
                      ldkv, (const bf16_t*)dout, ldo, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, (int)n, (int)H, (int)dh, scale);
   return true;
 }
+
+// ====================================================================================== masked cross-attention (UNet TransformerBlock)
+// MFMA form of dl_attn_cross_fwd / _bwd (csrc/unet.hip) for Nq <= 64 queries, head_dim % 64 == 0 up to 512, L context keys: one
+// workgroup (4 waves) per (batch, head), the pattern of attn_small_mfma_* with the keys streamed in tiles of 64.  K and V of one
+// head at L = 512, dh = 512 (512 KB) do not fit the LDS, so the scores S^T = K Q^T are taken from global fragments tile by tile into
+// the f32 probability rows (the saved `probs`; the workgroup re-reads its own rows after a barrier), the row softmax runs over them
+// in place, and O^T = V^T P^T accumulates over key tiles with one [64 keys, dh] V tile staged in the LDS at a time.  Backward: dP^T =
+// V dO^T tile by tile into `ds`, dS = P o (dP - rowsum(P o dP)) * scale in place, then dQ^T = K^T dS^T accumulated over key tiles
+// (K tiles staged), dV^T = dO^T P and dK^T = Q^T dS per key tile (dO, then Q staged once).  Masked keys have P = dS = 0 exactly:
+// their products are zeros, every output of a fully masked query row and every gradient row of a masked key is +0.
+#define AXM_MAXT 8  // O^T / dQ^T accumulator tiles per wave: 2 * (512 / 32) / 4
+__device__ __forceinline__ void load_score_tile(float* T, const float* g, int Nq, int L, int k0, int tid) {
+  for (int idx = tid; idx < 64 * 64; idx += 256) {
+    const int i = idx >> 6, j = idx & 63;
+    T[i * ASM_PITCH + j] = (i < Nq && k0 + j < L) ? g[(int64_t)i * L + k0 + j] : 0.f;
+  }
+}
+// S^T (or dP^T) tile of this wave for key tile k0: lane & 31 = query, registers <-> keys; rows beyond Nq / L re-read the last row
+// and are not stored.  dst[i * L + j] = acc * mul + (bias ? bias[j] : 0)
+__device__ __forceinline__ void score_tile_to_global(const bf16_t* __restrict__ arow_base, int64_t lda, const bf16_t* __restrict__ brow_base,
+                                                     int64_t ldb, float* __restrict__ dst, const float* __restrict__ bias, int Nq,
+                                                     int L, int k0, int dh, float mul, int wave, int lane) {
+  const int hi = lane >> 5;
+  const int ti = wave >> 1, tj = wave & 1;
+  const int qi = ti * 32 + (lane & 31);
+  const int kr = k0 + tj * 32 + (lane & 31);
+  const bf16_t* qrow = brow_base + (int64_t)(qi < Nq ? qi : Nq - 1) * ldb + hi * 8;
+  const bf16_t* krow = arow_base + (int64_t)(kr < L ? kr : L - 1) * lda + hi * 8;
+  f32x16_t st;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) st[r] = 0.f;
+  for (int ks = 0; ks < (dh >> 4); ++ks) st = MFMA(*(const bf16x8_t*)(krow + ks * 16), *(const bf16x8_t*)(qrow + ks * 16), st);
+  if (qi >= Nq) return;
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = k0 + tj * 32 + g4 * 8 + hi * 4 + e;
+      if (j < L) dst[(int64_t)qi * L + j] = st[g4 * 4 + e] * mul + (bias ? bias[j] : 0.f);
+    }
+}
+
+__global__ __launch_bounds__(256) void attn_cross_mfma_fwd_k(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                             const bf16_t* __restrict__ v, int64_t ldq, int64_t ldkv,
+                                                             const float* __restrict__ kbias, bf16_t* __restrict__ out, int64_t ldo,
+                                                             float* __restrict__ probs, int Nq, int L, int H, int dh, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* P = (float*)smem;
+  char* vt = smem + 64 * ASM_PITCH * 4;
+  const int lane = threadIdx.x & 63, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const bf16_t* qb = q + (int64_t)b * Nq * ldq + h * dh;
+  const bf16_t* kb = k + (int64_t)b * L * ldkv + h * dh;
+  const bf16_t* vb = v + (int64_t)b * L * ldkv + h * dh;
+  const float* bb = kbias ? kbias + (int64_t)b * L : nullptr;
+  float* pg = probs + (int64_t)bh * Nq * L;
+  for (int k0 = 0; k0 < L; k0 += 64) score_tile_to_global(kb, ldkv, qb, ldq, pg, bb, Nq, L, k0, dh, scale, wave, lane);
+  __syncthreads();
+  for (int i = wave; i < Nq; i += 4) {  // row softmax in place (one wave per row); every key masked: zeros
+    float* pr = pg + (int64_t)i * L;
+    float mx = -INFINITY;
+    for (int j = lane; j < L; j += 64) mx = fmaxf(mx, pr[j]);
+    mx = wave_max(mx);
+    if (mx == -INFINITY) {
+      for (int j = lane; j < L; j += 64) pr[j] = 0.f;
+      continue;
+    }
+    float sum = 0.f;
+    for (int j = lane; j < L; j += 64) sum += expf(pr[j] - mx);
+    const float inv = 1.0f / wave_sum(sum);
+    for (int j = lane; j < L; j += 64) pr[j] = expf(pr[j] - mx) * inv;
+  }
+  __syncthreads();
+  const int ncb = dh >> 6, ntile = 2 * (dh >> 5);
+  f32x16_t acc[AXM_MAXT];
+#pragma unroll
+  for (int u = 0; u < AXM_MAXT; ++u)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[u][r] = 0.f;
+  for (int k0 = 0; k0 < L; k0 += 64) {
+    for (int cb = 0; cb < ncb; ++cb) tile_dma_clamp(vb + (int64_t)k0 * ldkv + cb * 64, ldkv, vt + cb * 8192, L - k0, wave, 4, lane);
+    load_score_tile(P, pg, Nq, L, k0, threadIdx.x);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < AXM_MAXT; ++u) {
+      const int t = wave + 4 * u;
+      if (t < ntile) {
+        const int th = t & 1, c32 = t >> 1;
+        const int i = th * 32 + (lane & 31);
+#pragma unroll
+        for (int kg = 0; kg < 4; ++kg)
+          acc[u] = MFMA(frag_cols(vt + (c32 >> 1) * 8192, kg * 16, (c32 & 1) * 32, lane), score_frag_row(P, i, kg * 16, hi), acc[u]);
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int u = 0; u < AXM_MAXT; ++u) {
+    const int t = wave + 4 * u;
+    if (t < ntile) {
+      const int th = t & 1, c32 = t >> 1;
+      const int i = th * 32 + (lane & 31);
+      if (i < Nq) store_tile32(out + ((int64_t)b * Nq + i) * ldo + h * dh + c32 * 32, acc[u], hi);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void attn_cross_mfma_bwd_k(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                             const bf16_t* __restrict__ v, int64_t ldq, int64_t ldkv,
+                                                             const bf16_t* __restrict__ dout, int64_t ldo, const float* __restrict__ probs,
+                                                             float* __restrict__ ds, bf16_t* __restrict__ dq, bf16_t* __restrict__ dk,
+                                                             bf16_t* __restrict__ dv, int Nq, int L, int H, int dh, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* T = (float*)smem;
+  char* tt = smem + 64 * ASM_PITCH * 4;
+  const int lane = threadIdx.x & 63, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const bf16_t* qb = q + (int64_t)b * Nq * ldq + h * dh;
+  const bf16_t* kb = k + (int64_t)b * L * ldkv + h * dh;
+  const bf16_t* vb = v + (int64_t)b * L * ldkv + h * dh;
+  const bf16_t* dob = dout + (int64_t)b * Nq * ldo + h * dh;
+  const float* pg = probs + (int64_t)bh * Nq * L;
+  float* dg = ds + (int64_t)bh * Nq * L;
+  const int ncb = dh >> 6, ntile = 2 * (dh >> 5);
+  for (int k0 = 0; k0 < L; k0 += 64) score_tile_to_global(vb, ldkv, dob, ldo, dg, nullptr, Nq, L, k0, dh, 1.0f, wave, lane);  // dP
+  __syncthreads();
+  for (int i = wave; i < Nq; i += 4) {  // dS = P o (dP - rowsum(P o dP)) * scale, in place
+    const float* pr = pg + (int64_t)i * L;
+    float* dr = dg + (int64_t)i * L;
+    float dot = 0.f;
+    for (int j = lane; j < L; j += 64) dot += pr[j] * dr[j];
+    dot = wave_sum(dot);
+    for (int j = lane; j < L; j += 64) {
+      const float p = pr[j];
+      dr[j] = p == 0.f ? 0.f : p * (dr[j] - dot) * scale;
+    }
+  }
+  __syncthreads();
+  // dQ^T = K^T dS^T, accumulated over key tiles: lane & 31 = query
+  f32x16_t acc[AXM_MAXT];
+#pragma unroll
+  for (int u = 0; u < AXM_MAXT; ++u)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[u][r] = 0.f;
+  for (int k0 = 0; k0 < L; k0 += 64) {
+    for (int cb = 0; cb < ncb; ++cb) tile_dma_clamp(kb + (int64_t)k0 * ldkv + cb * 64, ldkv, tt + cb * 8192, L - k0, wave, 4, lane);
+    load_score_tile(T, dg, Nq, L, k0, threadIdx.x);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < AXM_MAXT; ++u) {
+      const int t = wave + 4 * u;
+      if (t < ntile) {
+        const int th = t & 1, c32 = t >> 1;
+        const int i = th * 32 + (lane & 31);
+#pragma unroll
+        for (int kg = 0; kg < 4; ++kg)
+          acc[u] = MFMA(frag_cols(tt + (c32 >> 1) * 8192, kg * 16, (c32 & 1) * 32, lane), score_frag_row(T, i, kg * 16, hi), acc[u]);
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int u = 0; u < AXM_MAXT; ++u) {
+    const int t = wave + 4 * u;
+    if (t < ntile) {
+      const int th = t & 1, c32 = t >> 1;
+      const int i = th * 32 + (lane & 31);
+      if (i < Nq) store_tile32(dq + ((int64_t)b * Nq + i) * ldq + h * dh + c32 * 32, acc[u], hi);
+    }
+  }
+  // dV^T = dO^T P (dO staged), then dK^T = Q^T dS (Q staged): contraction over the <= 64 queries, lane & 31 = key
+  for (int pass = 0; pass < 2; ++pass) {
+    const bf16_t* src = pass ? qb : dob;
+    const int64_t lds = pass ? ldq : ldo;
+    const float* sg = pass ? dg : pg;
+    bf16_t* dst = pass ? dk : dv;
+    for (int cb = 0; cb < ncb; ++cb) tile_dma_clamp(src + cb * 64, lds, tt + cb * 8192, Nq, wave, 4, lane);
+    for (int k0 = 0; k0 < L; k0 += 64) {
+      load_score_tile(T, sg, Nq, L, k0, threadIdx.x);  // rows >= Nq are zero: the clamped staged rows contribute nothing
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      for (int t = wave; t < ntile; t += 4) {
+        const int th = t & 1, c32 = t >> 1;
+        const int j = th * 32 + (lane & 31);
+        f32x16_t a;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a[r] = 0.f;
+#pragma unroll
+        for (int kg = 0; kg < 4; ++kg)
+          a = MFMA(frag_cols(tt + (c32 >> 1) * 8192, kg * 16, (c32 & 1) * 32, lane), score_frag_col(T, j, kg * 16, hi), a);
+        if (k0 + j < L) store_tile32(dst + ((int64_t)b * L + k0 + j) * ldkv + h * dh + c32 * 32, a, hi);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// launchers for dl_attn_cross_{fwd,bwd} (csrc/unet.hip); false: the shape is not theirs (Nq > 64, head_dim % 64, > 512)
+bool launch_attn_cross_mfma_fwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const float* kbias, void* out,
+                                int64_t ldo, float* probs, int64_t B, int64_t Nq, int64_t L, int64_t H, int64_t dh, float scale,
+                                hipStream_t stream) {
+  if (dh % 64 || dh > 512 || Nq > 64 || ldq % 8 || ldkv % 8 || ldo % 4) return false;
+  const int lds = 64 * ASM_PITCH * 4 + (int)dh * 128;
+  static DevOnce once;
+  (void)dev_cus(once, [] {
+    (void)hipFuncSetAttribute((const void*)attn_cross_mfma_fwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * ASM_PITCH * 4 + 512 * 128);
+  });
+  hipLaunchKernelGGL(attn_cross_mfma_fwd_k, (int)(B * H), 256, lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq,
+                     ldkv, kbias, (bf16_t*)out, ldo, probs, (int)Nq, (int)L, (int)H, (int)dh, scale);
+  return true;
+}
+bool launch_attn_cross_mfma_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const void* dout, int64_t ldo,
+                                const float* probs, float* ds, void* dq, void* dk, void* dv, int64_t B, int64_t Nq, int64_t L, int64_t H,
+                                int64_t dh, float scale, hipStream_t stream) {
+  if (dh % 64 || dh > 512 || Nq > 64 || ldq % 8 || ldkv % 8 || ldo % 8) return false;
+  const int lds = 64 * ASM_PITCH * 4 + (int)dh * 128;
+  static DevOnce once;
+  (void)dev_cus(once, [] {
+    (void)hipFuncSetAttribute((const void*)attn_cross_mfma_bwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * ASM_PITCH * 4 + 512 * 128);
+  });
+  hipLaunchKernelGGL(attn_cross_mfma_bwd_k, (int)(B * H), 256, lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq,
+                     ldkv, (const bf16_t*)dout, ldo, probs, ds, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, (int)Nq, (int)L, (int)H, (int)dh,
+                     scale);
+  return true;
+}

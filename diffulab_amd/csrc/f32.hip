@@ -947,6 +947,71 @@ extern "C" int dl_f32_softmax_bwd(const float* p, float* dp, int64_t rows, int64
   return DL_OK;
 }
 
+// row softmax with a per-sample key bias (the boolean key mask of the UNet cross-attention, unet.py:306-316, as 0 / -inf): rows of
+// sample b = rows [b * rows_per_sample, (b + 1) * rows_per_sample) read bias[b, :]; a row whose every key is masked becomes zeros
+__global__ __launch_bounds__(256) void f32_softmax_keymask_fwd_k(float* __restrict__ s, const float* __restrict__ bias, int64_t rows,
+                                                                 int64_t rows_per_sample, int cols) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+    float* p = s + row * cols;
+    const float* bb = bias ? bias + (row / rows_per_sample) * cols : nullptr;
+    float mx = -INFINITY;
+    for (int c = lane; c < cols; c += 64) mx = fmaxf(mx, p[c] + (bb ? bb[c] : 0.f));
+    mx = wave_max(mx);
+    if (mx == -INFINITY) {
+      for (int c = lane; c < cols; c += 64) p[c] = 0.f;
+      continue;
+    }
+    float sum = 0.f;
+    for (int c = lane; c < cols; c += 64) sum += expf(p[c] + (bb ? bb[c] : 0.f) - mx);
+    const float inv = 1.0f / wave_sum(sum);
+    for (int c = lane; c < cols; c += 64) p[c] = expf(p[c] + (bb ? bb[c] : 0.f) - mx) * inv;
+  }
+}
+extern "C" int dl_f32_softmax_keymask_fwd(float* s, const float* key_bias, int64_t B, int64_t rows_per_sample, int64_t cols,
+                                          dl_stream_t stream) {
+  DL_CHECK_ARG(s && B > 0 && rows_per_sample > 0 && cols > 0 && cols < (1ll << 31) && (((uintptr_t)s | (uintptr_t)key_bias) & 3) == 0,
+               "dl_f32_softmax_keymask_fwd: B=%lld rows=%lld cols=%lld", (long long)B, (long long)rows_per_sample, (long long)cols);
+  hipLaunchKernelGGL(f32_softmax_keymask_fwd_k, grid_1d(B * rows_per_sample, 4, 16384), 256, 0, (hipStream_t)stream, s, key_bias,
+                     B * rows_per_sample, rows_per_sample, (int)cols);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// GEGLU unet.py:325-336 in f32: u [M, 2F] = [a | g] -> h [M, F] = a * gelu_erf(g); backward du [M, 2F] = [dh gelu(g) | dh a gelu'(g)]
+__device__ __forceinline__ float f32_gelu_erf(float g) { return 0.5f * g * (1.0f + erff(g * 0.70710678118654752f)); }
+__global__ void f32_geglu_fwd_k(const float* __restrict__ u, float* __restrict__ h, int64_t M, int F) {
+  const int64_t n = M * F;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / F;
+    const int c = (int)(i - r * F);
+    h[i] = u[r * 2 * F + c] * f32_gelu_erf(u[r * 2 * F + F + c]);
+  }
+}
+__global__ void f32_geglu_bwd_k(const float* __restrict__ dh, const float* __restrict__ u, float* __restrict__ du, int64_t M, int F) {
+  const int64_t n = M * F;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / F;
+    const int c = (int)(i - r * F);
+    const float a = u[r * 2 * F + c], g = u[r * 2 * F + F + c], d = dh[i];
+    const float cdf = 0.5f * (1.0f + erff(g * 0.70710678118654752f));
+    du[r * 2 * F + c] = d * g * cdf;
+    du[r * 2 * F + F + c] = d * a * (cdf + g * 0.39894228040143268f * expf(-0.5f * g * g));
+  }
+}
+extern "C" int dl_f32_geglu_fwd(const float* u, float* h, int64_t M, int64_t F, dl_stream_t stream) {
+  DL_CHECK_ARG(u && h && M > 0 && F > 0 && F < (1ll << 30), "dl_f32_geglu_fwd: bad args");
+  hipLaunchKernelGGL(f32_geglu_fwd_k, grid_1d(M * F), 256, 0, (hipStream_t)stream, u, h, M, (int)F);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_f32_geglu_bwd(const float* dh, const float* u, float* du, int64_t M, int64_t F, dl_stream_t stream) {
+  DL_CHECK_ARG(dh && u && du && M > 0 && F > 0 && F < (1ll << 30), "dl_f32_geglu_bwd: bad args");
+  hipLaunchKernelGGL(f32_geglu_bwd_k, grid_1d(M * F), 256, 0, (hipStream_t)stream, dh, u, du, M, (int)F);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
 // ============================================================================================================ elementwise
 // PackedSwiGLU nn.py:484-486: h = silu(u[:, :F]) * u[:, F:]
 __global__ void f32_swiglu_fwd_k(const float* __restrict__ u, float* __restrict__ h, int64_t M, int F) {

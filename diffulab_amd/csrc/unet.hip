@@ -1,9 +1,10 @@
 // UNet (guided-diffusion style) kernels that are not GEMMs: layout changes, GroupNorm32 (+FiLM +SiLU) fwd/bwd,
 // im2col for the 3x3 convolutions (the contraction itself runs on the MFMA GEMMs of gemm.hip), 2x2 pool / nearest
-// upsample, and the small-sequence attention of AttentionBlock (<= 64 tokens, head_dim up to 512).
+// upsample, the small-sequence attention of AttentionBlock (<= 64 tokens, head_dim up to 512), the masked cross-attention core and
+// the GEGLU of the TransformerBlock (context conditioning).
 // Activations are NHWC bf16 inside the library ([B*H*W, C] token rows: a 3x3 conv is then im2col + NT GEMM with
 // K = 9*C contiguous per tap); the reference's NCHW f32 tensors are converted at the model boundary.
-// Reference: networks/utils/nn.py:11-88, networks/denoisers/unet.py:215-237,296-322.
+// Reference: networks/utils/nn.py:11-88, networks/denoisers/unet.py:215-237,296-355.
 #include "common.h"
 
 static inline int grid_for(int64_t n, int threads = 256, int cap = 4096) {
@@ -1478,6 +1479,302 @@ extern "C" int dl_copy2d_bf16(const void* src, int64_t lds, void* dst, int64_t l
   DL_CHECK_ARG(src && dst && rows > 0 && cols > 0 && lds >= cols && ldd >= cols, "dl_copy2d_bf16: bad args");
   hipLaunchKernelGGL(copy2d_bf16_k, grid_for(rows * cols), 256, 0, (hipStream_t)stream, (const bf16_t*)src, lds, (bf16_t*)dst, ldd,
                      rows, (int)cols);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// ---------------------------------------------------------------- masked cross-attention core (TransformerBlock.cross_attn)
+// q: query token rows [B*Nq, ldq], k / v: context token rows [B*L, ldkv] (column windows of the to_kv output), head h at columns
+// [h*dh, (h+1)*dh); key_bias f32 [B, L] (0: attend, -inf: masked) or NULL.  A masked key has probability 0 exactly and adds nothing
+// (these VALU kernels do not even read its K / V rows), a row whose every key is masked gets zero probabilities, zero output and zero
+// gradients.  Nq <= 64 with head_dim % 64 == 0 runs on the MFMA kernels of csrc/attention.hip (the UNet configurations: dh 256 / 512);
+// the VALU kernels below take every other shape in the envelope: one workgroup per (sample, head, 16 query rows), the score rows in
+// the LDS, K and V streamed from L2 one row at a time, so any head width fits.
+#define AX_MAXL 512
+#define AX_QT 16
+#define AX_QB 8
+__global__ __launch_bounds__(256) void attn_cross_fwd_k(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                        const bf16_t* __restrict__ v, int64_t ldq, int64_t ldkv,
+                                                        const float* __restrict__ kbias, bf16_t* __restrict__ out, int64_t ldo,
+                                                        float* __restrict__ probs, int Nq, int L, int H, int dh, float scale) {
+  __shared__ float S[AX_QT][AX_MAXL + 1];
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const int i0 = blockIdx.y * AX_QT, nq = min(AX_QT, Nq - i0);
+  const bf16_t* qb = q + ((int64_t)b * Nq + i0) * ldq + h * dh;
+  const bf16_t* kb = k + (int64_t)b * L * ldkv + h * dh;
+  const bf16_t* vb = v + (int64_t)b * L * ldkv + h * dh;
+  const float* bb = kbias ? kbias + (int64_t)b * L : nullptr;
+  for (int idx = threadIdx.x; idx < nq * L; idx += 256) {
+    const int i = idx / L, j = idx % L;
+    const float bj = bb ? bb[j] : 0.f;
+    float s = -INFINITY;
+    if (bj != -INFINITY) {
+      float acc = 0.f;
+      for (int d = 0; d < dh; d += 8) {
+        float a[8], c[8];
+        unpack8(*(const u32x4_t*)(qb + (int64_t)i * ldq + d), a);
+        unpack8(*(const u32x4_t*)(kb + (int64_t)j * ldkv + d), c);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc += a[e] * c[e];
+      }
+      s = acc * scale + bj;
+    }
+    S[i][j] = s;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = wave; i < nq; i += 4) {  // one wave per score row
+    float mx = -INFINITY;
+    for (int j = lane; j < L; j += 64) mx = fmaxf(mx, S[i][j]);
+    mx = wave_max(mx);
+    float* prow = probs + ((int64_t)bh * Nq + i0 + i) * L;
+    if (mx == -INFINITY) {  // every key masked: zero probabilities (torch SDPA on CPU returns zeros for such rows)
+      for (int j = lane; j < L; j += 64) {
+        S[i][j] = 0.f;
+        prow[j] = 0.f;
+      }
+      continue;
+    }
+    float sum = 0.f;
+    for (int j = lane; j < L; j += 64) {
+      const float e = expf(S[i][j] - mx);
+      S[i][j] = e;
+      sum += e;
+    }
+    const float inv = 1.0f / wave_sum(sum);
+    for (int j = lane; j < L; j += 64) {
+      const float p = S[i][j] * inv;
+      S[i][j] = p;
+      prow[j] = p;
+    }
+  }
+  __syncthreads();
+  const int d8 = dh >> 3;
+  for (int idx = threadIdx.x; idx < nq * d8; idx += 256) {
+    const int i = idx / d8, dc = (idx % d8) * 8;
+    float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int j = 0; j < L; ++j) {
+      const float p = S[i][j];
+      if (p == 0.f) continue;  // masked keys (and underflowed ones) add nothing: their V rows are not read
+      float c[8];
+      unpack8(*(const u32x4_t*)(vb + (int64_t)j * ldkv + dc), c);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] += p * c[e];
+    }
+    *(u32x4_t*)(out + ((int64_t)b * Nq + i0 + i) * ldo + h * dh + dc) = pack8(o);
+  }
+}
+// backward, query side: dP = dO V^T over the kept probabilities, dS = P (dP - rowsum(P dP)) scale (written to ds [B, H, Nq, L] for the
+// key side), dQ = dS K; one workgroup per (sample, head, 8 query rows)
+__global__ __launch_bounds__(256) void attn_cross_bwd_q_k(const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int64_t ldkv,
+                                                          const bf16_t* __restrict__ dout, int64_t ldo, const float* __restrict__ probs,
+                                                          float* __restrict__ ds, bf16_t* __restrict__ dq, int64_t ldq, int Nq, int L,
+                                                          int H, int dh, float scale) {
+  __shared__ float P[AX_QB][AX_MAXL + 1];
+  __shared__ float D[AX_QB][AX_MAXL + 1];
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const int i0 = blockIdx.y * AX_QB, nq = min(AX_QB, Nq - i0);
+  const bf16_t* kb = k + (int64_t)b * L * ldkv + h * dh;
+  const bf16_t* vb = v + (int64_t)b * L * ldkv + h * dh;
+  const bf16_t* dob = dout + ((int64_t)b * Nq + i0) * ldo + h * dh;
+  const float* pb = probs + ((int64_t)bh * Nq + i0) * L;
+  for (int idx = threadIdx.x; idx < nq * L; idx += 256) {
+    const int i = idx / L, j = idx % L;
+    const float p = pb[(int64_t)i * L + j];
+    float s = 0.f;
+    if (p != 0.f) {
+      for (int d = 0; d < dh; d += 8) {
+        float a[8], c[8];
+        unpack8(*(const u32x4_t*)(dob + (int64_t)i * ldo + d), a);
+        unpack8(*(const u32x4_t*)(vb + (int64_t)j * ldkv + d), c);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += a[e] * c[e];
+      }
+    }
+    P[i][j] = p;
+    D[i][j] = s;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = wave; i < nq; i += 4) {
+    float dot = 0.f;
+    for (int j = lane; j < L; j += 64) dot += P[i][j] * D[i][j];
+    dot = wave_sum(dot);
+    float* dsrow = ds + ((int64_t)bh * Nq + i0 + i) * L;
+    for (int j = lane; j < L; j += 64) {
+      const float p = P[i][j];
+      const float g = p == 0.f ? 0.f : p * (D[i][j] - dot) * scale;
+      D[i][j] = g;
+      dsrow[j] = g;
+    }
+  }
+  __syncthreads();
+  const int d8 = dh >> 3;
+  for (int idx = threadIdx.x; idx < nq * d8; idx += 256) {
+    const int i = idx / d8, dc = (idx % d8) * 8;
+    float g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int j = 0; j < L; ++j) {
+      if (P[i][j] == 0.f) continue;
+      const float s = D[i][j];
+      float c[8];
+      unpack8(*(const u32x4_t*)(kb + (int64_t)j * ldkv + dc), c);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] += s * c[e];
+    }
+    *(u32x4_t*)(dq + ((int64_t)b * Nq + i0 + i) * ldq + h * dh + dc) = pack8(g);
+  }
+}
+// backward, key side: dK[j] = sum_i dS[i][j] Q[i], dV[j] = sum_i P[i][j] dO[i]; one thread per (key, 8 columns), every query row summed
+// in order (no atomics); masked keys get exact zeros
+__global__ __launch_bounds__(256) void attn_cross_bwd_kv_k(const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ dout,
+                                                           int64_t ldo, const float* __restrict__ probs, const float* __restrict__ ds,
+                                                           const float* __restrict__ kbias, bf16_t* __restrict__ dk,
+                                                           bf16_t* __restrict__ dv, int64_t ldkv, int Nq, int L, int H, int dh) {
+  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const int d8 = dh >> 3;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)L * d8) return;
+  const int j = (int)(idx / d8), dc = (int)(idx % d8) * 8;
+  float gk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (!(kbias && kbias[(int64_t)b * L + j] == -INFINITY)) {
+    const float* pc = probs + (int64_t)bh * Nq * L + j;
+    const float* sc = ds + (int64_t)bh * Nq * L + j;
+    const bf16_t* qb = q + (int64_t)b * Nq * ldq + h * dh + dc;
+    const bf16_t* db = dout + (int64_t)b * Nq * ldo + h * dh + dc;
+    for (int i = 0; i < Nq; ++i) {
+      const float p = pc[(int64_t)i * L];
+      if (p == 0.f) continue;
+      const float s = sc[(int64_t)i * L];
+      float qq[8], dd[8];
+      unpack8(*(const u32x4_t*)(qb + (int64_t)i * ldq), qq);
+      unpack8(*(const u32x4_t*)(db + (int64_t)i * ldo), dd);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        gk[e] += s * qq[e];
+        gv[e] += p * dd[e];
+      }
+    }
+  }
+  const int64_t o = ((int64_t)b * L + j) * ldkv + h * dh + dc;
+  *(u32x4_t*)(dk + o) = pack8(gk);
+  *(u32x4_t*)(dv + o) = pack8(gv);
+}
+// MFMA form for Nq <= 64, head_dim % 64 == 0 up to 512 (csrc/attention.hip); other shapes take the VALU kernels above
+bool launch_attn_cross_mfma_fwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const float* kbias, void* out,
+                                int64_t ldo, float* probs, int64_t B, int64_t Nq, int64_t L, int64_t H, int64_t dh, float scale,
+                                hipStream_t stream);
+bool launch_attn_cross_mfma_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const void* dout, int64_t ldo,
+                                const float* probs, float* ds, void* dq, void* dk, void* dv, int64_t B, int64_t Nq, int64_t L, int64_t H,
+                                int64_t dh, float scale, hipStream_t stream);
+static bool attn_cross_args_ok(const void* const* ptrs, int np, const int64_t* lds, int nl, int64_t dh) {
+  uintptr_t a = 0;
+  for (int i = 0; i < np; ++i) a |= (uintptr_t)ptrs[i];
+  int64_t l = dh;
+  for (int i = 0; i < nl; ++i) l |= lds[i];
+  return (a & 15) == 0 && (l & 7) == 0;
+}
+extern "C" int dl_attn_cross_fwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const float* key_bias, void* out,
+                                 int64_t ldo, float* probs, int64_t B, int64_t Nq, int64_t L, int64_t H, int64_t dh, float scale,
+                                 dl_stream_t stream) {
+  DL_CHECK_ARG(q && k && v && out && probs && B > 0 && Nq > 0 && L > 0 && L <= AX_MAXL && H > 0 && dh > 0 && dh % 8 == 0 &&
+                   ldq >= H * dh && ldkv >= H * dh && ldo >= H * dh && B * H < (1ll << 31) && (Nq + AX_QT - 1) / AX_QT < 65536,
+               "dl_attn_cross_fwd: Nq=%lld L=%lld (<= %d) H=%lld dh=%lld (%% 8)", (long long)Nq, (long long)L, AX_MAXL, (long long)H,
+               (long long)dh);
+  const void* p[] = {q, k, v, out};
+  const int64_t l[] = {ldq, ldkv, ldo};
+  DL_CHECK_ARG(attn_cross_args_ok(p, 4, l, 3, dh) && ((uintptr_t)key_bias & 3) == 0 && ((uintptr_t)probs & 3) == 0,
+               "dl_attn_cross_fwd: operands must be 16-byte aligned, leading dimensions multiples of 8");
+  if (launch_attn_cross_mfma_fwd(q, k, v, ldq, ldkv, key_bias, out, ldo, probs, B, Nq, L, H, dh, scale, (hipStream_t)stream)) {
+    DL_LAUNCH_CHECK();
+    return DL_OK;
+  }
+  hipLaunchKernelGGL(attn_cross_fwd_k, dim3((unsigned)(B * H), (unsigned)((Nq + AX_QT - 1) / AX_QT)), 256, 0, (hipStream_t)stream,
+                     (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldkv, key_bias, (bf16_t*)out, ldo, probs, (int)Nq,
+                     (int)L, (int)H, (int)dh, scale);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_attn_cross_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const float* key_bias,
+                                 const void* dout, int64_t ldo, const float* probs, float* ds, void* dq, void* dk, void* dv, int64_t B,
+                                 int64_t Nq, int64_t L, int64_t H, int64_t dh, float scale, dl_stream_t stream) {
+  DL_CHECK_ARG(q && k && v && dout && probs && ds && dq && dk && dv && B > 0 && Nq > 0 && L > 0 && L <= AX_MAXL && H > 0 && dh > 0 &&
+                   dh % 8 == 0 && ldq >= H * dh && ldkv >= H * dh && ldo >= H * dh && B * H < 65536 &&
+                   (Nq + AX_QB - 1) / AX_QB < 65536,
+               "dl_attn_cross_bwd: Nq=%lld L=%lld (<= %d) H=%lld dh=%lld (%% 8)", (long long)Nq, (long long)L, AX_MAXL, (long long)H,
+               (long long)dh);
+  const void* p[] = {q, k, v, dout, dq, dk, dv};
+  const int64_t l[] = {ldq, ldkv, ldo};
+  DL_CHECK_ARG(attn_cross_args_ok(p, 7, l, 3, dh) && ((uintptr_t)key_bias & 3) == 0 && (((uintptr_t)probs | (uintptr_t)ds) & 3) == 0,
+               "dl_attn_cross_bwd: operands must be 16-byte aligned, leading dimensions multiples of 8");
+  if (launch_attn_cross_mfma_bwd(q, k, v, ldq, ldkv, dout, ldo, probs, ds, dq, dk, dv, B, Nq, L, H, dh, scale, (hipStream_t)stream)) {
+    DL_LAUNCH_CHECK();
+    return DL_OK;
+  }
+  hipLaunchKernelGGL(attn_cross_bwd_q_k, dim3((unsigned)(B * H), (unsigned)((Nq + AX_QB - 1) / AX_QB)), 256, 0, (hipStream_t)stream,
+                     (const bf16_t*)k, (const bf16_t*)v, ldkv, (const bf16_t*)dout, ldo, probs, ds, (bf16_t*)dq, ldq, (int)Nq, (int)L,
+                     (int)H, (int)dh, scale);
+  DL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(attn_cross_bwd_kv_k, dim3((unsigned)((L * (dh / 8) + 255) / 256), (unsigned)(B * H)), 256, 0, (hipStream_t)stream,
+                     (const bf16_t*)q, ldq, (const bf16_t*)dout, ldo, probs, ds, key_bias, (bf16_t*)dk, (bf16_t*)dv, ldkv, (int)Nq,
+                     (int)L, (int)H, (int)dh);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// ---------------------------------------------------------------- GEGLU (FeedForward.net.0, unet.py:325-336)
+// u [M, ldu] = [a | g] (two column halves of F, not interleaved) -> h [M, ldh] = a * gelu_erf(g); backward du = [dh gelu(g) | dh a gelu'(g)]
+__device__ __forceinline__ float gelu_erf_f(float g) { return 0.5f * g * (1.0f + erff(g * 0.70710678118654752f)); }
+__device__ __forceinline__ float dgelu_erf_f(float g) {
+  return 0.5f * (1.0f + erff(g * 0.70710678118654752f)) + g * 0.39894228040143268f * expf(-0.5f * g * g);
+}
+__global__ void geglu_fwd_k(const bf16_t* __restrict__ u, int64_t ldu, bf16_t* __restrict__ h, int64_t ldh, int64_t M, int F8) {
+  const int64_t n = M * F8;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / F8;
+    const int c = (int)(i - r * F8) * 8;
+    float a[8], g[8], o[8];
+    unpack8(*(const u32x4_t*)(u + r * ldu + c), a);
+    unpack8(*(const u32x4_t*)(u + r * ldu + (int64_t)F8 * 8 + c), g);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = a[e] * gelu_erf_f(g[e]);
+    *(u32x4_t*)(h + r * ldh + c) = pack8(o);
+  }
+}
+__global__ void geglu_bwd_k(const bf16_t* __restrict__ dh, int64_t ldd, const bf16_t* __restrict__ u, int64_t ldu, bf16_t* __restrict__ du,
+                            int64_t lddu, int64_t M, int F8) {
+  const int64_t n = M * F8;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / F8;
+    const int c = (int)(i - r * F8) * 8;
+    float d[8], a[8], g[8], da[8], dg[8];
+    unpack8(*(const u32x4_t*)(dh + r * ldd + c), d);
+    unpack8(*(const u32x4_t*)(u + r * ldu + c), a);
+    unpack8(*(const u32x4_t*)(u + r * ldu + (int64_t)F8 * 8 + c), g);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      da[e] = d[e] * gelu_erf_f(g[e]);
+      dg[e] = d[e] * a[e] * dgelu_erf_f(g[e]);
+    }
+    *(u32x4_t*)(du + r * lddu + c) = pack8(da);
+    *(u32x4_t*)(du + r * lddu + (int64_t)F8 * 8 + c) = pack8(dg);
+  }
+}
+extern "C" int dl_geglu_fwd(const void* u, int64_t ldu, void* h, int64_t ldh, int64_t M, int64_t F, dl_stream_t stream) {
+  DL_CHECK_ARG(u && h && M > 0 && F > 0 && F % 8 == 0 && ldu >= 2 * F && ldh >= F && ((ldu | ldh) & 7) == 0 &&
+                   (((uintptr_t)u | (uintptr_t)h) & 15) == 0,
+               "dl_geglu_fwd: bad args (F, ld % 8, 16-byte aligned)");
+  hipLaunchKernelGGL(geglu_fwd_k, grid_for(M * F / 8), 256, 0, (hipStream_t)stream, (const bf16_t*)u, ldu, (bf16_t*)h, ldh, M,
+                     (int)(F / 8));
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_geglu_bwd(const void* dh, int64_t ldd, const void* u, int64_t ldu, void* du, int64_t lddu, int64_t M, int64_t F,
+                            dl_stream_t stream) {
+  DL_CHECK_ARG(dh && u && du && M > 0 && F > 0 && F % 8 == 0 && ldd >= F && ldu >= 2 * F && lddu >= 2 * F &&
+                   ((ldd | ldu | lddu) & 7) == 0 && (((uintptr_t)dh | (uintptr_t)u | (uintptr_t)du) & 15) == 0,
+               "dl_geglu_bwd: bad args (F, ld % 8, 16-byte aligned)");
+  hipLaunchKernelGGL(geglu_bwd_k, grid_for(M * F / 8), 256, 0, (hipStream_t)stream, (const bf16_t*)dh, ldd, (const bf16_t*)u, ldu,
+                     (bf16_t*)du, lddu, M, (int)(F / 8));
   DL_LAUNCH_CHECK();
   return DL_OK;
 }

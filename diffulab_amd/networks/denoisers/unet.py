@@ -10,8 +10,13 @@ parameters (views into one flat HBM arena); the arithmetic is the hand-written H
 
 Covered: FiLM (``use_scale_shift_norm=True``, what ``configs/model/unet.yaml`` builds) and additive conditioning, ResBlock
 resampling (``resblock_updown=True``) and the plain ``Downsample`` / ``Upsample`` modules with or without their 3x3 conv
-(``conv_resample``), labels or unconditional -- the constructor defaults included.  The cross-attention Transformer blocks of a
-context embedder and dropout > 0 raise ``NotImplementedError``.
+(``conv_resample``), labels or unconditional -- the constructor defaults included -- and text / multimodal conditioning through a
+parameter-free context embedder with one output (``context_embedder=``, ``transformer_depth=``): a ``TransformerBlock`` (unet.py:409-464:
+self-attention, masked cross-attention to the context tokens, GEGLU feed-forward) wherever an ``AttentionBlock`` would go, the middle
+block included.  The context contract is the reference's: ``embeddings`` channel-first ``[B, C_ctx, L]`` (a ``[B, L, C]`` tensor raises
+``ValueError``, nothing is transposed), ``attn_mask`` a boolean ``[B, L]`` (True = attend) or absent; a context model takes ``p = 0``
+only (unet.py:825-831), so guided sampling raises the reference's ``AssertionError``.  Dropout > 0, trainable or pooled-embedding
+context embedders raise ``NotImplementedError``.
 """
 
 from __future__ import annotations
@@ -54,13 +59,44 @@ class _Upsample(nn.Module):  # parameter holder for nn.py:28-56
 
 
 class _AttentionBlock(nn.Module):  # parameter holder for unet.py:240-322
-    def __init__(self, c: int) -> None:
+    def __init__(self, c: int, context_channels: int | None = None) -> None:
+        super().__init__()
+        cc = context_channels or c
+        self.norm_x = nn.GroupNorm(32, c)
+        self.norm_context = nn.GroupNorm(32, cc)
+        self.to_q = nn.Conv1d(c, c, 1)
+        self.to_kv = nn.Conv1d(cc, 2 * c, 1)
+        self.to_out = nn.Sequential(nn.Conv1d(c, c, 1), nn.Dropout(0.0))
+
+
+class _GEGLU(nn.Module):  # parameter holder for unet.py:325-336
+    def __init__(self, cin: int, cout: int) -> None:
+        super().__init__()
+        self.proj = nn.Conv1d(cin, 2 * cout, 1)
+
+
+class _FeedForward(nn.Module):  # parameter holder for unet.py:339-355
+    def __init__(self, c: int, inner: int) -> None:
+        super().__init__()
+        self.net = nn.Sequential(_GEGLU(c, inner), nn.Dropout(0.0), nn.Conv1d(inner, c, 1))
+        self.norm = nn.GroupNorm(32, c)
+
+
+class _TransformerAttentionBlock(nn.Module):  # parameter holder for unet.py:358-406
+    def __init__(self, c: int, context_channels: int) -> None:
+        super().__init__()
+        self.self_attn = _AttentionBlock(c)
+        self.cross_attn = _AttentionBlock(c, context_channels)
+        self.ff = _FeedForward(c, 4 * c)
+
+
+class _TransformerBlock(nn.Module):  # parameter holder for unet.py:409-464 (proj_out is not zero-initialised there)
+    def __init__(self, c: int, context_channels: int, depth: int) -> None:
         super().__init__()
         self.norm_x = nn.GroupNorm(32, c)
-        self.norm_context = nn.GroupNorm(32, c)
-        self.to_q = nn.Conv1d(c, c, 1)
-        self.to_kv = nn.Conv1d(c, 2 * c, 1)
-        self.to_out = nn.Sequential(nn.Conv1d(c, c, 1), nn.Dropout(0.0))
+        self.proj_in = nn.Conv2d(c, c, 1)
+        self.attn_blocks = nn.ModuleList([_TransformerAttentionBlock(c, context_channels) for _ in range(depth)])
+        self.proj_out = nn.Conv2d(c, c, 1)
 
 
 class UNetModel(FlatArenaDenoiser):
@@ -89,8 +125,11 @@ class UNetModel(FlatArenaDenoiser):
         super().__init__()
         assert not (n_classes is not None and context_embedder is not None), (
             "n_classes and context_embedder cannot both be specified")
-        if context_embedder is not None:
-            raise NotImplementedError("diffulab_amd.UNetModel: cross-attention context blocks (unet.py:358-465) are not built")
+        if context_embedder:
+            assert context_embedder.n_output == 1, (
+                "For UNet please provide a context embedder with n_output=1 (context and attention mask)")
+            if any(True for _ in context_embedder.parameters()):
+                raise NotImplementedError("diffulab_amd.UNetModel: the context embedder must be parameter-free (precomputed embeddings)")
         if dropout:
             raise NotImplementedError("diffulab_amd.UNetModel: dropout > 0 is not built (every reference config uses 0)")
         self.image_size = list(image_size)
@@ -104,7 +143,12 @@ class UNetModel(FlatArenaDenoiser):
         self.conv_resample = conv_resample
         self.use_checkpoint = use_checkpoint  # activations stay resident in HBM; nothing to checkpoint
         self.num_heads = num_heads
-        self.context_embedder = None
+        self.context_channels = None if context_embedder is None else int(context_embedder.output_size[0])
+        self.transformer_depth = transformer_depth
+        self.use_context = self.context_channels is not None
+        self.context_embedder = context_embedder
+        if self.use_context:
+            self.cfg_pair_capable = False  # p > 0 is refused for context models (unet.py:825-831): no batched guided pair either
         self.classifier_free = classifier_free
         self.n_classes = n_classes
         self.time_embed_dim = model_channels * 4
@@ -112,7 +156,8 @@ class UNetModel(FlatArenaDenoiser):
                              out_channels=out_channels, num_res_blocks=num_res_blocks,
                              attention_resolutions=tuple(self.attention_resolutions), channel_mult=tuple(self.channel_mult),
                              num_heads=num_heads, use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown,
-                             conv_resample=conv_resample, n_classes=n_classes, classifier_free=classifier_free)
+                             conv_resample=conv_resample, n_classes=n_classes, classifier_free=classifier_free,
+                             context_channels=self.context_channels, transformer_depth=transformer_depth)
         self.dims.validate()
 
         te = self.time_embed_dim
@@ -131,6 +176,8 @@ class UNetModel(FlatArenaDenoiser):
                     mods.append(_Downsample(b.cin, conv_resample))
                 elif b.kind == "up":
                     mods.append(_Upsample(b.cin, conv_resample))
+                elif b.kind == "xf":
+                    mods.append(_TransformerBlock(b.cin, self.context_channels, transformer_depth))
                 else:
                     mods.append(_AttentionBlock(b.cin))
             return nn.Sequential(*mods)
@@ -163,7 +210,8 @@ class UNetModel(FlatArenaDenoiser):
         x_context: Tensor | None = None,
     ) -> ModelOutput:
         assert (y is not None) == (self.n_classes is not None), "must specify y if and only if the model is class-conditional"
-        assert context is None, "must specify context if and only if the model is context-conditional"
+        assert (context is not None) == (self.context_embedder is not None), (
+            "must specify context if and only if the model is context-conditional")
         if p > 0:
             assert self.classifier_free, (
                 "probability of dropping for classifier free guidance is only available if model is set up to be classifier free")
@@ -178,4 +226,32 @@ class UNetModel(FlatArenaDenoiser):
         y_eff = None
         if self.label_embed is not None:
             y_eff = self._effective_labels(y.to(device=dev, dtype=torch.int64), p).contiguous()  # (drop_labels nn.py:149)
+        if self.context_embedder is not None:
+            self.engine.context = self._context_inputs(context, p, x.shape[0], dev)
         return {"x": self._run(x, t, y_eff)}
+
+    def _context_inputs(self, context: Any, p: float, B: int, dev: torch.device) -> tuple[Tensor, Tensor | None]:
+        """unet.py:838-841: the embedder runs host-side; -> (embeddings f32 [B, C_ctx, L], key bias f32 [B, L] (0 / -inf) or None)"""
+        out = self.context_embedder(context, p)
+        emb = out["embeddings"]
+        if emb.dim() != 3 or emb.shape[0] != B or emb.shape[1] != self.context_channels:
+            raise ValueError(f"diffulab_amd.UNetModel: context embeddings must be channel-first [B, C_ctx, L] = [{B}, "
+                             f"{self.context_channels}, L] (the reference's layout: they enter GroupNorm(32, C_ctx) and a Conv1d), got "
+                             f"{tuple(emb.shape)}")
+        emb = emb.to(device=dev, dtype=torch.float32).contiguous()
+        mask = out.get("attn_mask")
+        if mask is None:
+            return emb, None
+        if tuple(mask.shape) != (B, emb.shape[2]):
+            raise ValueError(f"diffulab_amd.UNetModel: attn_mask must be [B, L] = [{B}, {emb.shape[2]}], got {tuple(mask.shape)}")
+        keep = mask.to(device=dev).bool()
+        bias = torch.zeros(keep.shape, device=dev, dtype=torch.float32).masked_fill_(~keep, float("-inf"))
+        return emb, bias
+
+    # the context is a per-call input of the launch sequence: a captured graph reads static copies of it
+    def _graph_inputs(self, eng) -> tuple:
+        return tuple(eng.context) if self.use_context else ()
+
+    def _graph_set_inputs(self, eng, tensors: tuple) -> None:
+        if self.use_context:
+            eng.context = tuple(tensors)

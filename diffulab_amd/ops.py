@@ -65,12 +65,13 @@ class LaunchPlan:
     closure (`rec`); every buffer the calls name is kept alive by the plan (`keep`); per-call inputs live in static buffers the
     caller copies into before a replay."""
 
-    __slots__ = ("calls", "held", "state", "inputs", "out", "bwd")
+    __slots__ = ("calls", "held", "state", "inputs", "out", "bwd", "ctx")
 
     def __init__(self) -> None:
         self.calls: list = []
         self.held: list = []
         self.state = self.inputs = self.out = self.bwd = None
+        self.ctx = ()
 
     def replay(self) -> None:
         for fn, args in self.calls:
@@ -1021,6 +1022,30 @@ def attn_small_bwd(q, k, v, dout, probs, dq, dk, dv, B, n, H, dh):
           _p(dk), _p(dv), B, n, H, dh, float(dh) ** -0.5, _s())
 
 
+def attn_cross_fwd(q, k, v, key_bias, out, probs, B, Nq, L, H, dh):
+    """TransformerBlock cross-attention core (dl_attn_cross_fwd): q [B*Nq, >= H*dh], k / v [B*L, ...] bf16 rows, key_bias f32 [B, L] or None"""
+    _call("dl_attn_cross_fwd", _p(q), _p(k), _p(v), q.stride(0), k.stride(0), _p(key_bias), _p(out), out.stride(0), _p(probs), B, Nq,
+          L, H, dh, float(dh) ** -0.5, _s())
+
+
+def attn_cross_bwd(q, k, v, key_bias, dout, probs, ds, dq, dk, dv, B, Nq, L, H, dh):
+    """ds: f32 scratch [B, H, Nq, L]"""
+    assert dq.stride(0) == q.stride(0) and dk.stride(0) == k.stride(0) == dv.stride(0) == v.stride(0)
+    _call("dl_attn_cross_bwd", _p(q), _p(k), _p(v), q.stride(0), k.stride(0), _p(key_bias), _p(dout), dout.stride(0), _p(probs), _p(ds),
+          _p(dq), _p(dk), _p(dv), B, Nq, L, H, dh, float(dh) ** -0.5, _s())
+
+
+def geglu_fwd(u, h):
+    """u bf16 [M, 2F] (column windows allowed) -> h [M, F] = u[:, :F] * gelu(u[:, F:])"""
+    M, F = h.shape[0], h.shape[1]
+    _call("dl_geglu_fwd", _p(u), u.stride(0), _p(h), h.stride(0), M, F, _s())
+
+
+def geglu_bwd(dh, u, du):
+    M, F = dh.shape[0], dh.shape[1]
+    _call("dl_geglu_bwd", _p(dh), dh.stride(0), _p(u), u.stride(0), _p(du), du.stride(0), M, F, _s())
+
+
 def add_bf16(a, b, out):
     _call("dl_add_bf16", _p(a), _p(b), _p(out), a.numel(), _s())
 
@@ -1178,6 +1203,44 @@ def f32_softmax_fwd(s, rows, cols):
 
 def f32_softmax_bwd(p, dp, rows, cols):
     _call("dl_f32_softmax_bwd", _p(p), _p(dp), rows, cols, _s())
+
+
+def f32_softmax_keymask_fwd(s, key_bias, B, rows_per_sample, cols):
+    _call("dl_f32_softmax_keymask_fwd", _p(s), _p(key_bias), B, rows_per_sample, cols, _s())
+
+
+def f32_xattn_fwd(q, k, v, key_bias, out, probs, B, Nq, L, H, dh):
+    """masked cross-attention core (unet.py:306-318 with a context) over f32 token rows: Nq query rows, L context rows per sample, any
+    sizes; probs f32 [B, H, Nq, L] kept for the backward (f32_attn_bwd's batched GEMMs with the two token counts)"""
+    sc = float(dh) ** -0.5
+    f32_gemm(q, k, probs, Nq, L, dh, lda=q.stride(0), ldb=k.stride(0), ldc=L, batch=(B, H), sa=(Nq * q.stride(0), dh),
+             sb=(L * k.stride(0), dh), sc=(H * Nq * L, Nq * L), alpha=sc)
+    f32_softmax_keymask_fwd(probs, key_bias, B, H * Nq, L)
+    f32_gemm(probs, v, out, Nq, dh, L, lda=L, ldb=v.stride(0), ldc=out.stride(0), tb=True, batch=(B, H), sa=(H * Nq * L, Nq * L),
+             sb=(L * v.stride(0), dh), sc=(Nq * out.stride(0), dh))
+
+
+def f32_xattn_bwd(q, k, v, dout, probs, dP, dq, dk, dv, B, Nq, L, H, dh):
+    """dP: f32 scratch [B, H, Nq, L] (overwritten: dP, then dS).  Masked keys have P = 0, hence dS = 0 and zero dK / dV rows"""
+    sc = float(dh) ** -0.5
+    pb, hb = (H * Nq * L, Nq * L), dict(batch=(B, H))
+    f32_gemm(dout, v, dP, Nq, L, dh, lda=dout.stride(0), ldb=v.stride(0), ldc=L, sa=(Nq * dout.stride(0), dh),
+             sb=(L * v.stride(0), dh), sc=pb, **hb)                                                   # dP = dO V^T
+    f32_gemm(probs, dout, dv, L, dh, Nq, lda=L, ldb=dout.stride(0), ldc=dv.stride(0), ta=True, tb=True, sa=pb,
+             sb=(Nq * dout.stride(0), dh), sc=(L * dv.stride(0), dh), **hb)                           # dV = P^T dO
+    f32_softmax_bwd(probs, dP, B * H * Nq, L)                                                         # dS over dP
+    f32_gemm(dP, k, dq, Nq, dh, L, lda=L, ldb=k.stride(0), ldc=dq.stride(0), tb=True, sa=pb, sb=(L * k.stride(0), dh),
+             sc=(Nq * dq.stride(0), dh), alpha=sc, **hb)                                              # dQ = scale dS K
+    f32_gemm(dP, q, dk, L, dh, Nq, lda=L, ldb=q.stride(0), ldc=dk.stride(0), ta=True, tb=True, sa=pb,
+             sb=(Nq * q.stride(0), dh), sc=(L * dk.stride(0), dh), alpha=sc, **hb)                    # dK = scale dS^T Q
+
+
+def f32_geglu_fwd(u, h):
+    _call("dl_f32_geglu_fwd", _p(u), _p(h), u.shape[0], h.shape[1], _s())
+
+
+def f32_geglu_bwd(dh, u, du):
+    _call("dl_f32_geglu_bwd", _p(dh), _p(u), _p(du), u.shape[0], dh.shape[1], _s())
 
 
 def f32_swiglu_fwd(u, h):

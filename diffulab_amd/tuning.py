@@ -46,6 +46,9 @@ SWITCHES: dict[str, tuple[str, str]] = {
     "DL_UNET_SIDE": ("1", "UNet weight gradients on a side stream"),
     "DL_UNET_NT_PAIR": ("1", "UNet AttentionBlock: the q and kv projections (and their data gradients) as one launch of the 128 x 128 GEMM "
                         "kernel where both are small (dl_gemm_nt_pair: 64 + 128 tiles on 256 CUs at the 4 x 4 level); bit-identical"),
+    "DL_UNET_XATTN_HIP": ("1", "UNet TransformerBlock (context conditioning): the cross-attention core as dl_attn_cross_* (bf16 operands, f32 "
+                          "softmax; MFMA with the keys streamed in 64-key tiles where dh % 64 == 0, VALU otherwise) where Nq <= 64, L <= 512, "
+                          "dh % 8 == 0; 0 = the f32 copies + batched dl_f32_gemm + masked softmax fallback"),
     "DL_UNET_SPLITK": ("1", "split-K convolutions at the UNet's low-resolution levels (partial images + fixed-order fold: -7 % per step)"),
     "DL_UNET_WGRAD_WGS": ("128", "workgroup cap of the UNet's side-stream convolution weight gradients (0 = one per CU).  Round 6, with the "
                           "tap-reusing kernel and partial images (every workgroup stores its 295 KB of accumulators once, so the cap also "

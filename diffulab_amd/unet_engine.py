@@ -9,8 +9,13 @@ bf16 token rows so that 3x3 convolutions are im2col + MFMA GEMM with the residua
 
 Reference sites restated by the sequences below (``/root/reference/src/diffulab``): networks/denoisers/unet.py:593-745 (block
 wiring), :832-853 (forward), :215-237 (ResBlock._forward), :296-322 (AttentionBlock._forward); networks/utils/nn.py:11-88
-(GroupNorm32, Upsample, Downsample).  Only what ``configs/model/unet.yaml`` builds is covered: ``resblock_updown=True``,
-``use_scale_shift_norm=True``, class-conditional or unconditional, self-attention blocks (no context embedder).
+(GroupNorm32, Upsample, Downsample).  Covered: FiLM or additive conditioning, ResBlock or module resampling, class-conditional or
+unconditional, and either self-attention blocks or -- with a context embedder (``UNetDims.context_channels``) -- the
+``TransformerBlock`` of unet.py:358-464 at every attention stage: GroupNorm + 1x1 ``proj_in``, ``transformer_depth`` x (self-attention =
+the AttentionBlock sequence under its own prefix, masked cross-attention to the context tokens, GEGLU feed-forward), 1x1 ``proj_out`` +
+residual.  The context ``[B, C_ctx, L]`` becomes token rows ``[B*L, C_ctx]`` once per forward (``self.context`` holds it and the f32
+key bias ``[B, L]``, 0 / -inf, or None: per-call inputs that a launch plan or a captured graph reads from static copies); it receives
+no gradient, the ``norm_context`` affine parameters do.  A network without a context issues exactly the launch sequence it did before.
 """
 
 from __future__ import annotations
@@ -41,11 +46,15 @@ class UNetDims:
     conv_resample: bool = True  # read only when resblock_updown is False (unet.py:646,735)
     n_classes: int | None = None
     classifier_free: bool = False
+    context_channels: int | None = None  # C_ctx of the context embedder: TransformerBlocks replace the AttentionBlocks (unet.py:611-627)
+    transformer_depth: int = 1
 
     def validate(self) -> None:
         mc = self.model_channels
         if mc % 32:
             raise NotImplementedError("model_channels must be a multiple of 32 (GroupNorm32)")
+        if self.context_channels is not None and self.context_channels % 32:  # the reference's GroupNorm(32, C_ctx) raises this
+            raise ValueError("num_channels must be divisible by num_groups")
         down = 2 ** (len(self.channel_mult) - 1)
         if self.image_size[0] % down or self.image_size[1] % down:
             raise NotImplementedError("image size must be divisible by 2^(levels-1)")
@@ -60,7 +69,7 @@ class UNetDims:
 
 @dataclass
 class _Blk:
-    kind: str  # "conv" | "res" | "attn" | "down" | "up" (the last two: Downsample / Upsample modules, nn.py:28-88)
+    kind: str  # "conv" | "res" | "attn" | "xf" | "down" | "up" ("xf": TransformerBlock unet.py:409-464; "down" / "up": nn.py:28-88)
     prefix: str
     cin: int = 0
     cout: int = 0
@@ -81,8 +90,9 @@ class _Plan:
 
 
 def build_plan(d: UNetDims) -> _Plan:
-    """module wiring of unet.py:593-745 without a context embedder"""
+    """module wiring of unet.py:593-745 (TransformerBlocks in place of the AttentionBlocks with a context embedder)"""
     mc = d.model_channels
+    attn = "attn" if d.context_channels is None else "xf"
     plan = _Plan()
     ch = int(d.channel_mult[0] * mc)
     plan.input_blocks.append([_Blk("conv", "input_blocks.0.0.", d.in_channels, ch)])
@@ -93,7 +103,7 @@ def build_plan(d: UNetDims) -> _Plan:
             layers = [_Blk("res", f"input_blocks.{i}.0.", ch, int(mult * mc))]
             ch = int(mult * mc)
             if ds in d.attention_resolutions:
-                layers.append(_Blk("attn", f"input_blocks.{i}.1.", ch, ch))
+                layers.append(_Blk(attn, f"input_blocks.{i}.1.", ch, ch))
             plan.input_blocks.append(layers)
             chans.append(ch)
         if level != len(d.channel_mult) - 1:
@@ -102,7 +112,7 @@ def build_plan(d: UNetDims) -> _Plan:
                                       else _Blk("down", f"input_blocks.{i}.0.", ch, ch)])
             chans.append(ch)
             ds *= 2
-    plan.middle = [_Blk("res", "middle_block.0.", ch, ch), _Blk("attn", "middle_block.1.", ch, ch),
+    plan.middle = [_Blk("res", "middle_block.0.", ch, ch), _Blk(attn, "middle_block.1.", ch, ch),
                    _Blk("res", "middle_block.2.", ch, ch)]
     for level, mult in list(enumerate(d.channel_mult))[::-1]:
         for k in range(d.num_res_blocks + 1):
@@ -111,7 +121,7 @@ def build_plan(d: UNetDims) -> _Plan:
             layers = [_Blk("res", f"output_blocks.{i}.0.", ch + ich, int(mc * mult))]
             ch = int(mc * mult)
             if ds in d.attention_resolutions:
-                layers.append(_Blk("attn", f"output_blocks.{i}.{len(layers)}.", ch, ch))
+                layers.append(_Blk(attn, f"output_blocks.{i}.{len(layers)}.", ch, ch))
             if level and k == d.num_res_blocks:
                 layers.append(_Blk("res", f"output_blocks.{i}.{len(layers)}.", ch, ch, up=True) if d.resblock_updown
                               else _Blk("up", f"output_blocks.{i}.{len(layers)}.", ch, ch))
@@ -129,6 +139,13 @@ def build_plan(d: UNetDims) -> _Plan:
 def emb_width(d: UNetDims, b: _Blk) -> int:
     """rows of emb_layers.1 (unet.py:161-166): [scale | shift] under FiLM, one additive term otherwise"""
     return 2 * b.cout if d.use_scale_shift_norm else b.cout
+
+
+def xf_subblocks(d: UNetDims, b: _Blk) -> list[tuple[_Blk, _Blk, str]]:
+    """(self_attn, cross_attn, ff prefix) of every TransformerAttentionBlock of a TransformerBlock (unet.py:358-406)"""
+    return [(_Blk("attn", f"{b.prefix}attn_blocks.{j}.self_attn.", b.cin, b.cin),
+             _Blk("xattn", f"{b.prefix}attn_blocks.{j}.cross_attn.", b.cin, b.cin), f"{b.prefix}attn_blocks.{j}.ff.")
+            for j in range(d.transformer_depth)]
 
 
 def resample_conv(b: _Blk) -> str:
@@ -149,6 +166,18 @@ class UNetLayout:
             self.size = _rup(self.size, align)
             self.entries[name] = (self.size, shape)
             self.size += math.prod(shape)
+
+        def attn(p: str, c: int, cc: int) -> None:  # AttentionBlock unet.py:240-322 (cc: channels of the context it attends to)
+            add(p + "norm_x.weight", (c,))
+            add(p + "norm_x.bias", (c,))
+            add(p + "norm_context.weight", (cc,))
+            add(p + "norm_context.bias", (cc,))
+            add(p + "to_q.weight", (c, c, 1))
+            add(p + "to_q.bias", (c,))
+            add(p + "to_kv.weight", (2 * c, cc, 1))
+            add(p + "to_kv.bias", (2 * c,))
+            add(p + "to_out.0.weight", (c, c, 1))
+            add(p + "to_out.0.bias", (c,))
 
         res = [b for b in plan.all_blocks() if b.kind == "res"]
         for i, b in enumerate(res):
@@ -184,17 +213,25 @@ class UNetLayout:
                 if d.conv_resample:
                     add(resample_conv(b) + "weight", (b.cout, b.cin, 3, 3))
                     add(resample_conv(b) + "bias", (b.cout,))
-            else:
+            elif b.kind == "attn":
+                attn(p, b.cin, b.cin)
+            else:  # TransformerBlock (unet.py:409-464)
                 c = b.cin
-                for n in ("norm_x", "norm_context"):
-                    add(p + n + ".weight", (c,))
-                    add(p + n + ".bias", (c,))
-                add(p + "to_q.weight", (c, c, 1))
-                add(p + "to_q.bias", (c,))
-                add(p + "to_kv.weight", (2 * c, c, 1))
-                add(p + "to_kv.bias", (2 * c,))
-                add(p + "to_out.0.weight", (c, c, 1))
-                add(p + "to_out.0.bias", (c,))
+                add(p + "norm_x.weight", (c,))
+                add(p + "norm_x.bias", (c,))
+                add(p + "proj_in.weight", (c, c, 1, 1))
+                add(p + "proj_in.bias", (c,))
+                for sa, xa, ff in xf_subblocks(d, b):
+                    attn(sa.prefix, c, c)
+                    attn(xa.prefix, c, d.context_channels)
+                    add(ff + "net.0.proj.weight", (8 * c, c, 1))  # GEGLU(c, 4c) (unet.py:325-355)
+                    add(ff + "net.0.proj.bias", (8 * c,))
+                    add(ff + "net.2.weight", (c, 4 * c, 1))
+                    add(ff + "net.2.bias", (c,))
+                    add(ff + "norm.weight", (c,))
+                    add(ff + "norm.bias", (c,))
+                add(p + "proj_out.weight", (c, c, 1, 1))
+                add(p + "proj_out.bias", (c,))
         add("out.0.weight", (plan.final_ch,))
         add("out.0.bias", (plan.final_ch,))
         add("out.2.weight", (d.out_channels, int(d.channel_mult[0] * d.model_channels), 3, 3))
@@ -226,6 +263,7 @@ class UNetEngine:
         self._saved: dict | None = None
         self._zero = torch.zeros(64, device=self.dev, dtype=torch.bfloat16)  # out-of-image taps of the implicit-GEMM convs
         self.o = ops  # resampling / layout / attention entry points of the block orchestration (the fp32 engine swaps in f32 forms)
+        self.context: tuple = (None, None)  # context models: (embeddings f32 [B, C_ctx, L], key bias f32 [B, L] or None) of the next forward
         self._build_shadows()
 
     # ------------------------------------------------------------------ parameters
@@ -277,11 +315,22 @@ class UNetEngine:
             elif b.kind in ("down", "up"):
                 if d.conv_resample:
                     conv(resample_conv(b) + "weight", b.cout, b.cin)
-            else:
+            elif b.kind == "attn":
                 c = b.cin
                 lin(p + "to_q.weight", c, c)
                 lin(p + "to_kv.weight", 2 * c, c)
                 lin(p + "to_out.0.weight", c, c)
+            else:
+                c = b.cin
+                lin(p + "proj_in.weight", c, c)
+                for sa, xa, ff in xf_subblocks(d, b):
+                    for a, cc in ((sa, c), (xa, d.context_channels)):
+                        lin(a.prefix + "to_q.weight", c, c)
+                        lin(a.prefix + "to_kv.weight", 2 * c, cc)
+                        lin(a.prefix + "to_out.0.weight", c, c)
+                    lin(ff + "net.0.proj.weight", 8 * c, c)
+                    lin(ff + "net.2.weight", c, 4 * c)
+                lin(p + "proj_out.weight", c, c)
         conv("out.2.weight", d.out_channels, int(d.channel_mult[0] * d.model_channels))
 
     def refresh_shadows(self, force: bool = False) -> None:
@@ -739,6 +788,139 @@ class UNetEngine:
         dx = self._gn_bwd(dnx, x, st, B, n, c, p + "norm_x.", silu=False, dres=dout)
         return self._gn_bwd(dnc, x, st, B, n, c, p + "norm_context.", silu=False, dres=dx)
 
+    # ---- TransformerBlock (unet.py:358-464): context conditioning.  self._xctx = {"rows": context token rows [B*L, C_ctx], "bias": f32
+    #      key bias [B, L] or None, "L": L, "st": GroupNorm statistics of the rows (shared by every norm_context: same input)}
+    def _xattn_hip_ok(self, n: int, L: int, dh: int) -> bool:
+        return self.precision != "fp32" and n <= 64 and L <= 512 and dh % 8 == 0 and tuning.on("DL_UNET_XATTN_HIP")
+
+    def _xattn_core_fwd(self, q: Tensor, kv: Tensor, bias: Tensor | None, att: Tensor, probs: Tensor, B: int, n: int, L: int, nh: int,
+                        c: int) -> None:
+        if self.precision == "fp32":
+            ops.f32_xattn_fwd(q, kv[:, :c], kv[:, c:], bias, att, probs, B, n, L, nh, c // nh)
+            return
+        if self._xattn_hip_ok(n, L, c // nh):
+            ops.attn_cross_fwd(q, kv[:, :c], kv[:, c:], bias, att, probs, B, n, L, nh, c // nh)
+            return
+        qf = self._scr("xattn_qf", B * n * c, torch.float32).view(B * n, c)
+        kvf = self._scr("xattn_kvf", B * L * 2 * c, torch.float32).view(B * L, 2 * c)
+        of = self._scr("xattn_of", B * n * c, torch.float32).view(B * n, c)
+        ops.cast_bf16_to_f32(q, qf)
+        ops.cast_bf16_to_f32(kv, kvf)
+        ops.f32_xattn_fwd(qf, kvf[:, :c], kvf[:, c:], bias, of, probs, B, n, L, nh, c // nh)
+        ops.cast_f32_to_bf16(of, att)
+
+    def _xattn_core_bwd(self, q: Tensor, kv: Tensor, bias: Tensor | None, datt: Tensor, probs: Tensor, dq: Tensor, dkv: Tensor, B: int,
+                        n: int, L: int, nh: int, c: int) -> None:
+        dP = self._scr("xattn_dp", B * nh * n * L, torch.float32).view(B, nh, n, L)
+        if self.precision == "fp32":
+            ops.f32_xattn_bwd(q, kv[:, :c], kv[:, c:], datt, probs, dP, dq, dkv[:, :c], dkv[:, c:], B, n, L, nh, c // nh)
+            return
+        if self._xattn_hip_ok(n, L, c // nh):
+            ops.attn_cross_bwd(q, kv[:, :c], kv[:, c:], bias, datt, probs, dP, dq, dkv[:, :c], dkv[:, c:], B, n, L, nh, c // nh)
+            return
+        qf = self._scr("xattn_qf", B * n * c, torch.float32).view(B * n, c)
+        kvf = self._scr("xattn_kvf", B * L * 2 * c, torch.float32).view(B * L, 2 * c)
+        df = self._scr("xattn_of", B * n * c, torch.float32).view(B * n, c)
+        dqf = self._scr("xattn_dqf", B * n * c, torch.float32).view(B * n, c)
+        dkvf = self._scr("xattn_dkvf", B * L * 2 * c, torch.float32).view(B * L, 2 * c)
+        ops.cast_bf16_to_f32(q, qf)
+        ops.cast_bf16_to_f32(kv, kvf)
+        ops.cast_bf16_to_f32(datt, df)
+        ops.f32_xattn_bwd(qf, kvf[:, :c], kvf[:, c:], df, probs, dP, dqf, dkvf[:, :c], dkvf[:, c:], B, n, L, nh, c // nh)
+        ops.cast_f32_to_bf16(dqf, dq)
+        ops.cast_f32_to_bf16(dkvf, dkv)
+
+    def _xattn_fwd(self, b: _Blk, x: Tensor, B: int, n: int, save: list) -> Tensor:
+        """AttentionBlock._forward with a context (unet.py:296-322): q from GN(x), k / v from norm_context(context) through to_kv"""
+        p, c, nh, cc = b.prefix, b.cin, self.d.num_heads, self.d.context_channels
+        xc = self._xctx
+        L, rows = xc["L"], xc["rows"]
+        nx, st = self._gn(x, B, n, c, p + "norm_x.", silu=False)
+        nc, xc["st"] = self._gn(rows, B, L, cc, p + "norm_context.", silu=False, stats=xc["st"])
+        q = self._lin_fwd(nx, p + "to_q.weight", c, c)
+        kv = self._lin_fwd(nc, p + "to_kv.weight", 2 * c, cc)
+        att = self._new(B * n, c)
+        probs = self._new(B, nh, n, L, dtype=torch.float32)
+        self._xattn_core_fwd(q, kv, xc["bias"], att, probs, B, n, L, nh, c)
+        out = self._lin_fwd(att, p + "to_out.0.weight", c, c, resid=x)
+        save.append((x, st, nx, nc, q, kv, att, probs))
+        return out
+
+    def _xattn_bwd(self, b: _Blk, dout: Tensor, B: int, n: int, saved) -> Tensor:
+        p, c, nh, cc = b.prefix, b.cin, self.d.num_heads, self.d.context_channels
+        xc = self._xctx
+        L = xc["L"]
+        x, st, nx, nc, q, kv, att, probs = saved
+        datt = self._lin_bwd(dout, att, p + "to_out.0.weight", c, c)
+        dq, dkv = self._new(B * n, c), self._new(B * L, 2 * c)
+        self._xattn_core_bwd(q, kv, xc["bias"], datt, probs, dq, dkv, B, n, L, nh, c)
+        dnx = self._lin_bwd(dq, nx, p + "to_q.weight", c, c)
+        dnc = self._lin_bwd(dkv, nc, p + "to_kv.weight", 2 * c, cc)
+        # (only the affine gradients are kept: the context gets none.  The GroupNorm backward also writes a [B*L, C_ctx] data gradient
+        #  that is dropped -- 2 * B * L * C_ctx bytes per cross-attention, ~7.6 MB at B = 64, L = 77, C_ctx = 768: below 1 % of the step)
+        self._gn_bwd(dnc, xc["rows"], xc["st"], B, L, cc, p + "norm_context.", silu=False)
+        return self._gn_bwd(dnx, x, st, B, n, c, p + "norm_x.", silu=False, dres=dout)
+
+    def _ff_fwd(self, p: str, x: Tensor, B: int, n: int, save: list) -> Tensor:
+        """FeedForward unet.py:339-355: x + net.2(GEGLU(net.0.proj(GN(x))))"""
+        c = x.shape[1]
+        hn, st = self._gn(x, B, n, c, p + "norm.", silu=False)
+        u = self._lin_fwd(hn, p + "net.0.proj.weight", 8 * c, c)
+        g = self._new(B * n, 4 * c)
+        self.o.geglu_fwd(u, g)
+        out = self._lin_fwd(g, p + "net.2.weight", c, 4 * c, resid=x)
+        save.append((x, st, hn, u, g))
+        return out
+
+    def _ff_bwd(self, p: str, dout: Tensor, B: int, n: int, saved) -> Tensor:
+        x, st, hn, u, g = saved
+        c = x.shape[1]
+        dg = self._lin_bwd(dout, g, p + "net.2.weight", c, 4 * c)
+        du = self._new(B * n, 8 * c)
+        self.o.geglu_bwd(dg, u, du)
+        dhn = self._lin_bwd(du, hn, p + "net.0.proj.weight", 8 * c, c)
+        return self._gn_bwd(dhn, x, st, B, n, c, p + "norm.", silu=False, dres=dout)
+
+    def _xf_fwd(self, b: _Blk, x: Tensor, B: int, H: int, W: int, save: list | None) -> Tensor:
+        """TransformerBlock.forward (unet.py:452-464)"""
+        p, c, n = b.prefix, b.cin, H * W
+        sub: list = []
+        h0, st = self._gn(x, B, n, c, p + "norm_x.", silu=False)
+        h = self._lin_fwd(h0, p + "proj_in.weight", c, c)
+        for sa, xa, ff in xf_subblocks(self.d, b):  # TransformerAttentionBlock.forward (unet.py:398-406)
+            h = self._attn_fwd(sa, h, B, H, W, sub)
+            h = self._xattn_fwd(xa, h, B, n, sub)
+            h = self._ff_fwd(ff, h, B, n, sub)
+        out = self._lin_fwd(h, p + "proj_out.weight", c, c, resid=x)
+        if save is not None:
+            save.append((x, st, h0, h, sub, H, W))
+        return out
+
+    def _xf_bwd(self, b: _Blk, dout: Tensor, B: int, saved) -> Tensor:
+        p, c = b.prefix, b.cin
+        x, st, h0, h, sub, H, W = saved
+        n = H * W
+        sub = list(sub)
+        dh = self._lin_bwd(dout, h, p + "proj_out.weight", c, c)
+        for sa, xa, ff in xf_subblocks(self.d, b)[::-1]:
+            dh = self._ff_bwd(ff, dh, B, n, sub.pop())
+            dh = self._xattn_bwd(xa, dh, B, n, sub.pop())
+            dh = self._attn_bwd(sa, dh, B, sub.pop())
+        dh0 = self._lin_bwd(dh, h0, p + "proj_in.weight", c, c)
+        return self._gn_bwd(dh0, x, st, B, n, c, p + "norm_x.", silu=False, dres=dout)
+
+    def _context_rows(self, B: int) -> dict | None:
+        """self.context = (embeddings f32 [B, C_ctx, L], key bias f32 [B, L] or None) -> the per-forward context state"""
+        if self.d.context_channels is None:
+            return None
+        ctx, bias = self.context
+        assert ctx.shape[0] == B and ctx.shape[1] == self.d.context_channels and ctx.dtype == torch.float32 and ctx.is_contiguous()
+        L = ctx.shape[2]
+        assert bias is None or (bias.shape == (B, L) and bias.dtype == torch.float32 and bias.is_contiguous())
+        rows = self._new(B * L, self.d.context_channels)
+        self.o.nchw_to_nhwc(ctx, rows, B, self.d.context_channels, L)
+        return dict(rows=rows, bias=bias, L=L, st=None)
+
     def _group_fwd(self, blocks: list[_Blk], h: Tensor, B: int, H: int, W: int, eo: Tensor, save: list | None):
         for b in blocks:
             if b.kind == "conv":
@@ -749,6 +931,8 @@ class UNetEngine:
                 h, H, W = self._res_fwd(b, h, B, H, W, eo, save)
             elif b.kind in ("down", "up"):
                 h, H, W = self._resample_fwd(b, h, B, H, W, save)
+            elif b.kind == "xf":
+                h = self._xf_fwd(b, h, B, H, W, save)
             else:
                 h = self._attn_fwd(b, h, B, H, W, save)
         return h, H, W
@@ -763,6 +947,8 @@ class UNetEngine:
                 dh = self._res_bwd(b, dh, B, s, eo, deo)
             elif b.kind in ("down", "up"):
                 dh = self._resample_bwd(b, dh, B, s)
+            elif b.kind == "xf":
+                dh = self._xf_bwd(b, dh, B, s)
             else:
                 dh = self._attn_bwd(b, dh, B, s)
         return dh
@@ -810,8 +996,10 @@ class UNetEngine:
             return self._forward_pass(x, t, y_eff, train, refresh)
         if refresh:
             self.refresh_shadows(force=True)  # (outside the plan: whether the shadows are stale is per-call state)
+        ctx = self.context if self.d.context_channels is not None else ()
         key = (tuple(x.shape), x.dtype, t.dtype, None if y_eff is None else y_eff.dtype, ops._s(), self.params.data_ptr(),
-               0 if self.grads is None else self.grads.data_ptr(), id(self.reducer))
+               0 if self.grads is None else self.grads.data_ptr(), id(self.reducer),
+               tuple(None if c is None else tuple(c.shape) for c in ctx))  # (context models: L and C_ctx, whether a mask is given)
         plans = self.__dict__.setdefault("_launch_plans", {})
         ent = plans.get(key)
         if ent is None or ent is False:  # first pass of this shape: eager (scratch buffers, tables and stages come into being)
@@ -824,12 +1012,18 @@ class UNetEngine:
         if ent == 1:  # second pass: record it
             lp = ops.LaunchPlan()
             lp.inputs = (x.detach().clone(), t.detach().clone(), None if y_eff is None else y_eff.detach().clone())
+            lp.ctx = tuple(None if c is None else c.detach().clone() for c in ctx)  # the context the plan reads: copied in before replay
+            if ctx:
+                self.context = lp.ctx
             try:
                 with ops.recording(lp):
                     lp.out = self._forward_pass(*lp.inputs, True, False)
             except Exception:
                 plans[key] = False
                 raise
+            finally:
+                if ctx:
+                    self.context = ctx
             lp.state = self._saved
             plans[key] = self._cur_plan = lp
             return lp.out
@@ -839,6 +1033,9 @@ class UNetEngine:
         ts.copy_(t)
         if ys is not None:
             ys.copy_(y_eff)
+        for st, cur in zip(lp.ctx, ctx):
+            if st is not None:
+                st.copy_(cur)
         lp.replay()
         self._saved, self._cur_plan = lp.state, lp
         return lp.out
@@ -876,6 +1073,7 @@ class UNetEngine:
         save: list | None = [] if train else None
 
         eo, cs = self._cond_fwd(t, y_eff, B)
+        self._xctx = self._context_rows(B)
 
         h = self._new(B * H * W, Cin)
         self.o.nchw_to_nhwc(x, h, B, Cin, H * W)
@@ -897,7 +1095,7 @@ class UNetEngine:
         pred = self._new(B, d.out_channels, H, W, dtype=torch.float32)
         self.o.nhwc_to_nchw(o, pred, B, d.out_channels, H * W)
         if train:
-            self._saved = dict(B=B, H=H, W=W, save=save, eo=eo, y=y_eff, h=h, stf=stf, hf=hf, **cs)
+            self._saved = dict(B=B, H=H, W=W, save=save, eo=eo, y=y_eff, h=h, stf=stf, hf=hf, xctx=self._xctx, **cs)
         return pred
 
     # ------------------------------------------------------------------ backward
@@ -912,6 +1110,7 @@ class UNetEngine:
             for g in self.__dict__.get("_stage", {}).values():
                 g.zero_()
         B, H, W, save, eo = s["B"], s["H"], s["W"], s["save"], s["eo"]
+        self._xctx = s["xctx"]
         mc, te = d.model_channels, 4 * d.model_channels
         Bp = _rup(B, 64)
         R = self.layout.emb_rows

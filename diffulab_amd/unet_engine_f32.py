@@ -2,14 +2,15 @@
 BASELINE configuration 1, train_mnist_ddpm.yaml, inherits it).
 
 `UNetEngineF32` is `unet_engine.UNetEngine` with every primitive replaced by its f32 form (csrc/f32.hip): the block orchestration
-(`_res_fwd` / `_res_bwd`, `_resample_*`, `_attn_*`, the skip-connection bookkeeping of forward / backward) is inherited unchanged, so
+(`_res_fwd` / `_res_bwd`, `_resample_*`, `_attn_*`, the TransformerBlock's `_xf_*` / `_xattn_*` / `_ff_*`, the skip-connection bookkeeping of forward / backward) is inherited unchanged, so
 the two regimes cannot drift apart structurally.  Differences:
   * activations are NHWC f32 rows; a 3x3 convolution (unet.py:187,208,594,745) is `dl_f32_im2col3x3` + `dl_f32_gemm` against the weight
     in its NATIVE [Co, Ci*9] layout (no shadows), its data gradient `dl_f32_gemm` + `dl_f32_col2im3x3`, its weight gradient
     `dl_f32_gemm` accumulated straight into the gradient arena; 1x1 convolutions and Linear layers are `dl_f32_gemm` on the arena;
   * GroupNorm32 / FiLM (nn.py:11-13, unet.py:215-237) are `dl_f32_gn_*` (one workgroup per (sample, group), per-sample partials of the
     affine gradients folded in a fixed order); the AttentionBlock (unet.py:296-322) is the strided batched `dl_f32_gemm` over
-    materialised probabilities + `dl_f32_softmax_*`, like the fp32 DiT;
+    materialised probabilities + `dl_f32_softmax_*`, like the fp32 DiT; the TransformerBlock's cross-attention the same with L context
+    tokens and `dl_f32_softmax_keymask_fwd` (unet.py:306-318), its GEGLU `dl_f32_geglu_*` (unet.py:325-336);
   * nothing runs on a side stream and nothing is accumulated through atomics: a step is bit-reproducible.
 """
 
@@ -58,6 +59,10 @@ class _F32Ops:
     # AttentionBlock core (unet.py:311-318): any token count / head width (ops.f32_attn_fwd / f32_attn_bwd)
     attn_small_fwd = staticmethod(ops.f32_attn_fwd)
 
+    # TransformerBlock feed-forward (unet.py:325-336)
+    geglu_fwd = staticmethod(ops.f32_geglu_fwd)
+    geglu_bwd = staticmethod(ops.f32_geglu_bwd)
+
     def attn_small_bwd(self, q, k, v, dout, probs, dq, dk, dv, B, n, H, dh):
         dP = self.eng._scr("attn_dp", B * H * n * n, torch.float32).view(B, H, n, n)
         ops.f32_attn_bwd(q, k, v, dout, probs, dP, dq, dk, dv, B, n, H, dh)
@@ -81,6 +86,7 @@ class UNetEngineF32(UNetEngine):
         self._saved: dict | None = None
         self.o = _F32Ops(self)
         self.sh = {}
+        self.context: tuple = (None, None)
 
     # ------------------------------------------------------------------ parameters: the GEMMs read the f32 arena directly
     def bind(self, params: Tensor, grads: Tensor | None) -> None:

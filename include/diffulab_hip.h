@@ -613,6 +613,24 @@ DL_API int dl_attn_small_fwd(const void* q, const void* k, const void* v, int64_
 DL_API int dl_attn_small_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const void* dout,
                              int64_t ldo, const float* probs, void* dq, void* dk, void* dv, int64_t B, int64_t n,
                              int64_t H, int64_t dh, float scale, dl_stream_t stream);
+/* TransformerBlock cross-attention core (unet.py:296-318 with context: q from the image tokens, k / v from the context tokens, boolean
+ * key mask attn_mask[B, L] expanded over the queries, scale = dh^-0.5): q token rows [B*Nq, ldq], k / v context token rows [B*L, ldkv]
+ * (column windows of the to_kv output), head h at columns [h*dh, (h+1)*dh); key_bias f32 [B, L] (0 = attend, -inf = masked) or NULL.
+ * L <= 512, dh % 8 == 0, any Nq; MFMA (32x32x16 bf16, keys streamed in tiles of 64) where Nq <= 64 and dh % 64 == 0 up to 512, f32 VALU
+ * otherwise; probs f32 [B, H, Nq, L] is kept for the backward.  A masked key has probability 0 and contributes exact zeros; a query
+ * row with every key masked gets zero output and zero gradients (what SDPA returns on CPU).
+ * Backward: ds f32 [B, H, Nq, L] scratch (dS, overwritten); dq, dk, dv WRITTEN (no atomics). */
+DL_API int dl_attn_cross_fwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const float* key_bias,
+                             void* out, int64_t ldo, float* probs, int64_t B, int64_t Nq, int64_t L, int64_t H, int64_t dh,
+                             float scale, dl_stream_t stream);
+DL_API int dl_attn_cross_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const float* key_bias,
+                             const void* dout, int64_t ldo, const float* probs, float* ds, void* dq, void* dk, void* dv,
+                             int64_t B, int64_t Nq, int64_t L, int64_t H, int64_t dh, float scale, dl_stream_t stream);
+/* GEGLU unet.py:325-336 (FeedForward.net.0 after its Conv1d): u [M, ldu] = [a | g], two column halves of F (chunk(2, dim=1), not
+ * interleaved) -> h [M, ldh] = a * gelu_erf(g); backward du [M, lddu] = [dh * gelu(g) | dh * a * gelu'(g)].  F, ld % 8 == 0 */
+DL_API int dl_geglu_fwd(const void* u, int64_t ldu, void* h, int64_t ldh, int64_t M, int64_t F, dl_stream_t stream);
+DL_API int dl_geglu_bwd(const void* dh, int64_t ldd, const void* u, int64_t ldu, void* du, int64_t lddu, int64_t M, int64_t F,
+                        dl_stream_t stream);
 /* out = a + b (bf16): gradient fan-in of the UNet skip connections (unet.py:846-851: hs.append / torch.cat) */
 DL_API int dl_add_bf16(const void* a, const void* b, void* out, int64_t n, dl_stream_t stream);
 /* dst[r, c] = src[r, c] for a [rows, cols] window of two pitched bf16 matrices: channel concat / split of the skip
@@ -698,6 +716,14 @@ DL_API int dl_f32_ddt_cond_bwd(const float* dsz, const float* enc, int64_t ld, c
 /* softmax over the last dimension of the scaled scores (mmdit.py:92-100), in place; backward dS = P (dP - rowsum(dP P)) over dP */
 DL_API int dl_f32_softmax_fwd(float* s, int64_t rows, int64_t cols, dl_stream_t stream);
 DL_API int dl_f32_softmax_bwd(const float* p, float* dp, int64_t rows, int64_t cols, dl_stream_t stream);
+/* softmax of the UNet cross-attention scores (unet.py:306-316: boolean key mask attn_mask[B, L] broadcast over heads and queries),
+ * in place over s [B, rows_per_sample, cols]: row r of sample b = softmax(s[b, r, :] + key_bias[b, :]), key_bias f32 [B, cols]
+ * (0 / -inf) or NULL; a row whose every key is masked becomes zeros.  The backward is dl_f32_softmax_bwd. */
+DL_API int dl_f32_softmax_keymask_fwd(float* s, const float* key_bias, int64_t B, int64_t rows_per_sample, int64_t cols,
+                                      dl_stream_t stream);
+/* GEGLU unet.py:325-336 in f32: u [M, 2F] = [a | g] -> h [M, F] = a * gelu_erf(g); backward du [M, 2F] */
+DL_API int dl_f32_geglu_fwd(const float* u, float* h, int64_t M, int64_t F, dl_stream_t stream);
+DL_API int dl_f32_geglu_bwd(const float* dh, const float* u, float* du, int64_t M, int64_t F, dl_stream_t stream);
 /* PackedSwiGLU nn.py:484-486 in f32: u [M, 2F] -> h [M, F]; backward du [M, 2F] */
 DL_API int dl_f32_swiglu_fwd(const float* u, float* h, int64_t M, int64_t F, dl_stream_t stream);
 DL_API int dl_f32_swiglu_bwd(const float* dh, const float* u, float* du, int64_t M, int64_t F, dl_stream_t stream);

@@ -14,6 +14,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_paths.h"
+
+// the path code of the last GEMM-family launch (gemm_paths.h): one relaxed host-side store per call, read by the tests
+static std::atomic<int> g_last_path{DL_PATH_NONE};
+void dl_note_path(int path) { g_last_path.store(path, std::memory_order_relaxed); }
+extern "C" __attribute__((visibility("default"))) int dl_lab_last_path() { return g_last_path.load(std::memory_order_relaxed); }
 
 #define BM 128
 #define BN 128
@@ -711,6 +717,7 @@ static int launch_big(const void* A, int64_t lda, const void* B, int64_t ldb, vo
   // phase skew of the tile starts (sleep units per k-step and phase group): pays only when every workgroup walks many tiles
   // (measured: MLP-up)
   ep.stagger = (ntiles >= 6 * grid) ? 2 : 0;
+  if (epi != 3 || TN_ == 384) dl_note_path(TN_ == 384 ? NT_BIG_384 : TN_ == 256 ? NT_BIG_256 : TN_ == 192 ? NT_BIG_192 : NT_BIG_128);
 #define BIG_GO(E)                                                                                                     \
   hipLaunchKernelGGL((gemm_nt_big_k<TN_, NST, E>), grid, BIG_THREADS, LDS, stream, (const bf16_t*)A, lda, (const bf16_t*)B, \
                      ldb, C, ldc, (int)M, (int)N, (int)K, ep)
@@ -763,15 +770,18 @@ static int dispatch_big(const void* A, int64_t lda, const void* B, int64_t ldb, 
 
 static int g_nt_deep = 1;  // LAB A/B switch (not in the header): 0 = the two-slot ring everywhere
 extern "C" __attribute__((visibility("default"))) void dl_lab_set_nt_deep(int on) { g_nt_deep = on; }
-// the 128 x 128 kernel: the four-slot ring when the launch is at most one workgroup per CU (and deep enough to have a steady state)
+// the 128 x 128 kernel: the four-slot ring when the launch is at most one workgroup per CU (and deep enough to have a steady state);
+// `path2` = the caller's path code of the two-slot form (the four-slot form is the next code)
 template <bool CONV>
 static void launch_nt_small(dim3 grid, hipStream_t stream, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int64_t ldc,
-                            int M, int N, int K, const NtEpilogue& ep, int ksplit, const ConvGeom& cg) {
+                            int M, int N, int K, const NtEpilogue& ep, int ksplit, const ConvGeom& cg, int path2) {
   static DevOnce once;
   const int n_cu = dev_cus(once, [] {
     (void)hipFuncSetAttribute((const void*)gemm_nt_k<CONV, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
   });
-  if (g_nt_deep && (int64_t)grid.x * grid.y <= n_cu && K / BK / ksplit >= 4)
+  const bool deep = g_nt_deep && (int64_t)grid.x * grid.y <= n_cu && K / BK / ksplit >= 4;
+  dl_note_path(path2 + (deep ? 1 : 0));
+  if (deep)
     hipLaunchKernelGGL((gemm_nt_k<CONV, 4>), grid, NT_THREADS, 4 * 32768, stream, A, lda, B, ldb, C, ldc, M, N, K, ep, ksplit, cg);
   else
     hipLaunchKernelGGL((gemm_nt_k<CONV, 2>), grid, NT_THREADS, NT_LDS_BYTES, stream, A, lda, B, ldb, C, ldc, M, N, K, ep, ksplit, cg);
@@ -814,7 +824,7 @@ extern "C" int dl_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb
     }
   }
   launch_nt_small<false>(dim3(nwg, ksplit), (hipStream_t)stream, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, (int)M, (int)N, (int)K, ep,
-                         ksplit, ConvGeom{});
+                         ksplit, ConvGeom{}, ksplit > 1 ? NT_SPLITK_RING2 : NT_SMALL_RING2);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
@@ -844,6 +854,7 @@ extern "C" int dl_gemm_nt_pair(const dl_nt_problem_t* p, int n, dl_stream_t stre
                                 nullptr, p[i].resid, p[i].ldr, nullptr, 0, 1, stream);
       if (rc != DL_OK) return rc;
     }
+    dl_note_path(NT_PAIR_FALLBACK);  // (after the two calls, which note their own paths)
     return DL_OK;
   }
   // the product with the shallower contraction goes first: launch_nt_small picks the ring depth from the K it is given (a four-slot
@@ -854,7 +865,7 @@ extern "C" int dl_gemm_nt_pair(const dl_nt_problem_t* p, int n, dl_stream_t stre
   ep.lda2 = p[g].lda, ep.ldb2 = p[g].ldb, ep.ldc2 = p[g].ldc, ep.ldr2 = p[g].ldr;
   ep.M2 = (int)p[g].M, ep.N2 = (int)p[g].N, ep.K2 = (int)p[g].K, ep.tiles0 = (int)nwg[f];
   launch_nt_small<false>(dim3((unsigned)(nwg[0] + nwg[1]), 1), (hipStream_t)stream, (const bf16_t*)p[f].A, p[f].lda, (const bf16_t*)p[f].B, p[f].ldb,
-                         p[f].C, p[f].ldc, (int)p[f].M, (int)p[f].N, (int)p[f].K, ep, 1, ConvGeom{});
+                         p[f].C, p[f].ldc, (int)p[f].M, (int)p[f].N, (int)p[f].K, ep, 1, ConvGeom{}, NT_PAIR_RING2);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
@@ -1281,6 +1292,7 @@ extern "C" int dl_gemm_tn_ex(const void* A, int64_t lda, const void* B, int64_t 
       const int sps = (nsteps + splits - 1) / splits;
       splits = (nsteps + sps - 1) / sps;
       const int units = (tiles_m * splits + 7) & ~7;  // surplus units exit at once
+      dl_note_path(TN_BIG);
       hipLaunchKernelGGL(gemm_tn_big_k<false>, units * (int)(N / WBN), BIG_THREADS, 2 * W_STAGE, (hipStream_t)stream,
                          (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, (int)M, (int)N, (int)R, sps, ConvGeom{}, (int64_t)0);
       DL_LAUNCH_CHECK();
@@ -1295,6 +1307,7 @@ extern "C" int dl_gemm_tn_ex(const void* A, int64_t lda, const void* B, int64_t 
   if (g_tn_split_model) splits = tn_pick_splits(ntile, nsteps, M * N, 512, 0.4, splits);  // (two workgroups per CU: 64 KiB of LDS each)
   const int sps = (nsteps + splits - 1) / splits;
   splits = (nsteps + sps - 1) / sps;
+  dl_note_path(splits > 1 ? TN_SMALL_SPLITK : TN_SMALL);
   hipLaunchKernelGGL(gemm_tn_k<false>, ntile * splits, NT_THREADS, 65536, (hipStream_t)stream, (const bf16_t*)A, lda,
                      (const bf16_t*)B, ldb, C, ldc, (int)M, (int)N, (int)R, sps, ConvGeom{}, (int64_t)0);
   DL_LAUNCH_CHECK();
@@ -1381,6 +1394,7 @@ extern "C" int dl_gemm_tn_det(const void* A, int64_t lda, const void* B, int64_t
   if (splits < 1) splits = 1;
   const int sps = (nsteps + splits - 1) / splits;
   splits = (nsteps + sps - 1) / sps;  // every split owns at least one step
+  dl_note_path(TN_DET);
   hipLaunchKernelGGL(gemm_tn_k<false>, ntile * splits, NT_THREADS, 65536, (hipStream_t)stream, (const bf16_t*)A, lda,
                      (const bf16_t*)B, ldb, scratch, N, (int)M, (int)N, (int)R, sps, ConvGeom{}, (int64_t)(M * N));
   DL_LAUNCH_CHECK();
@@ -1404,6 +1418,7 @@ extern "C" int dl_gemm_nt_f32_det(const void* A, int64_t lda, const void* B, int
   NtEpilogue ep{};
   ep.out_f32 = 1;
   ep.rows_per_gate = 1;
+  dl_note_path(ksplit == 1 ? NT_DET : NT_DET_SPLITK);
   if (ksplit == 1) {
     hipLaunchKernelGGL(gemm_nt_k<false>, dim3(nwg, 1), NT_THREADS, NT_LDS_BYTES, (hipStream_t)stream, (const bf16_t*)A, lda,
                        (const bf16_t*)B, ldb, C, ldc, (int)M, (int)N, (int)K, ep, 1, ConvGeom{});
@@ -1623,6 +1638,7 @@ static int launch_conv_big(const void* x, const void* Wf, int64_t ldw, void* C, 
   const int64_t items = (M / TBM) * (N / TN_) * ksplit;
   int grid = (int)(items < n_cu ? items : n_cu) & ~7;
   if (grid < 8) return 1;
+  dl_note_path(TN_ == 256 ? (ksplit > 1 ? CONV_BIG_256_SPLITK : CONV_BIG_256) : (ksplit > 1 ? CONV_BIG_128_SPLITK : CONV_BIG_128));
   hipLaunchKernelGGL((conv3x3_big_k<TN_>), grid, BIG_THREADS, LDS, stream, (const bf16_t*)x, (const bf16_t*)Wf, ldw, C, ldc, (int)M, (int)N,
                      (int)K, ep, ksplit, cg);
   DL_LAUNCH_CHECK();
@@ -1837,6 +1853,7 @@ static int launch_conv_halo(const void* x, const void* Wf, int64_t ldw, void* C,
   const int64_t items = (M / TBM) * (N / TN_);
   int grid = (int)(items < n_cu ? items : n_cu) & ~7;
   if (grid < 8) return 1;
+  dl_note_path(TN_ == 256 ? CONV_HALO_256_2 : NST == 4 ? CONV_HALO_128_4 : NST == 3 ? CONV_HALO_128_3 : CONV_HALO_128_2);
   hipLaunchKernelGGL((conv3x3_halo_k<TN_, NST>), grid, BIG_THREADS, LDS, stream, (const bf16_t*)x, (const bf16_t*)Wf, ldw, C, ldc, (int)M, (int)N, ep,
                      cg, nrow, nseg, nchunks);
   DL_LAUNCH_CHECK();
@@ -1963,7 +1980,7 @@ extern "C" int dl_conv3x3_nt(const void* x, int64_t ldx, int64_t Bn, int64_t H, 
     ep0.rows_per_gate = 1;
     ep0.part_stride = M * Co;
     launch_nt_small<true>(dim3(nwg, ksplit), (hipStream_t)stream, (const bf16_t*)x, ldx, (const bf16_t*)Wf, ldw, splitk_scratch, Co, (int)M,
-                          (int)Co, (int)K, ep0, ksplit, cg);
+                          (int)Co, (int)K, ep0, ksplit, cg, CONV_SPLITK_RING2);
     int64_t g = (M * (Co / 8) + 255) / 256;
     if (g > 4096) g = 4096;
     hipLaunchKernelGGL(conv_splitk_finalize_k, (int)g, 256, 0, (hipStream_t)stream, splitk_scratch, ksplit, M * Co, bias,
@@ -1973,7 +1990,7 @@ extern "C" int dl_conv3x3_nt(const void* x, int64_t ldx, int64_t Bn, int64_t H, 
   }
   NtEpilogue ep{bias, DL_ACT_NONE, 0, nullptr, (const bf16_t*)resid, ldr, nullptr, 0, 1, nullptr, 0, 0};
   launch_nt_small<true>(dim3(nwg, 1), (hipStream_t)stream, (const bf16_t*)x, ldx, (const bf16_t*)Wf, ldw, out, ldc, (int)M, (int)Co, (int)K, ep, 1,
-                        cg);
+                        cg, CONV_SMALL_RING2);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }

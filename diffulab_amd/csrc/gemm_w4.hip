@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_paths.h"
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
@@ -387,6 +388,7 @@ int launch_tn_w4(const void* A, int64_t lda, const void* B, int64_t ldb, float* 
     splits = (nsteps + sps - 1) / sps;
     grid = ((tiles_m * splits + 7) & ~7) * tiles_n;  // surplus units exit at once
   }
+  dl_note_path(TN_W4);
   hipLaunchKernelGGL(gemm_tn_w4_k, grid, W4_WAVES * 64, W4_LDS, stream, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, (int)M,
                      (int)N, (int)R, sps, spx);
   if (hipGetLastError() != hipSuccess) return DL_ERR_LAUNCH;
@@ -459,6 +461,7 @@ extern "C" int dl_gemm_tn_group(const dl_wgrad_t* probs, int n_probs, int64_t R,
   g.nsteps = nsteps;
   g.slab_stride = total;
   g.slab = slab;
+  dl_note_path(t384 ? TN_GROUP_384 : t256 ? TN_GROUP_256 : TN_GROUP_256_EDGE);
   if (t384)
     hipLaunchKernelGGL((gemm_tn_group_k<384, 192>), splits * ntile, W4_WAVES * 64, W4_LDS, (hipStream_t)stream, g);
   else

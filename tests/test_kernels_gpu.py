@@ -176,16 +176,23 @@ def test_two_small_products_in_one_launch_equal_their_separate_launches(ops, M, 
         b_ = synth.normal(f"pr.b{tag}", (N,), std=0.1).to(DEV) if bias else None
         r_ = dev_bf(bf(synth.normal(f"pr.r{tag}{M}", (M, N)))) if resid else None
         return a, w, b_, r_
+    from elementwise_bounds import is_poison, poison_
+
     p0, p1 = mk("0", N0, K0), mk("1", N1, K1)
     sep = []
     for a, w, b_, r_ in (p0, p1):
-        o = torch.full((M, w.shape[0] + 8), 7.0, device=DEV, dtype=torch.bfloat16)
+        o = poison_(torch.empty((M, w.shape[0] + 8), device=DEV, dtype=torch.bfloat16))  # pad columns: a NaN no kernel writes
         ops.gemm_nt(a, w, o[:, : w.shape[0]], bias=b_, resid=r_)
         sep.append(o)
-    outs = [torch.full((M, N0 + 8), 7.0, device=DEV, dtype=torch.bfloat16), torch.full((M, N1 + 8), 7.0, device=DEV, dtype=torch.bfloat16)]
+    outs = [poison_(torch.empty((M, N0 + 8), device=DEV, dtype=torch.bfloat16)), poison_(torch.empty((M, N1 + 8), device=DEV, dtype=torch.bfloat16))]
     ops.gemm_nt_pair([(p0[0], p0[1], outs[0][:, :N0], p0[2], p0[3], None, None, None), (p1[0], p1[1], outs[1][:, :N1], p1[2], p1[3], None, None, None)])
     torch.cuda.synchronize()
-    assert torch.equal(outs[0], sep[0]) and torch.equal(outs[1], sep[1])
+    for o, N in ((outs[0], N0), (outs[1], N1), (sep[0], N0), (sep[1], N1)):
+        assert bool(is_poison(o[:, N:]).all()), "a pad column was written"
+        assert bool(torch.isfinite(o[:, :N].float()).all())
+    assert torch.equal(outs[0][:, :N0], sep[0][:, :N0]) and torch.equal(outs[1][:, :N1], sep[1][:, :N1])
+    # the whole buffers bit for bit (through int16 views: the pads hold NaN)
+    assert torch.equal(outs[0].view(torch.int16), sep[0].view(torch.int16)) and torch.equal(outs[1].view(torch.int16), sep[1].view(torch.int16))
     ref = p1[0].float() @ p1[1].float().t() + (p1[2] if bias else 0) + (p1[3].float() if resid else 0)
     assert rel(outs[1][:, :N1].float(), ref) < 5e-3
 

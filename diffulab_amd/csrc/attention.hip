@@ -17,6 +17,8 @@
 // two workgroups share a CU, so one head's tile loads overlap the other's MFMA phases.
 // Longer sequences (multiples of 256 up to 2048 tokens): `*_tiled_k` below run the same wave-level algorithms with one
 // workgroup per (batch, head, 256-row chunk) that streams the other operand through LDS in 256-row chunks.
+// Beyond 2048 tokens (up to 32768): `*_long_k` -- the forward double-buffers its K / V stream, the backward computes delta in a
+// pre-pass and splits dK / dV and dQ into two launches, so that no LDS array grows with N.
 #include "common.h"
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -66,6 +68,12 @@ __device__ __forceinline__ bf16x8_t frag_cols(const char* tile, int rbase, int c
   u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s16x4_t*)(tile + r1 * ROWB + (((col >> 3) ^ swz8(r1)) << 4) + (col & 7) * 2));
   return u.v;
+}
+// frag_cols' transposing read as inline asm: the compiler sees no LDS read, so puts no wait for an in-flight DMA in front of it
+__device__ __forceinline__ s16x4_t attn_lds_tr16(const char* p) {
+  s16x4_t v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"((unsigned)(uintptr_t)(lds_void_t*)p));
+  return v;
 }
 __device__ __forceinline__ bf16x8_t pack_frag(const float* p) {
   union {
@@ -319,14 +327,180 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
   if (hi == 0) lse[(int64_t)bh * Nq + qrow] = (m_run + log2f(l_tot)) * LN2;
 }
 
-/* general form: Nq queries against Nk keys (both multiples of 256, <= 2048) with an optional additive key bias f32 [B, Nk]
- * (0 = keep, -inf = masked / padded key): cross-attention and key-padding masks */
+// ------------------------------------------------------------------------------ forward, very long sequences (max(Nq, Nk) > 2048)
+// Flash-style: one 8-wave workgroup per (batch, head, 256-query chunk), Q in registers, K / V / key bias streamed in 128-key
+// chunks through two LDS buffers: the DMA of chunk i + 1 is requested right after the barrier that opens chunk i, so it is in
+// flight under chunk i's MFMA / softmax work (65 KiB of LDS whatever N: two workgroups per CU).  The arithmetic per 64-key block is
+// attn_fwd_tiled_k's.  As in attn_fwd_qkn_pipe_k the V fragments are read with inline-asm transposing reads and an explicit lgkmcnt
+// wait, so that the compiler puts no vmcnt(0) (= a wait for the prefetch) in front of them.  The key bias is DMA'd too (dword
+// lanes), raw: it is scaled by log2(e) where it is read.
+#define LCH 128                     // keys per streamed chunk
+#define LBUF (2 * LCH * ROWB + LCH * 4)  // bytes per LDS buffer: K, V, key bias
+#define ATTN_MAX_N 32768            // longest Nq / Nk the long-sequence kernels take
+__device__ __forceinline__ bf16x8_t frag_cols_asm(const char* tile, int rbase, int colbase, int lane) {
+  const int li = lane & 15, g = lane >> 4;
+  const int col = colbase + (g & 1) * 16 + (li & 3) * 4;
+  const int r0 = rbase + (g >> 1) * 4 + (li >> 2), r1 = r0 + 8;
+  union {
+    s16x4_t h[2];
+    bf16x8_t v;
+  } u;
+  u.h[0] = attn_lds_tr16(tile + r0 * ROWB + (((col >> 3) ^ swz8(r0)) << 4) + (col & 7) * 2);
+  u.h[1] = attn_lds_tr16(tile + r1 * ROWB + (((col >> 3) ^ swz8(r1)) << 4) + (col & 7) * 2);
+  return u.v;
+}
+template <bool BIAS>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void attn_fwd_long_k(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, bf16_t* __restrict__ out,
+    float* __restrict__ lse, int H, int Nq, int Nk, float scale, const float* __restrict__ key_bias) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nchq = Nq / ACH, nch = Nk / LCH;
+  const int bh = blockIdx.x / nchq, qc = blockIdx.x - bh * nchq, b = bh / H, h = bh - b * H;
+  const bf16_t* qg = q + (int64_t)bh * Nq * DH;
+  const bf16_t* kg = k + (int64_t)bh * Nk * DH;
+  const bf16_t* vg = v + (int64_t)bh * Nk * DH;
+  const float* bg = BIAS ? key_bias + (int64_t)b * Nk : nullptr;
+  const int q0 = qc * ACH + wave * 32;
+  bf16x8_t qf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8_t*)(qg + (int64_t)(q0 + (lane & 31)) * DH + ks * 16 + hi * 8);
+  // tile_dma's addressing for this kernel's fixed geometry (8 waves, 128 rows: rows 8 c .. 8 c + 7 for c = wave, wave + 8): the lane
+  // part of the source offset is the same for both row groups and both operands.  Nothing here may be a spill reload: its
+  // vmcnt(0) between two requests would wait for the first.
+  auto issue = [&](int kc, int buf) {
+    char* kt = smem + buf * LBUF;
+    int ln = lane;
+    asm volatile("" : "+v"(ln));  // opaque: keeps the compiler from hoisting 64-bit lane addresses out of the loop (they spill)
+    const int dma_lane = (ln >> 3) * DH + (((ln & 7) ^ swz8(wave * 8 + (ln >> 3))) << 3);
+    const int dma_bias_lane = wave * 64 + ln;
+    // (the bias first: anything the compiler inserts in front of a later request waits for the earlier ones)
+    if (BIAS && wave < LCH / 64)
+      __builtin_amdgcn_global_load_lds((glb_void_t*)(bg + kc * LCH + dma_bias_lane), (lds_void_t*)(kt + 2 * LCH * ROWB + wave * 256),
+                                       4, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int cidx = wave + 8 * i;
+      const int64_t row0 = (int64_t)kc * LCH + cidx * 8;
+      __builtin_amdgcn_global_load_lds((glb_void_t*)(kg + row0 * DH + dma_lane), (lds_void_t*)(kt + cidx * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((glb_void_t*)(vg + row0 * DH + dma_lane), (lds_void_t*)(kt + LCH * ROWB + cidx * 1024), 16, 0, 0);
+    }
+  };
+  issue(0, 0);
+  const float c = scale * LOG2E;
+  f32x16_t o[2];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) o[0][r] = o[1][r] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+#pragma unroll 1
+  for (int kc = 0; kc < nch; ++kc) {
+    const char* kt = smem + (kc & 1) * LBUF;
+    const char* vt = kt + LCH * ROWB;
+    const float* bs = (const float*)(vt + LCH * ROWB);
+    // chunk kc was requested one chunk ago and nothing younger is in flight; the barrier also retires every wave's reads of the
+    // other buffer (chunk kc - 1), which the next request overwrites
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (kc + 1 < nch) issue(kc + 1, (kc + 1) & 1);
+#pragma unroll 1
+    for (int kb = 0; kb < LCH; kb += 64) {
+      f32x16_t s[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[t][r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) s[t] = MFMA(frag_rows(kt, kb + t * 32 + (lane & 31), ks, hi), qf[ks], s[t]);
+      }
+      float mx = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          f32x4_t b4 = {0.f, 0.f, 0.f, 0.f};
+          if (BIAS) b4 = *(const f32x4_t*)(bs + kb + t * 32 + g4 * 8 + hi * 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = g4 * 4 + e;
+            s[t][r] = BIAS ? s[t][r] * c + b4[e] * LOG2E : s[t][r] * c;
+            mx = fmaxf(mx, s[t][r]);
+          }
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      float m_new = fmaxf(m_run, mx);
+      if (m_new == -INFINITY) m_new = 0.f;  // every key so far is masked: keep exp2(-inf - m) = 0 well defined
+      const float alpha = fast_exp2(m_run - m_new);
+      m_run = m_new;
+      float ps = 0.f;
+      float p[2][16];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          p[t][r] = fast_exp2(s[t][r] - m_new);
+          ps += p[t][r];
+        }
+      l_run = l_run * alpha + ps;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        o[0][r] *= alpha;
+        o[1][r] *= alpha;
+      }
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {  // V fragments 32 keys at a time (all 64 keys' would spill at 128 VGPRs)
+        bf16x8_t vf[2][2];
+#pragma unroll
+        for (int kg2 = 0; kg2 < 2; ++kg2)
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) vf[kg2][cb] = frag_cols_asm(vt, kb + t * 32 + kg2 * 16, cb * 32, lane);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int kg2 = 0; kg2 < 2; ++kg2)
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) asm volatile("" : "+v"(vf[kg2][cb]));  // (no MFMA on these registers above the wait)
+#pragma unroll
+        for (int kg2 = 0; kg2 < 2; ++kg2) {
+          const bf16x8_t pf = pack_frag(&p[t][kg2 * 8]);
+          o[0] = MFMA(vf[kg2][0], pf, o[0]);
+          o[1] = MFMA(vf[kg2][1], pf, o[1]);
+        }
+      }
+    }
+  }
+  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+  const float inv = 1.0f / l_tot;
+  const int qrow = q0 + (lane & 31);
+  store_rows64(out + ((int64_t)b * Nq + qrow) * (H * DH) + h * DH, o, inv, hi);
+  if (hi == 0) lse[(int64_t)bh * Nq + qrow] = (m_run + log2f(l_tot)) * LN2;
+}
+
+/* general form: Nq queries against Nk keys (both multiples of 256, <= ATTN_MAX_N) with an optional additive key bias f32 [B, Nk]
+ * (0 = keep, -inf = masked / padded key): cross-attention and key-padding masks.  Up to 2048 tokens attn_fwd_tiled_k, beyond
+ * attn_fwd_long_k. */
 extern "C" int dl_attn_fwd_ex(const void* q, const void* k, const void* v, void* out, float* lse, int64_t B, int64_t H,
                               int64_t Nq, int64_t Nk, int64_t dh, float scale, const float* key_bias, dl_stream_t stream) {
   DL_CHECK_ARG(q && k && v && out && lse && B > 0 && H > 0, "dl_attn_fwd_ex: null operand");
   DL_CHECK_ARG(dh == DH, "dl_attn_fwd_ex: head_dim %lld unsupported (64 only)", (long long)dh);
-  DL_CHECK_ARG(Nq % ACH == 0 && Nk % ACH == 0 && Nq > 0 && Nk > 0 && Nq <= 2048 && Nk <= 2048,
-               "dl_attn_fwd_ex: Nq=%lld Nk=%lld must be multiples of 256 up to 2048 (pad and mask)", (long long)Nq, (long long)Nk);
+  DL_CHECK_ARG(Nq % ACH == 0 && Nk % ACH == 0 && Nq > 0 && Nk > 0 && Nq <= ATTN_MAX_N && Nk <= ATTN_MAX_N,
+               "dl_attn_fwd_ex: Nq=%lld Nk=%lld must be multiples of 256 up to 32768 (pad and mask)", (long long)Nq, (long long)Nk);
+  DL_CHECK_ARG(B * H * (Nq / ACH) <= INT32_MAX, "dl_attn_fwd_ex: B*H*Nq/256 = %lld workgroups exceed the grid limit",
+               (long long)(B * H * (Nq / ACH)));
+  if (Nq > 2048 || Nk > 2048) {
+    static DevOnce once;
+    (void)dev_cus(once, [] {
+      (void)hipFuncSetAttribute((const void*)attn_fwd_long_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * LBUF);
+      (void)hipFuncSetAttribute((const void*)attn_fwd_long_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * LBUF);
+    });
+    if (key_bias)
+      hipLaunchKernelGGL(attn_fwd_long_k<true>, (int)(B * H * (Nq / ACH)), 512, 2 * LBUF, (hipStream_t)stream, (const bf16_t*)q,
+                         (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, lse, (int)H, (int)Nq, (int)Nk, scale, key_bias);
+    else
+      hipLaunchKernelGGL(attn_fwd_long_k<false>, (int)(B * H * (Nq / ACH)), 512, 2 * LBUF, (hipStream_t)stream, (const bf16_t*)q,
+                         (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, lse, (int)H, (int)Nq, (int)Nk, scale, key_bias);
+    DL_LAUNCH_CHECK();
+    return DL_OK;
+  }
   const int ldt = 2 * ACH * ROWB + ACH * (int)sizeof(float);
   (void)hipFuncSetAttribute((const void*)attn_fwd_tiled_k, hipFuncAttributeMaxDynamicSharedMemorySize, ldt);
   hipLaunchKernelGGL(attn_fwd_tiled_k, (int)(B * H * (Nq / ACH)), 512, ldt, (hipStream_t)stream, (const bf16_t*)q,
@@ -338,8 +512,8 @@ extern "C" int dl_attn_fwd(const void* q, const void* k, const void* v, void* ou
                            int64_t N, int64_t dh, float scale, dl_stream_t stream) {
   DL_CHECK_ARG(q && k && v && out && lse && B > 0 && H > 0, "dl_attn_fwd: null operand");
   DL_CHECK_ARG(dh == DH, "dl_attn_fwd: head_dim %lld unsupported (64 only)", (long long)dh);
-  DL_CHECK_ARG(N % 64 == 0 && N >= 64 && (N <= 256 || (N % ACH == 0 && N <= 2048)),
-               "dl_attn_fwd: N=%lld must be a multiple of 64 up to 256, or a multiple of 256 up to 2048", (long long)N);
+  DL_CHECK_ARG(N % 64 == 0 && N >= 64 && (N <= 256 || (N % ACH == 0 && N <= ATTN_MAX_N)),
+               "dl_attn_fwd: N=%lld must be a multiple of 64 up to 256, or a multiple of 256 up to 32768", (long long)N);
   if (N > 256)  // (the resident-tile kernel runs N/32 waves per workgroup: 8 at most)
     return dl_attn_fwd_ex(q, k, v, out, lse, B, H, N, N, dh, scale, nullptr, stream);
   return dl_attn_fwd_sv(q, k, v, H * N * DH, N * DH, DH, out, lse, B, H, N, dh, scale, stream);
@@ -560,11 +734,6 @@ __global__ __launch_bounds__(512) void attn_fwd_qkn_k(const bf16_t* __restrict__
 static int g_attn_pipe = 1;  // 1: the persistent forms where they apply; 0: the chain forms everywhere
 extern "C" __attribute__((visibility("default"))) void dl_lab_set_attn_pipe(int mode) { g_attn_pipe = mode; }  // LAB A/B switch (not in the header)
 static int attn_fwd_pipe_on() { return g_attn_pipe & 1; }
-__device__ __forceinline__ s16x4_t attn_lds_tr16(const char* p) {
-  s16x4_t v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"((unsigned)(uintptr_t)(lds_void_t*)p));
-  return v;
-}
 #define PIPE_N 256
 __global__ __launch_bounds__(512) void attn_fwd_qkn_pipe_k(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ lse,
                                                            int H, int items, float scale, QkNorm qn) {
@@ -1129,13 +1298,227 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_tiled_k(const bf16_t* __restr
   }
 }
 
+// ------------------------------------------------------------------------------ backward, very long sequences (max(Nq, Nk) > 2048)
+// Three launches, no N-sized LDS array and no atomics (bit-reproducible):
+//   attn_bwd_delta_k  delta = rowsum(O * dO), reading O and dO once;
+//   attn_bwd_dkdv_long_k  phase B of attn_bwd_tiled_k: a workgroup owns 256 keys and streams Q / dO chunks, with the lse and delta of
+//                     each streamed 256-query chunk staged in LDS beside it;
+//   attn_bwd_dq_long_k    phase A: a workgroup owns 256 queries and streams K / V / key-bias chunks.
+// dq doubles as the delta scratch: delta of the 32-query block starting at row r is kept as 32 floats in (head-major) dq row r, whose
+// 128 bytes it fills exactly.  The dK / dV launch reads it there; the dQ launch, which owns whole 32-row blocks, reads a block's
+// delta back into registers before the owning wave overwrites that row with dQ.  (No library scratch, no extra argument.  The caller
+// must therefore pass a dense head-major dq that overlaps none of q, k, v, out, dout and lse: include/diffulab_hip.h, dl_attn_bwd.)
+__device__ __forceinline__ const float* delta_row(const bf16_t* dq_head, int row) {
+  return (const float*)(dq_head + (int64_t)(row & ~31) * DH) + (row & 31);
+}
+__global__ __launch_bounds__(256) void attn_bwd_delta_k(const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout,
+                                                        bf16_t* __restrict__ dq, int H, int Nq) {
+  // two threads per (b, n, h) row of 64 channels, h fastest: consecutive threads read consecutive bytes of the token-major rows
+  const int64_t pr = (int64_t)blockIdx.x * 128 + (threadIdx.x >> 1);
+  const int half = threadIdx.x & 1;
+  const int h = (int)(pr % H);
+  const int64_t bn = pr / H;
+  const int n = (int)(bn % Nq), b = (int)(bn / Nq);
+  const bf16_t* po = out + pr * DH + half * 32;
+  const bf16_t* pd = dout + pr * DH + half * 32;
+  float acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float a[8], d[8];
+    unpack8(*(const u32x4_t*)(po + i * 8), a);
+    unpack8(*(const u32x4_t*)(pd + i * 8), d);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc += a[e] * d[e];
+  }
+  acc += __shfl_xor(acc, 1, 64);
+  if (half == 0) *(float*)delta_row(dq + ((int64_t)b * H + h) * Nq * DH, n) = acc;
+}
+
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_long_k(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                               const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
+                                                               const float* __restrict__ lse, const bf16_t* __restrict__ dq,
+                                                               bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int H, int Nq, int Nk,
+                                                               float scale, const float* __restrict__ key_bias) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* ta = smem;            // Q chunk
+  char* tb = ta + ACH * ROWB;  // dO chunk
+  float* lse2 = (float*)(tb + ACH * ROWB);  // lse * log2(e) of the chunk's queries
+  float* delta = lse2 + ACH;                // their rowsum(dO * O)
+  const int lane = threadIdx.x & 63, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
+  const int nchq = Nq / ACH, nchk = Nk / ACH;
+  const int bh = blockIdx.x / nchk, cc = blockIdx.x - bh * nchk, b = bh / H, h = bh - b * H;
+  const int64_t hoffq = (int64_t)bh * Nq * DH, hoffk = (int64_t)bh * Nk * DH;
+  const int64_t tok_pitch = (int64_t)H * DH;
+  const bf16_t* dog = dout + (int64_t)b * Nq * tok_pitch + h * DH;
+  const float c = scale * LOG2E;
+  for (int ob = 0; ob < 2; ++ob) {
+    const int own = cc * ACH + (wave * 2 + ob) * 32;
+    const float kbias = key_bias ? key_bias[(int64_t)b * Nk + own + (lane & 31)] * LOG2E : 0.f;
+    bf16x8_t kf[4], vf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      kf[ks] = frag_rows_g(k + hoffk, DH, own + (lane & 31), ks, hi);
+      vf[ks] = frag_rows_g(v + hoffk, DH, own + (lane & 31), ks, hi);
+    }
+    f32x16_t dka[2], dva[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dka[0][r] = dka[1][r] = dva[0][r] = dva[1][r] = 0.f;
+    for (int qc = 0; qc < nchq; ++qc) {
+      __syncthreads();
+      tile_dma(q + hoffq + (int64_t)qc * ACH * DH, DH, ta, ACH, wave, nwaves, lane);
+      tile_dma(dog + (int64_t)qc * ACH * tok_pitch, tok_pitch, tb, ACH, wave, nwaves, lane);
+      for (int i = threadIdx.x; i < ACH; i += blockDim.x) {
+        lse2[i] = lse[(int64_t)bh * Nq + qc * ACH + i] * LOG2E;
+        delta[i] = *delta_row(dq + hoffq, qc * ACH + i);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      for (int qb = 0; qb < ACH; qb += 32) {
+        f32x16_t s2, dp;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s2[r] = dp[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          s2 = MFMA(frag_rows(ta, qb + (lane & 31), ks, hi), kf[ks], s2);
+          dp = MFMA(frag_rows(tb, qb + (lane & 31), ks, hi), vf[ks], dp);
+        }
+        float p[16], ds[16];
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const f32x4_t l4 = *(const f32x4_t*)(lse2 + qb + g4 * 8 + hi * 4);
+          const f32x4_t d4 = *(const f32x4_t*)(delta + qb + g4 * 8 + hi * 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = g4 * 4 + e;
+            p[r] = fast_exp2(s2[r] * c + kbias - l4[e]);
+            ds[r] = p[r] * (dp[r] - d4[e]);
+          }
+        }
+#pragma unroll
+        for (int kg2 = 0; kg2 < 2; ++kg2) {
+          const bf16x8_t pf = pack_frag(&p[kg2 * 8]);
+          const bf16x8_t df = pack_frag(&ds[kg2 * 8]);
+          const int rbase = qb + kg2 * 16;
+          dva[0] = MFMA(frag_cols(tb, rbase, 0, lane), pf, dva[0]);
+          dva[1] = MFMA(frag_cols(tb, rbase, 32, lane), pf, dva[1]);
+          dka[0] = MFMA(frag_cols(ta, rbase, 0, lane), df, dka[0]);
+          dka[1] = MFMA(frag_cols(ta, rbase, 32, lane), df, dka[1]);
+        }
+      }
+    }
+    store_rows64(dk + hoffk + (int64_t)(own + (lane & 31)) * DH, dka, scale, hi);
+    store_rows64(dv + hoffk + (int64_t)(own + (lane & 31)) * DH, dva, 1.0f, hi);
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_long_k(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                             const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
+                                                             const float* __restrict__ lse, bf16_t* __restrict__ dq, int H, int Nq,
+                                                             int Nk, float scale, const float* __restrict__ key_bias) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* ta = smem;            // K chunk
+  char* tb = ta + ACH * ROWB;  // V chunk
+  float* bs = (float*)(tb + ACH * ROWB);  // its key bias, times log2(e)
+  const int lane = threadIdx.x & 63, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
+  const int nchq = Nq / ACH, nchk = Nk / ACH;
+  const int bh = blockIdx.x / nchq, cc = blockIdx.x - bh * nchq, b = bh / H, h = bh - b * H;
+  const int64_t hoffq = (int64_t)bh * Nq * DH, hoffk = (int64_t)bh * Nk * DH;
+  const int64_t tok_pitch = (int64_t)H * DH;
+  const bf16_t* dog = dout + (int64_t)b * Nq * tok_pitch + h * DH;
+  const float c = scale * LOG2E;
+  bf16x8_t qf[2][4], dof[2][4];
+  float my_lse[2], my_delta[2];
+  f32x16_t dqa[2][2];
+#pragma unroll
+  for (int ob = 0; ob < 2; ++ob) {
+    const int own = cc * ACH + (wave * 2 + ob) * 32;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      qf[ob][ks] = frag_rows_g(q + hoffq, DH, own + (lane & 31), ks, hi);
+      dof[ob][ks] = frag_rows_g(dog, tok_pitch, own + (lane & 31), ks, hi);
+    }
+    my_lse[ob] = lse[(int64_t)bh * Nq + own + (lane & 31)] * LOG2E;
+    my_delta[ob] = *delta_row(dq + hoffq, own + (lane & 31));  // (read here, overwritten by this wave's dQ store below)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dqa[ob][0][r] = dqa[ob][1][r] = 0.f;
+  }
+  for (int kc = 0; kc < nchk; ++kc) {
+    __syncthreads();
+    tile_dma(k + hoffk + (int64_t)kc * ACH * DH, DH, ta, ACH, wave, nwaves, lane);
+    tile_dma(v + hoffk + (int64_t)kc * ACH * DH, DH, tb, ACH, wave, nwaves, lane);
+    for (int i = threadIdx.x; i < ACH; i += blockDim.x) bs[i] = key_bias ? key_bias[(int64_t)b * Nk + kc * ACH + i] * LOG2E : 0.f;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll
+    for (int ob = 0; ob < 2; ++ob)
+      for (int kb = 0; kb < ACH; kb += 32) {
+        f32x16_t st, dpt;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[r] = dpt[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          st = MFMA(frag_rows(ta, kb + (lane & 31), ks, hi), qf[ob][ks], st);
+          dpt = MFMA(frag_rows(tb, kb + (lane & 31), ks, hi), dof[ob][ks], dpt);
+        }
+        float ds[16];
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const f32x4_t b4 = *(const f32x4_t*)(bs + kb + g4 * 8 + hi * 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = g4 * 4 + e;
+            const float p = fast_exp2(st[r] * c + b4[e] - my_lse[ob]);
+            ds[r] = p * (dpt[r] - my_delta[ob]);
+          }
+        }
+#pragma unroll
+        for (int kg2 = 0; kg2 < 2; ++kg2) {
+          const bf16x8_t df = pack_frag(&ds[kg2 * 8]);
+          dqa[ob][0] = MFMA(frag_cols(ta, kb + kg2 * 16, 0, lane), df, dqa[ob][0]);
+          dqa[ob][1] = MFMA(frag_cols(ta, kb + kg2 * 16, 32, lane), df, dqa[ob][1]);
+        }
+      }
+  }
+#pragma unroll
+  for (int ob = 0; ob < 2; ++ob) {
+    const int own = cc * ACH + (wave * 2 + ob) * 32;
+    store_rows64(dq + hoffq + (int64_t)(own + (lane & 31)) * DH, dqa[ob], scale, hi);
+  }
+}
+
 extern "C" int dl_attn_bwd_ex(const void* q, const void* k, const void* v, const void* out, const void* dout,
                               const float* lse, void* dq, void* dk, void* dv, int64_t B, int64_t H, int64_t Nq, int64_t Nk,
                               int64_t dh, float scale, const float* key_bias, dl_stream_t stream) {
   DL_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv && B > 0 && H > 0, "dl_attn_bwd_ex: null operand");
   DL_CHECK_ARG(dh == DH, "dl_attn_bwd_ex: head_dim %lld unsupported (64 only)", (long long)dh);
-  DL_CHECK_ARG(Nq % ACH == 0 && Nk % ACH == 0 && Nq > 0 && Nk > 0 && Nq <= 2048 && Nk <= 2048,
-               "dl_attn_bwd_ex: Nq=%lld Nk=%lld must be multiples of 256 up to 2048", (long long)Nq, (long long)Nk);
+  DL_CHECK_ARG(Nq % ACH == 0 && Nk % ACH == 0 && Nq > 0 && Nk > 0 && Nq <= ATTN_MAX_N && Nk <= ATTN_MAX_N,
+               "dl_attn_bwd_ex: Nq=%lld Nk=%lld must be multiples of 256 up to 32768", (long long)Nq, (long long)Nk);
+  DL_CHECK_ARG(B * H * (Nq > Nk ? Nq : Nk) / 128 <= INT32_MAX, "dl_attn_bwd_ex: B=%lld H=%lld exceed the grid limit", (long long)B,
+               (long long)H);
+  if (Nq > 2048 || Nk > 2048) {
+    const int lds = 2 * ACH * ROWB + 2 * ACH * (int)sizeof(float);
+    static DevOnce once;
+    (void)dev_cus(once, [] {
+      (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_long_k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                2 * ACH * ROWB + 2 * ACH * (int)sizeof(float));
+      (void)hipFuncSetAttribute((const void*)attn_bwd_dq_long_k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                2 * ACH * ROWB + ACH * (int)sizeof(float));
+    });
+    hipLaunchKernelGGL(attn_bwd_delta_k, (int)(B * Nq * H / 128), 256, 0, (hipStream_t)stream, (const bf16_t*)out, (const bf16_t*)dout,
+                       (bf16_t*)dq, (int)H, (int)Nq);
+    DL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(attn_bwd_dkdv_long_k, (int)(B * H * (Nk / ACH)), 256, lds, (hipStream_t)stream, (const bf16_t*)q,
+                       (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse, (const bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv,
+                       (int)H, (int)Nq, (int)Nk, scale, key_bias);
+    DL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(attn_bwd_dq_long_k, (int)(B * H * (Nq / ACH)), 256, 2 * ACH * ROWB + ACH * (int)sizeof(float),
+                       (hipStream_t)stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse, (bf16_t*)dq,
+                       (int)H, (int)Nq, (int)Nk, scale, key_bias);
+    DL_LAUNCH_CHECK();
+    return DL_OK;
+  }
   const int ldt = (int)(2 * ACH * ROWB + (2 * Nq + ACH) * sizeof(float));
   const int64_t nmax = (Nq > Nk ? Nq : Nk) / ACH;
   (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_k, hipFuncAttributeMaxDynamicSharedMemorySize, ldt);
@@ -1150,8 +1533,8 @@ extern "C" int dl_attn_bwd(const void* q, const void* k, const void* v, const vo
                            int64_t dh, float scale, dl_stream_t stream) {
   DL_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv && B > 0 && H > 0, "dl_attn_bwd: null operand");
   DL_CHECK_ARG(dh == DH, "dl_attn_bwd: head_dim %lld unsupported (64 only)", (long long)dh);
-  DL_CHECK_ARG(N % 64 == 0 && N >= 64 && (N <= 256 || (N % ACH == 0 && N <= 2048)),
-               "dl_attn_bwd: N=%lld must be a multiple of 64 up to 256, or a multiple of 256 up to 2048", (long long)N);
+  DL_CHECK_ARG(N % 64 == 0 && N >= 64 && (N <= 256 || (N % ACH == 0 && N <= ATTN_MAX_N)),
+               "dl_attn_bwd: N=%lld must be a multiple of 64 up to 256, or a multiple of 256 up to 32768", (long long)N);
   if (N > 256) return dl_attn_bwd_ex(q, k, v, out, dout, lse, dq, dk, dv, B, H, N, N, dh, scale, nullptr, stream);
   return dl_attn_bwd_sv(q, k, v, H * N * DH, N * DH, DH, out, dout, lse, dq, dk, dv, H * N * DH, N * DH, DH, B, H, N, dh, scale,
                         stream);

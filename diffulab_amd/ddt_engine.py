@@ -284,10 +284,11 @@ class DDTEngine(SprintEngine, PerTokenDecoder):
         D, E, p, L = d.inner_dim, d.embedding_dim, d.patch_size, d.depth
         gh, gw = H // p, W // p
         N = gh * gw
-        if N % 64 or (N > 256 and (N % 256 or N > 2048)):
+        if N % 64 or (N > 256 and (N % 256 or N > ops.ATTN_MAX_TOKENS)):
             raise NotImplementedError(f"DDT HIP path: token grid {gh}x{gw} must give a multiple of 64 tokens up to 256, or of 256 up "
-                                      "to 2048")
+                                      f"to {ops.ATTN_MAX_TOKENS}")
         M, Bp, Fo, F = B * N, _rup(B, 64), p * p * d.output_channels, d.mlp_ratio * D
+        ops.check_row_extent(M, max(2 * F, 6 * D, self.layout.tmod_rows), "DDT HIP path")
         bf, f32 = torch.bfloat16, torch.float32
         R = self.layout.tmod_rows
 
@@ -551,12 +552,13 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
         N = gh * gw
         Tf = Lc + N
         Tpf = _rup(Tf, 256)
-        if Tpf > 2048 or (B * N) % 64 or Lc < 1:
-            raise NotImplementedError(f"joint DDT HIP path: context + image tokens <= 2048 (got {Lc} + {N}), batch * image tokens a "
+        if Tpf > ops.ATTN_MAX_TOKENS or (B * N) % 64 or Lc < 1:
+            raise NotImplementedError(f"joint DDT HIP path: context + image tokens <= {ops.ATTN_MAX_TOKENS} (got {Lc} + {N}), batch * image tokens a "
                                       f"multiple of 64 (got {B} * {N})")
         pad = ops.attn_needs_padding(N)  # decoder attention on rows padded to a multiple of 256 with masked pad keys (_decoder_fwd)
         Nd = _rup(N, 256) if pad else N
         M, Bp, Fo, F = B * N, _rup(B, 64), p * p * d.output_channels, d.mlp_ratio * D
+        ops.check_row_extent(B * Tpf, max(2 * F, 6 * D, self.layout.tmod_rows), "joint DDT HIP path")
         bf, f32 = torch.bfloat16, torch.float32
         Hh, R = d.num_heads, self.layout.tmod_rows
 

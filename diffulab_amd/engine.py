@@ -299,15 +299,16 @@ class DiTEngine:
         # multi-aspect-ratio latents): q / k / v rows padded to a multiple of 256 per (sample, head), pad keys masked (dl_attn_*_ex)
         pad = ops.attn_needs_padding(N)
         Nd = _rup(N, 256) if pad else N
-        if pad and type(self) is DiTEngine and Nd <= 2048 and M % 64:
+        if pad and type(self) is DiTEngine and Nd <= ops.ATTN_MAX_TOKENS and M % 64:
             raise NotImplementedError(f"token grid {gh}x{gw} ({N} tokens) in the bf16 regime: batch * tokens must be a multiple of 64 (got "
                                       f"{B} * {N}); the fp32 regime (precision_type=\"no\" / set_precision(\"fp32\")) takes any grid and batch")
-        if Nd > 2048 or (pad and type(self) is not DiTEngine):
-            raise NotImplementedError(f"token grid {gh}x{gw}: the bf16 regime's attention takes up to 2048 tokens"
+        if Nd > ops.ATTN_MAX_TOKENS or (pad and type(self) is not DiTEngine):
+            raise NotImplementedError(f"token grid {gh}x{gw}: the bf16 regime's attention takes up to {ops.ATTN_MAX_TOKENS} tokens"
                                       + ("" if type(self) is DiTEngine else ", N % 64 == 0 up to 256 or N % 256 == 0 beyond, in this engine")
                                       + f" (got {N}); the fp32 regime (precision_type=\"no\" / set_precision(\"fp32\")) takes any grid")
         Bp = _rup(B, 64)
         Fo = p * p * d.output_channels
+        ops.check_row_extent(B * Nd, max(2 * d.mlp_ratio * D, 6 * D), "DiT bf16 path")
         bf, f32 = torch.bfloat16, torch.float32
 
         def z(*shape, dtype=bf):

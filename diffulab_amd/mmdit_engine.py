@@ -154,10 +154,11 @@ class JointEngine(DiTEngine):
         N = gh * gw
         T = Lc + N
         Tp = _rup(T, 256)
-        if Tp > 2048 or (B * N) % 64 or Lc < 1:
-            raise NotImplementedError(f"joint MMDiT HIP path: context + image tokens <= 2048 (got {Lc} + {N}), image tokens a "
+        if Tp > ops.ATTN_MAX_TOKENS or (B * N) % 64 or Lc < 1:
+            raise NotImplementedError(f"joint MMDiT HIP path: context + image tokens <= {ops.ATTN_MAX_TOKENS} (got {Lc} + {N}), image tokens a "
                                       "multiple of 64")
         M, Bp, Fo, F = B * N, _rup(B, 64), p * p * d.output_channels, d.mlp_ratio * D
+        ops.check_row_extent(B * Tp, max(2 * F, 6 * D), "joint MMDiT HIP path")
         bf, f32 = torch.bfloat16, torch.float32
 
         def z(*shape, dtype=bf):

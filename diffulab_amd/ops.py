@@ -578,8 +578,20 @@ def attn_bwd(q, k, v, out, dout, lse, dq, dk, dv, B, H, N, dh, scale):
           float(scale), _s())
 
 
+ATTN_MAX_TOKENS = 32768  # longest Nq / Nk of dl_attn_*: multiples of 256 up to here (up to 2048 the tiled kernels, beyond the long ones)
+_INT32_ELEMS = 2 ** 31
+
+
+def check_row_extent(rows: int, width: int, what: str) -> None:
+    """refuse a token-row buffer [rows, width] whose element offsets would pass 2^31: the row kernels, GEMMs and token gathers on the
+    bf16 engines' paths index elements with 32-bit integers in places"""
+    if rows * width >= _INT32_ELEMS:
+        raise NotImplementedError(f"{what}: {rows} token rows x {width} columns = {rows * width} elements exceed the 2^31 elements the "
+                                  "bf16 regime's kernels index; use a smaller batch")
+
+
 def attn_needs_padding(N: int) -> bool:
-    """token counts the resident / tiled attention kernels do not take as they are (multiples of 64 up to 256, of 256 up to 2048):
+    """token counts the resident / tiled attention kernels do not take as they are (multiples of 64 up to 256, of 256 up to 32768):
     the caller pads q / k / v to a multiple of 256 rows and masks the pad keys (dl_attn_fwd_ex / _bwd_ex with a key bias)"""
     return N % 64 != 0 or (N > 256 and N % 256 != 0)
 

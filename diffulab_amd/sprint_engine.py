@@ -76,12 +76,13 @@ class SprintEngine(DiTEngine):
             return
         D, E, L = d.inner_dim, d.embedding_dim, d.depth
         for n in (N, k):
-            if n % 64 or (n > 256 and (n % 256 or n > 2048)):
+            if n % 64 or (n > 256 and (n % 256 or n > ops.ATTN_MAX_TOKENS)):
                 raise NotImplementedError(f"SprintDiT HIP path: token counts must be multiples of 64 up to 256, or of 256 up to "
-                                          f"2048 (grid {gh}x{gw} = {N} tokens, {k} kept)")
+                                          f"{ops.ATTN_MAX_TOKENS} (grid {gh}x{gw} = {N} tokens, {k} kept)")
         M, Bp, Fo = B * N, _rup(B, 64), p * p * d.output_channels
         bf, f32 = torch.bfloat16, torch.float32
         F = d.mlp_ratio * D
+        ops.check_row_extent(M, max(2 * F, 6 * D), "SprintDiT HIP path")
 
         def z(*shape, dtype=bf):
             with torch.inference_mode(False):

@@ -306,16 +306,22 @@ DL_API int dl_qk_norm_rope_bwd_inplace(const void* qkv, const float* scale_q, co
                                        dl_stream_t stream);
 /* F.scaled_dot_product_attention mmdit.py:92-100, no mask: out = softmax(q k^T * scale) v, written as
  * 'b h n d -> b n (h d)'.  lse f32 [B,H,N] = natural-log-sum-exp of the scaled scores (for the backward).
- * dh must be 64; N a multiple of 64 up to 256 (K and V of one head stay resident in LDS), or a multiple of 256 up to 2048
- * (one workgroup per 256-row chunk, the other operand streamed through LDS in 256-row chunks). */
+ * dh must be 64; N a multiple of 64 up to 256 (K and V of one head stay resident in LDS), or a multiple of 256 up to 32768
+ * (one workgroup per 256-row chunk, the other operand streamed through LDS; beyond 2048 tokens the long-sequence kernels:
+ * double-buffered K / V stream in the forward, a delta = rowsum(O * dO) pre-pass and separate dK / dV and dQ launches in the
+ * backward).  Requirement of the backward beyond 2048 tokens (dl_attn_bwd, dl_attn_bwd_ex): dq is a dense head-major
+ * [B, H, Nq, 64] buffer that overlaps none of q, k, v, out, dout and lse -- it is used as the scratch of the per-row delta between
+ * the launches before the dQ launch overwrites it. */
 DL_API int dl_attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int64_t B, int64_t H,
                        int64_t N, int64_t dh, float scale, dl_stream_t stream);
 DL_API int dl_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
                        const float* lse, void* dq, void* dk, void* dv, int64_t B, int64_t H, int64_t N,
                        int64_t dh, float scale, dl_stream_t stream);
 /* general form (joint text-image attention mmdit.py:172-190 with its key-padding mask, cross-attention of a resampler):
- * q [B,H,Nq,64] against k, v [B,H,Nk,64]; Nq, Nk multiples of 256 up to 2048 (pad); key_bias f32 [B, Nk] is ADDED to the
- * scaled scores (0 = attend, -inf = masked / padded key) or NULL; out [B, Nq, H*64], lse [B,H,Nq]. */
+ * q [B,H,Nq,64] against k, v [B,H,Nk,64]; Nq, Nk multiples of 256 up to 32768 (pad; the kernels of max(Nq, Nk) <= 2048
+ * are unchanged, longer calls take the long-sequence kernels, whose backward requires dq as stated for dl_attn_bwd above);
+ * key_bias f32 [B, Nk] is ADDED to the scaled scores (0 = attend, -inf = masked / padded key) or NULL; out [B, Nq, H*64],
+ * lse [B,H,Nq]. */
 DL_API int dl_attn_fwd_ex(const void* q, const void* k, const void* v, void* out, float* lse, int64_t B, int64_t H,
                           int64_t Nq, int64_t Nk, int64_t dh, float scale, const float* key_bias, dl_stream_t stream);
 DL_API int dl_attn_bwd_ex(const void* q, const void* k, const void* v, const void* out, const void* dout,

@@ -1,19 +1,22 @@
 // HBM-bound row kernels of the DiT block: adaLN (LayerNorm + modulate) fwd/bwd, gated-residual bwd,
 // QK-RMSNorm + N-D RoPE + head split fwd/bwd, SwiGLU fwd/bwd.
-// One 64-lane wave owns one token row; every lane moves 16-byte (8 x bf16) chunks; row statistics are
+// One 64-lane wave owns one token row (D <= 1024); every lane moves 16-byte (8 x bf16) chunks; row statistics are
 // wavefront shuffles (no LDS); per-sample column reductions (adaLN gradients) are register accumulators
-// reduced across the workgroup's waves through LDS once per workgroup.
+// reduced across the workgroup's waves through LDS once per workgroup.  1024 < D <= 4096: the *_rows_k kernels give a row to a
+// whole 256-thread workgroup (rows_sum); a thread then owns its columns, so column sums need no cross-wave reduction.
 #include <stdlib.h>
 
 #include "common.h"
 
-#define MAXJ 2  // chunks of 8 per lane -> D <= 1024 (NJ=4 spills; wider rows need an LDS-staged variant)
+#define MAXJ 2  // chunks of 8 per lane -> one wave owns a row of D <= 1024 (NJ=4 spills); wider rows: the *_rows_k kernels below
+#define ROW_MAX_D 4096  // 1024 < D <= 4096: one 256-thread workgroup owns a row, thread t holds chunks t + 256 j (j < cdiv(D, 2048))
 
-template <int NJ>
+// S: the lane stride of the chunks (64: a wave owns the row; 256: the four waves of a workgroup share it)
+template <int NJ, int S = 64>
 __device__ __forceinline__ void load_row(const bf16_t* __restrict__ p, int D8, int lane, float (&v)[NJ][8]) {
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
-    const int c = lane + 64 * j;
+    const int c = lane + S * j;
     if (c < D8) {
       unpack8(*(const u32x4_t*)(p + c * 8), v[j]);
     } else {
@@ -22,11 +25,11 @@ __device__ __forceinline__ void load_row(const bf16_t* __restrict__ p, int D8, i
     }
   }
 }
-template <int NJ>
+template <int NJ, int S = 64>
 __device__ __forceinline__ void load_row_f32(const float* __restrict__ p, int D8, int lane, float (&v)[NJ][8], float fill) {
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
-    const int c = lane + 64 * j;
+    const int c = lane + S * j;
     if (p && c < D8) {
       *(f32x4_t*)&v[j][0] = *(const f32x4_t*)(p + c * 8);
       *(f32x4_t*)&v[j][4] = *(const f32x4_t*)(p + c * 8 + 4);
@@ -36,13 +39,32 @@ __device__ __forceinline__ void load_row_f32(const float* __restrict__ p, int D8
     }
   }
 }
-template <int NJ>
+template <int NJ, int S = 64>
 __device__ __forceinline__ void store_row(bf16_t* __restrict__ p, int D8, int lane, const float (&v)[NJ][8]) {
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
-    const int c = lane + 64 * j;
+    const int c = lane + S * j;
     if (c < D8) *(u32x4_t*)(p + c * 8) = pack8(v[j]);
   }
+}
+
+// Row sums of the wide (*_rows_k) kernels: NV per-thread partial sums -> the sums over the workgroup's 256 threads, on every thread.
+// wave_sum, then lane 0 of each wave drops its NV values into an LDS slot [NV][4] and the four are added in a fixed order (the row
+// statistics do not depend on timing).  Two slots alternate: a wave writes slot s again only after the barrier of the call in
+// between, which every wave passes after it has read slot s.  red: 2 * NV * 4 floats; every thread of the workgroup calls it.
+template <int NV>
+__device__ __forceinline__ void rows_sum(float (&v)[NV], float* red, int& slot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* r = red + slot * NV * 4;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const float s = wave_sum(v[i]);
+    if (lane == 0) r[i * 4 + wave] = s;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = (r[i * 4] + r[i * 4 + 1]) + (r[i * 4 + 2] + r[i * 4 + 3]);
+  slot ^= 1;
 }
 
 // ======================================================================== LayerNorm + modulate, forward
@@ -108,6 +130,73 @@ __global__ __launch_bounds__(256) void ln_mod_fwd_k(const bf16_t* __restrict__ x
   }
 }
 
+// 1024 < D <= 4096: the same arithmetic, one row per 256-thread workgroup (rows_sum for the two statistics)
+template <int NJ>
+__global__ __launch_bounds__(256) void ln_mod_fwd_rows_k(const bf16_t* __restrict__ x, const float* __restrict__ w,
+                                                         const float* __restrict__ b, const bf16_t* __restrict__ scale,
+                                                         const bf16_t* __restrict__ shift, int64_t ld_mod, int64_t rows_per_mod,
+                                                         float eps, bf16_t* __restrict__ out, float* __restrict__ mean_o,
+                                                         float* __restrict__ rstd_o, const bf16_t* __restrict__ t,
+                                                         const bf16_t* __restrict__ gate, int64_t ld_gate, bf16_t* __restrict__ x_out,
+                                                         int64_t M, int D) {
+  __shared__ float red[2 * 1 * 4];
+  const int tid = threadIdx.x;
+  const int D8 = D >> 3;
+  const float invD = 1.0f / (float)D;
+  int slot = 0;
+  float wv[NJ][8], bv[NJ][8];
+  load_row_f32<NJ, 256>(w, D8, tid, wv, 1.0f);
+  load_row_f32<NJ, 256>(b, D8, tid, bv, 0.0f);
+  for (int64_t row = blockIdx.x; row < M; row += gridDim.x) {
+    float xv[NJ][8], sc[NJ][8], sh[NJ][8];
+    load_row<NJ, 256>(x + row * D, D8, tid, xv);
+    const int64_t g = row / rows_per_mod;
+    if (t) {
+      float tv[NJ][8], gv[NJ][8];
+      load_row<NJ, 256>(t + row * D, D8, tid, tv);
+      load_row<NJ, 256>(gate + g * ld_gate, D8, tid, gv);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xv[j][e] = bf2f(f2bf(xv[j][e] + gv[j][e] * tv[j][e]));
+      store_row<NJ, 256>(x_out + row * D, D8, tid, xv);
+    }
+    load_row<NJ, 256>(scale + g * ld_mod, D8, tid, sc);
+    load_row<NJ, 256>(shift + g * ld_mod, D8, tid, sh);
+    float s[1] = {0.f};
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[0] += xv[j][e];
+    rows_sum<1>(s, red, slot);
+    const float mu = s[0] * invD;
+    float q[1] = {0.f};
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const bool on = (tid + 256 * j) < D8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float d = on ? (xv[j][e] - mu) : 0.f;
+        q[0] += d * d;
+      }
+    }
+    rows_sum<1>(q, red, slot);
+    const float rs = rsqrtf(q[0] * invD + eps);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float y = (xv[j][e] - mu) * rs * wv[j][e] + bv[j][e];
+        xv[j][e] = y * (1.0f + sc[j][e]) + sh[j][e];
+      }
+    store_row<NJ, 256>(out + row * D, D8, tid, xv);
+    if (tid == 0) {
+      mean_o[row] = mu;
+      rstd_o[row] = rs;
+    }
+  }
+}
+
 extern "C" int dl_ln_modulate_fwd(const void* x, const float* w, const float* b, const void* scale, const void* shift,
                                   int64_t ld_mod, int64_t rows_per_mod, float eps, void* out, float* mean,
                                   float* rstd, const void* t, const void* gate, int64_t ld_gate, void* x_out, int64_t M,
@@ -116,8 +205,9 @@ extern "C" int dl_ln_modulate_fwd(const void* x, const float* w, const float* b,
   DL_CHECK_ARG(!t || (gate && x_out && ld_gate % 8 == 0 && (((uintptr_t)t | (uintptr_t)gate | (uintptr_t)x_out) & 15) == 0),
                "dl_ln_modulate_fwd: the fused gated residual needs t, gate and x_out (16-byte aligned)");
   DL_CHECK_ARG((w == nullptr) == (b == nullptr), "dl_ln_modulate_fwd: w and b must both be given or both NULL");
-  DL_CHECK_ARG(D % 8 == 0 && D <= 512 * MAXJ && ld_mod % 8 == 0 && rows_per_mod > 0, "dl_ln_modulate_fwd: D=%lld",
-               (long long)D);
+  DL_CHECK_ARG(D % 8 == 0 && D <= ROW_MAX_D, "dl_ln_modulate_fwd: D=%lld (a multiple of 8 up to 4096)", (long long)D);
+  DL_CHECK_ARG(ld_mod % 8 == 0 && rows_per_mod > 0, "dl_ln_modulate_fwd: ld_mod=%lld rows_per_mod=%lld", (long long)ld_mod,
+               (long long)rows_per_mod);
   DL_CHECK_ARG((((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)out) & 15) == 0,
                "dl_ln_modulate_fwd: 16-byte alignment");
   const int nj = cdiv(D, 512);
@@ -127,9 +217,16 @@ extern "C" int dl_ln_modulate_fwd(const void* x, const float* w, const float* b,
   hipLaunchKernelGGL(ln_mod_fwd_k<NJ>, grid, 256, 0, (hipStream_t)stream, (const bf16_t*)x, w, b,                \
                      (const bf16_t*)scale, (const bf16_t*)shift, ld_mod, rows_per_mod, eps, (bf16_t*)out, mean, \
                      rstd, (const bf16_t*)t, (const bf16_t*)gate, ld_gate, (bf16_t*)x_out, M, (int)D)
+#define LAUNCH_ROWS(NJ)                                                                                             \
+  hipLaunchKernelGGL(ln_mod_fwd_rows_k<NJ>, (int)(M < 4096 ? M : 4096), 256, 0, (hipStream_t)stream, (const bf16_t*)x, w, \
+                     b, (const bf16_t*)scale, (const bf16_t*)shift, ld_mod, rows_per_mod, eps, (bf16_t*)out, mean, rstd,        \
+                     (const bf16_t*)t, (const bf16_t*)gate, ld_gate, (bf16_t*)x_out, M, (int)D)
   if (nj == 1) LAUNCH(1);
-  else LAUNCH(2);
+  else if (nj == 2) LAUNCH(2);
+  else if (D <= 2048) LAUNCH_ROWS(1);
+  else LAUNCH_ROWS(2);
 #undef LAUNCH
+#undef LAUNCH_ROWS
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
@@ -315,6 +412,113 @@ __global__ __launch_bounds__(256) void ln_mod_bwd_wide_k(LNB_ARGS) {
   ln_mod_bwd_body<2, PF>(LNB_PASS);
 }
 
+// 1024 < D <= 4096: a 256-thread workgroup takes the rows of its share of one sample one at a time (rows_sum for the two row
+// reductions).  Every thread owns its columns, so the three column sums stay in its registers until they go to the caller's f32
+// accumulators: no LDS slab.  The shares are ceil(rows_per_mod / split) rows, so a sample whose token count is not a multiple
+// of 64 (joint models) still spreads over split workgroups.
+template <int NJ>
+__global__ __launch_bounds__(256) void ln_mod_bwd_rows_k(LNB_ARGS) {
+  __shared__ float red[2 * 2 * 4];
+  const int tid = threadIdx.x;
+  const int D8 = D >> 3;
+  const float invD = 1.0f / (float)D;
+  int slot = 0;
+  const int64_t g = blockIdx.x / split;
+  const int sp = blockIdx.x - (int)g * split;
+  const int64_t rows_per_wg = (rows_per_mod + split - 1) / split;
+  const int64_t row_begin = g * rows_per_mod + sp * rows_per_wg;
+  const int64_t row_end = row_begin + rows_per_wg < (g + 1) * rows_per_mod ? row_begin + rows_per_wg : (g + 1) * rows_per_mod;
+  float gw[NJ][8], gv[NJ][8];
+  {
+    float wv[NJ][8], sc[NJ][8];
+    load_row_f32<NJ, 256>(w, D8, tid, wv, 1.0f);
+    load_row<NJ, 256>(scale + g * ld_mod, D8, tid, sc);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gw[j][e] = (1.0f + sc[j][e]) * wv[j][e];
+  }
+  if (gt) load_row<NJ, 256>(ggate + g * ld_gate, D8, tid, gv);
+  float a_s1[NJ][8], a_s2[NJ][8], a_s3[NJ][8];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a_s1[j][e] = a_s2[j][e] = a_s3[j][e] = 0.f;
+  for (int64_t row = row_begin; row < row_end; ++row) {
+    float dv[NJ][8], xv[NJ][8], rv[NJ][8];
+    load_row<NJ, 256>(dout + row * D, D8, tid, dv);
+    load_row<NJ, 256>(x + row * D, D8, tid, xv);
+    if (dres) {
+      load_row<NJ, 256>(dres + row * D, D8, tid, rv);
+    } else {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) rv[j][e] = 0.f;
+    }
+    // this row's t of the fused gate: up to D = 2048 loaded with the other operands, before the row reduction's barrier (one memory
+    // round trip per row instead of two); at NJ = 2 its 16 registers would cost a wave per SIMD (161 -> 176 VGPRs)
+    constexpr bool early_t = NJ == 1;
+    float tv[NJ][8];
+    if (early_t && gt) load_row<NJ, 256>(gt + row * D, D8, tid, tv);
+    const float mu = mean[row], rs = rstd[row];
+    float s[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const bool on = (tid + 256 * j) < D8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float xh = on ? (xv[j][e] - mu) * rs : 0.f;
+        const float d = dv[j][e];
+        a_s1[j][e] += d;
+        a_s2[j][e] += d * xh;
+        const float dxh = d * gw[j][e];
+        s[0] += dxh;
+        s[1] += dxh * xh;
+        xv[j][e] = xh;
+        dv[j][e] = dxh;
+      }
+    }
+    rows_sum<2>(s, red, slot);
+    const float c1 = s[0] * invD, c2 = s[1] * invD;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) rv[j][e] += rs * (dv[j][e] - c1 - xv[j][e] * c2);
+    store_row<NJ, 256>(dx + row * D, D8, tid, rv);
+    if (gt) {  // fused backward of the gated residual that follows in the chain (see ln_mod_bwd_body)
+      if (!early_t) load_row<NJ, 256>(gt + row * D, D8, tid, tv);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float dxr = bf2f(f2bf(rv[j][e]));
+          a_s3[j][e] += dxr * tv[j][e];
+          rv[j][e] = dxr * gv[j][e];
+        }
+      store_row<NJ, 256>(gdt + row * D, D8, tid, rv);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = tid + 256 * j;
+    if (c >= D8) continue;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int col = c * 8 + e;
+      const float S1 = a_s1[j][e], S2 = a_s2[j][e];
+      const float wc = w ? w[col] : 1.0f, bc = b ? b[col] : 0.0f, sc1 = 1.0f + bf2f(scale[g * ld_mod + col]);
+      unsafeAtomicAdd(dscale + g * ld_dmod + col, wc * S2 + bc * S1);
+      unsafeAtomicAdd(dshift + g * ld_dmod + col, S1);
+      if (gt) unsafeAtomicAdd(dgate + g * ld_dmod + col, a_s3[j][e]);
+      if (dwb) {
+        unsafeAtomicAdd(dwb + (size_t)g * 2 * D + col, sc1 * S2);
+        unsafeAtomicAdd(dwb + (size_t)g * 2 * D + D + col, sc1 * S1);
+      }
+    }
+  }
+}
+
 extern "C" int dl_ln_modulate_bwd(const void* dout, const void* x, const float* w, const float* b, const void* scale,
                                   int64_t ld_mod, int64_t rows_per_mod, const float* mean, const float* rstd,
                                   const void* dres, void* dx, float* dscale, float* dshift, int64_t ld_dmod,
@@ -322,7 +526,8 @@ extern "C" int dl_ln_modulate_bwd(const void* dout, const void* x, const float* 
                                   float* dgate, int64_t M, int64_t D, dl_stream_t stream) {
   DL_CHECK_ARG(dout && x && scale && mean && rstd && dx && dscale && dshift && M > 0, "dl_ln_modulate_bwd: null operand");
   DL_CHECK_ARG((w == nullptr) == (b == nullptr), "dl_ln_modulate_bwd: w and b must both be given or both NULL");
-  DL_CHECK_ARG(D % 8 == 0 && D <= 512 * MAXJ && ld_mod % 8 == 0 && rows_per_mod > 0 && M % rows_per_mod == 0,
+  DL_CHECK_ARG(D % 8 == 0 && D <= ROW_MAX_D, "dl_ln_modulate_bwd: D=%lld (a multiple of 8 up to 4096)", (long long)D);
+  DL_CHECK_ARG(ld_mod % 8 == 0 && rows_per_mod > 0 && M % rows_per_mod == 0,
                "dl_ln_modulate_bwd: D=%lld M=%lld rows_per_mod=%lld", (long long)D, (long long)M, (long long)rows_per_mod);
   DL_CHECK_ARG((((uintptr_t)dout | (uintptr_t)x | (uintptr_t)scale | (uintptr_t)dx | (uintptr_t)dres) & 15) == 0,
                "dl_ln_modulate_bwd: 16-byte alignment");
@@ -333,6 +538,19 @@ extern "C" int dl_ln_modulate_bwd(const void* dout, const void* x, const float* 
   const int split = (rows_per_mod % rows_wg == 0) ? (int)(rows_per_mod / rows_wg) : 1;
   DL_CHECK_ARG(!gate_t || (gate && dt && dgate && ld_gate % 8 == 0 && (((uintptr_t)gate_t | (uintptr_t)gate | (uintptr_t)dt) & 15) == 0),
                "dl_ln_modulate_bwd: the fused gate backward needs gate_t, gate, dt and dgate (16-byte aligned)");
+  if (nj > 2) {  // 1024 < D <= 4096: shares of at most 64 rows
+    const int split_r = (int)((rows_per_mod + 63) / 64);
+#define LAUNCH_ROWS(NJ)                                                                                                      \
+  hipLaunchKernelGGL(ln_mod_bwd_rows_k<NJ>, groups * split_r, 256, 0, (hipStream_t)stream, (const bf16_t*)dout,              \
+                     (const bf16_t*)x, w, b, (const bf16_t*)scale, ld_mod, rows_per_mod, mean, rstd, (const bf16_t*)dres,    \
+                     (bf16_t*)dx, dscale, dshift, ld_dmod, dwb_partial, (const bf16_t*)gate_t, (const bf16_t*)gate, ld_gate, \
+                     (bf16_t*)dt, dgate, split_r, M, (int)D)
+    if (D <= 2048) LAUNCH_ROWS(1);
+    else LAUNCH_ROWS(2);
+#undef LAUNCH_ROWS
+    DL_LAUNCH_CHECK();
+    return DL_OK;
+  }
   const size_t lds = (size_t)3 * D * sizeof(float);
   const bool pf = false;  // (the two-row prefetch ring of ln_mod_bwd_k<true> measured +0.3 ms per step: round 1)
 #define LAUNCH(NJ, PF)                                                                                                        \
@@ -456,6 +674,103 @@ __global__ __launch_bounds__(256) void ln_mod_bwd_tok_k(const bf16_t* __restrict
   for (int i = threadIdx.x; i < 2 * D; i += 256) unsafeAtomicAdd(dst + i, red[i]);
 }
 
+// 1024 < D <= 4096: one row at a time per 256-thread workgroup; the affine-gradient sums stay in the registers of the thread that
+// owns the column until they are added to the workgroup's partial slab (no LDS slab)
+template <int NJ>
+__global__ __launch_bounds__(256) void ln_mod_bwd_tok_rows_k(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ x,
+                                                             const float* __restrict__ w, const float* __restrict__ b,
+                                                             const bf16_t* __restrict__ scale, int64_t ld_mod,
+                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                             const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
+                                                             bf16_t* __restrict__ dscale, bf16_t* __restrict__ dshift, int64_t ld_dmod,
+                                                             float* __restrict__ dwb, int n_part, const bf16_t* __restrict__ gt,
+                                                             const bf16_t* __restrict__ ggate, int64_t ld_gate,
+                                                             bf16_t* __restrict__ gdt, bf16_t* __restrict__ dgate, int rows_per_wg,
+                                                             int64_t M, int D) {
+  __shared__ float red[2 * 2 * 4];
+  const int tid = threadIdx.x;
+  const int D8 = D >> 3;
+  const float invD = 1.0f / (float)D;
+  int slot = 0;
+  float wv[NJ][8], bv[NJ][8], a_dw[NJ][8], a_db[NJ][8];
+  load_row_f32<NJ, 256>(w, D8, tid, wv, 1.0f);
+  load_row_f32<NJ, 256>(b, D8, tid, bv, 0.0f);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a_dw[j][e] = a_db[j][e] = 0.f;
+  const int64_t row_begin = (int64_t)blockIdx.x * rows_per_wg;
+  const int64_t row_end = row_begin + rows_per_wg < M ? row_begin + rows_per_wg : M;
+  for (int64_t row = row_begin; row < row_end; ++row) {
+    float dv[NJ][8], xv[NJ][8], rv[NJ][8], sc[NJ][8], ov[NJ][8];
+    load_row<NJ, 256>(dout + row * D, D8, tid, dv);
+    load_row<NJ, 256>(x + row * D, D8, tid, xv);
+    load_row<NJ, 256>(scale + row * ld_mod, D8, tid, sc);
+    if (dres) load_row<NJ, 256>(dres + row * D, D8, tid, rv);
+    const float mu = mean[row], rs = rstd[row];
+    float s[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const bool on = (tid + 256 * j) < D8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float xh = on ? (xv[j][e] - mu) * rs : 0.f;
+        const float d = on ? dv[j][e] : 0.f;
+        ov[j][e] = d * (xh * wv[j][e] + bv[j][e]);  // dscale of this token
+        const float dy = d * (1.0f + sc[j][e]);
+        a_dw[j][e] += dy * xh;
+        a_db[j][e] += dy;
+        const float dxh = dy * wv[j][e];
+        s[0] += dxh;
+        s[1] += dxh * xh;
+        xv[j][e] = xh;
+        dv[j][e] = dxh;
+        if (!dres) rv[j][e] = 0.f;
+      }
+    }
+    store_row<NJ, 256>(dscale + row * ld_dmod, D8, tid, ov);
+    {  // dshift of this token = dout (re-read: the registers now hold dxh)
+      float sv[NJ][8];
+      load_row<NJ, 256>(dout + row * D, D8, tid, sv);
+      store_row<NJ, 256>(dshift + row * ld_dmod, D8, tid, sv);
+    }
+    rows_sum<2>(s, red, slot);
+    const float c1 = s[0] * invD, c2 = s[1] * invD;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) rv[j][e] += rs * (dv[j][e] - c1 - xv[j][e] * c2);
+    store_row<NJ, 256>(dx + row * D, D8, tid, rv);
+    if (gt) {  // fused backward of the gated residual that follows in the chain, per-token gate
+      float tv[NJ][8], gv[NJ][8];
+      load_row<NJ, 256>(gt + row * D, D8, tid, tv);
+      load_row<NJ, 256>(ggate + row * ld_gate, D8, tid, gv);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float dxr = bf2f(f2bf(rv[j][e]));
+          tv[j][e] = dxr * tv[j][e];   // dgate of this token
+          rv[j][e] = dxr * gv[j][e];   // dt
+        }
+      store_row<NJ, 256>(dgate + row * ld_dmod, D8, tid, tv);
+      store_row<NJ, 256>(gdt + row * D, D8, tid, rv);
+    }
+  }
+  if (!dwb) return;
+  float* dst = dwb + (size_t)(blockIdx.x % n_part) * 2 * D;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = tid + 256 * j;
+    if (c >= D8) continue;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      unsafeAtomicAdd(dst + c * 8 + e, a_dw[j][e]);
+      unsafeAtomicAdd(dst + D + c * 8 + e, a_db[j][e]);
+    }
+  }
+}
+
 extern "C" int dl_ln_modulate_bwd_tok(const void* dout, const void* x, const float* w, const float* b, const void* scale,
                                       int64_t ld_mod, const float* mean, const float* rstd, const void* dres, void* dx,
                                       void* dscale, void* dshift, int64_t ld_dmod, float* dwb_partial, int64_t n_part,
@@ -464,7 +779,9 @@ extern "C" int dl_ln_modulate_bwd_tok(const void* dout, const void* x, const flo
   DL_CHECK_ARG(dout && x && scale && mean && rstd && dx && dscale && dshift && M > 0, "dl_ln_modulate_bwd_tok: null operand");
   DL_CHECK_ARG((w == nullptr) == (b == nullptr) && (w == nullptr) == (dwb_partial == nullptr) && (!dwb_partial || n_part > 0),
                "dl_ln_modulate_bwd_tok: w, b and dwb_partial must all be given or all NULL");
-  DL_CHECK_ARG(D % 8 == 0 && D <= 512 * MAXJ && ld_mod % 8 == 0 && ld_dmod % 8 == 0, "dl_ln_modulate_bwd_tok: D=%lld", (long long)D);
+  DL_CHECK_ARG(D % 8 == 0 && D <= ROW_MAX_D, "dl_ln_modulate_bwd_tok: D=%lld (a multiple of 8 up to 4096)", (long long)D);
+  DL_CHECK_ARG(ld_mod % 8 == 0 && ld_dmod % 8 == 0, "dl_ln_modulate_bwd_tok: ld_mod=%lld ld_dmod=%lld", (long long)ld_mod,
+               (long long)ld_dmod);
   DL_CHECK_ARG((((uintptr_t)dout | (uintptr_t)x | (uintptr_t)scale | (uintptr_t)dx | (uintptr_t)dres | (uintptr_t)dscale |
                  (uintptr_t)dshift) & 15) == 0, "dl_ln_modulate_bwd_tok: 16-byte alignment");
   DL_CHECK_ARG(!gate_t || (gate && dt && dgate && ld_gate % 8 == 0 &&
@@ -479,9 +796,17 @@ extern "C" int dl_ln_modulate_bwd_tok(const void* dout, const void* x, const flo
                      (const bf16_t*)scale, ld_mod, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, (bf16_t*)dscale, (bf16_t*)dshift,  \
                      ld_dmod, dwb_partial, (int)n_part, (const bf16_t*)gate_t, (const bf16_t*)gate, ld_gate, (bf16_t*)dt,            \
                      (bf16_t*)dgate, rows_per_wg, M, (int)D)
+#define LAUNCH_ROWS(NJ)                                                                                                       \
+  hipLaunchKernelGGL(ln_mod_bwd_tok_rows_k<NJ>, grid, 256, 0, (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)x, w, b, \
+                     (const bf16_t*)scale, ld_mod, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, (bf16_t*)dscale,               \
+                     (bf16_t*)dshift, ld_dmod, dwb_partial, (int)n_part, (const bf16_t*)gate_t, (const bf16_t*)gate, ld_gate,   \
+                     (bf16_t*)dt, (bf16_t*)dgate, rows_per_wg, M, (int)D)
   if (nj == 1) LAUNCH(1);
-  else LAUNCH(2);
+  else if (nj == 2) LAUNCH(2);
+  else if (D <= 2048) LAUNCH_ROWS(1);
+  else LAUNCH_ROWS(2);
 #undef LAUNCH
+#undef LAUNCH_ROWS
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
@@ -534,20 +859,78 @@ __global__ __launch_bounds__(512) void gate_bwd_k(const bf16_t* __restrict__ dou
   }
 }
 
+// 1024 < D <= 4096: two 256-thread row groups per sample (even / odd rows); thread t of a group owns chunks t + 256 j, so its
+// column sums are complete in its registers.  Group 1 hands its sums to group 0 through ONE [D] LDS row (16 KiB at D = 4096), and
+// group 0 writes (own + other) in that fixed order: plain stores, deterministic like gate_bwd_k.
+template <int NJ>
+__global__ __launch_bounds__(512) void gate_bwd_rows_k(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ t,
+                                                       const bf16_t* __restrict__ gate, int64_t ld_mod, int64_t rows_per_mod,
+                                                       bf16_t* __restrict__ dt, float* __restrict__ dgate, int64_t ld_dmod, int64_t M,
+                                                       int D) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* red = (float*)smem;  // [D]
+  const int tid = threadIdx.x & 255, rg = threadIdx.x >> 8;
+  const int D8 = D >> 3;
+  const int64_t g = blockIdx.x;
+  float gv[NJ][8], acc[NJ][8];
+  load_row<NJ, 256>(gate + g * ld_mod, D8, tid, gv);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+  const int64_t row_end = (g + 1) * rows_per_mod < M ? (g + 1) * rows_per_mod : M;
+  for (int64_t row = g * rows_per_mod + rg; row < row_end; row += 2) {
+    float dv[NJ][8], tv[NJ][8];
+    load_row<NJ, 256>(dout + row * D, D8, tid, dv);
+    load_row<NJ, 256>(t + row * D, D8, tid, tv);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        acc[j][e] += dv[j][e] * tv[j][e];
+        dv[j][e] *= gv[j][e];
+      }
+    store_row<NJ, 256>(dt + row * D, D8, tid, dv);
+  }
+  if (rg == 1) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int c = tid + 256 * j;
+      if (c < D8) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[c * 8 + e] = acc[j][e];
+      }
+    }
+  }
+  __syncthreads();
+  if (rg == 0) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int c = tid + 256 * j;
+      if (c >= D8) continue;
+      float* o = dgate + g * ld_dmod + c * 8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = acc[j][e] + red[c * 8 + e];
+    }
+  }
+}
+
 extern "C" int dl_gate_bwd(const void* dout, const void* t, const void* gate, int64_t ld_mod, int64_t rows_per_mod,
                            void* dt, float* dgate, int64_t ld_dmod, int64_t M, int64_t D, dl_stream_t stream) {
   DL_CHECK_ARG(dout && t && gate && dt && dgate && M > 0, "dl_gate_bwd: null operand");
-  DL_CHECK_ARG(D % 8 == 0 && D <= 512 * MAXJ && ld_mod % 8 == 0 && rows_per_mod > 0 && M % rows_per_mod == 0,
-               "dl_gate_bwd: bad dims");
+  DL_CHECK_ARG(D % 8 == 0 && D <= ROW_MAX_D, "dl_gate_bwd: D=%lld (a multiple of 8 up to 4096)", (long long)D);
+  DL_CHECK_ARG(ld_mod % 8 == 0 && rows_per_mod > 0 && M % rows_per_mod == 0, "dl_gate_bwd: bad dims");
   DL_CHECK_ARG((((uintptr_t)dout | (uintptr_t)t | (uintptr_t)gate | (uintptr_t)dt) & 15) == 0, "dl_gate_bwd: alignment");
   const int nj = cdiv(D, 512);
   const int groups = (int)(M / rows_per_mod);
-  const size_t lds = (size_t)LNB_WAVES * D * sizeof(float);
-#define LAUNCH(NJ)                                                                                               \
-  hipLaunchKernelGGL(gate_bwd_k<NJ>, groups, 512, lds, (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)t, \
+  const size_t lds = (size_t)(nj <= 2 ? LNB_WAVES : 1) * D * sizeof(float);
+#define LAUNCH(K)                                                                                               \
+  hipLaunchKernelGGL(K, groups, 512, lds, (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)t, \
                      (const bf16_t*)gate, ld_mod, rows_per_mod, (bf16_t*)dt, dgate, ld_dmod, M, (int)D)
-  if (nj == 1) LAUNCH(1);
-  else LAUNCH(2);
+  if (nj == 1) LAUNCH(gate_bwd_k<1>);
+  else if (nj == 2) LAUNCH(gate_bwd_k<2>);
+  else if (D <= 2048) LAUNCH(gate_bwd_rows_k<1>);
+  else LAUNCH(gate_bwd_rows_k<2>);
 #undef LAUNCH
   DL_LAUNCH_CHECK();
   return DL_OK;
@@ -621,6 +1004,76 @@ __global__ __launch_bounds__(256) void qk_norm_rope_fwd_k(const bf16_t* __restri
   }
 }
 
+// 1024 < D <= 4096: one token per 256-thread workgroup, thread t owns chunks t + 256 j of the q, k and v thirds; the two RMS
+// statistics are over the whole D-wide row (rows_sum)
+template <int NJ>
+__global__ __launch_bounds__(256) void qk_norm_rope_fwd_rows_k(const bf16_t* __restrict__ qkv, const float* __restrict__ sq,
+                                                               const float* __restrict__ sk, const float* __restrict__ cs,
+                                                               const float* __restrict__ sn, bf16_t* __restrict__ qo,
+                                                               bf16_t* __restrict__ ko, bf16_t* __restrict__ vo,
+                                                               float* __restrict__ rrms, int64_t M, int N, int H, int dh, int rot,
+                                                               float eps, const int* __restrict__ pos, int n_dst, int n_off) {
+  __shared__ float red[2 * 2 * 4];
+  const int tid = threadIdx.x;
+  const int D = H * dh, D8 = D >> 3;
+  const float invD = 1.0f / (float)D;
+  int slot = 0;
+  float wq[NJ][8], wk[NJ][8];
+  load_row_f32<NJ, 256>(sq, D8, tid, wq, 1.0f);
+  load_row_f32<NJ, 256>(sk, D8, tid, wk, 1.0f);
+  for (int64_t row = blockIdx.x; row < M; row += gridDim.x) {
+    const bf16_t* p = qkv + row * 3 * D;
+    float q[NJ][8], k[NJ][8], v[NJ][8];
+    load_row<NJ, 256>(p, D8, tid, q);
+    load_row<NJ, 256>(p + D, D8, tid, k);
+    if (vo) load_row<NJ, 256>(p + 2 * D, D8, tid, v);
+    float s[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        s[0] += q[j][e] * q[j][e];
+        s[1] += k[j][e] * k[j][e];
+      }
+    rows_sum<2>(s, red, slot);
+    const float rq = rsqrtf(s[0] * invD + eps), rk = rsqrtf(s[1] * invD + eps);
+    const int64_t b = row / N;
+    const int n = (int)(row - b * N);
+    const int nt = pos ? pos[row] : n;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int c = tid + 256 * j;
+      if (c >= D8) continue;
+      const int col = c * 8, h = col / dh, d0 = col - h * dh;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        q[j][e] = q[j][e] * rq * wq[j][e];
+        k[j][e] = k[j][e] * rk * wk[j][e];
+      }
+      if (d0 < rot) {
+        const f32x4_t cc = *(const f32x4_t*)(cs + (int64_t)nt * (rot >> 1) + (d0 >> 1));
+        const f32x4_t ss = *(const f32x4_t*)(sn + (int64_t)nt * (rot >> 1) + (d0 >> 1));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float qa = q[j][2 * i], qb = q[j][2 * i + 1], ka = k[j][2 * i], kb = k[j][2 * i + 1];
+          q[j][2 * i] = qa * cc[i] - qb * ss[i];
+          q[j][2 * i + 1] = qa * ss[i] + qb * cc[i];
+          k[j][2 * i] = ka * cc[i] - kb * ss[i];
+          k[j][2 * i + 1] = ka * ss[i] + kb * cc[i];
+        }
+      }
+      const int64_t o = (((int64_t)b * H + h) * n_dst + n_off + n) * dh + d0;
+      *(u32x4_t*)(qo + o) = pack8(q[j]);
+      *(u32x4_t*)(ko + o) = pack8(k[j]);
+      if (vo) *(u32x4_t*)(vo + o) = pack8(v[j]);
+    }
+    if (tid == 0) {
+      rrms[row * 2] = rq;
+      rrms[row * 2 + 1] = rk;
+    }
+  }
+}
+
 extern "C" int dl_qk_norm_rope_fwd_ex(const void* qkv, const float* scale_q, const float* scale_k, const float* cos,
                                       const float* sin, void* q, void* k, void* v, float* rrms, int64_t B, int64_t N,
                                       int64_t H, int64_t dh, int64_t rot, float eps, const int32_t* pos, int64_t n_dst,
@@ -639,8 +1092,8 @@ extern "C" int dl_qk_norm_rope_fwd_ex(const void* qkv, const float* scale_q, con
   DL_CHECK_ARG(n_off >= 0 && n_off + N <= n_dst, "dl_qk_norm_rope_fwd: row window [%lld, %lld) outside n_dst=%lld",
                (long long)n_off, (long long)(n_off + N), (long long)n_dst);
   const int64_t D = H * dh;
-  DL_CHECK_ARG(dh % 8 == 0 && rot % 8 == 0 && rot <= dh && D <= 512 * MAXJ, "dl_qk_norm_rope_fwd: dh=%lld rot=%lld",
-               (long long)dh, (long long)rot);
+  DL_CHECK_ARG(H > 0 && D <= ROW_MAX_D, "dl_qk_norm_rope_fwd: inner width H * dh = %lld (at most 4096)", (long long)D);
+  DL_CHECK_ARG(dh % 8 == 0 && rot % 8 == 0 && rot <= dh, "dl_qk_norm_rope_fwd: dh=%lld rot=%lld", (long long)dh, (long long)rot);
   const int64_t M = B * N;
   int grid = cdiv(M, 4);
   if (grid > 4096) grid = 4096;
@@ -649,9 +1102,16 @@ extern "C" int dl_qk_norm_rope_fwd_ex(const void* qkv, const float* scale_q, con
   hipLaunchKernelGGL(qk_norm_rope_fwd_k<NJ>, grid, 256, 0, (hipStream_t)stream, (const bf16_t*)qkv, scale_q, scale_k, \
                      cos, sin, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, rrms, M, (int)N, (int)H, (int)dh, (int)rot, eps, pos,      \
                      (int)n_dst, (int)n_off)
+#define LAUNCH_ROWS(NJ)                                                                                                          \
+  hipLaunchKernelGGL(qk_norm_rope_fwd_rows_k<NJ>, (int)(M < 4096 ? M : 4096), 256, 0, (hipStream_t)stream, (const bf16_t*)qkv,    \
+                     scale_q, scale_k, cos, sin, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, rrms, M, (int)N, (int)H, (int)dh, (int)rot, \
+                     eps, pos, (int)n_dst, (int)n_off)
   if (nj == 1) LAUNCH(1);
-  else LAUNCH(2);
+  else if (nj == 2) LAUNCH(2);
+  else if (D <= 2048) LAUNCH_ROWS(1);
+  else LAUNCH_ROWS(2);
 #undef LAUNCH
+#undef LAUNCH_ROWS
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
@@ -766,6 +1226,93 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void q
 }
 __global__ __launch_bounds__(256) void qk_norm_rope_bwd_wide_k(QKB_ARGS) { qk_norm_rope_bwd_body<2>(QKB_PASS); }
 
+// 1024 < D <= 4096: one token per 256-thread workgroup (rows_sum for the two row reductions); the thread that owns a column keeps
+// its scale-gradient sums in registers and adds them to dscale at the end (no LDS slab)
+template <int NJ>
+__global__ __launch_bounds__(256) void qk_norm_rope_bwd_rows_k(QKB_ARGS) {
+  __shared__ float red[2 * 2 * 4];
+  const int tid = threadIdx.x;
+  const int D = H * dh, D8 = D >> 3;
+  const float invD = 1.0f / (float)D;
+  int slot = 0;
+  float wq[NJ][8], wk[NJ][8], aq[NJ][8], ak[NJ][8];
+  load_row_f32<NJ, 256>(sq, D8, tid, wq, 1.0f);
+  load_row_f32<NJ, 256>(sk, D8, tid, wk, 1.0f);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) aq[j][e] = ak[j][e] = 0.f;
+  for (int64_t row = blockIdx.x; row < M; row += gridDim.x) {
+    const int64_t b = row / N;
+    const int n = (int)(row - b * N);
+    const int nt = pos ? pos[row] : n;
+    const bf16_t* p = qkv + row * 3 * D;
+    float xq[NJ][8], xk[NJ][8], gq[NJ][8], gk[NJ][8], gv[NJ][8];
+    load_row<NJ, 256>(p, D8, tid, xq);
+    load_row<NJ, 256>(p + D, D8, tid, xk);
+    const float rq = rrms[row * 2], rk = rrms[row * 2 + 1];
+    float s[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int c = tid + 256 * j;
+      if (c >= D8) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gq[j][e] = gk[j][e] = gv[j][e] = 0.f;
+        continue;
+      }
+      const int col = c * 8, h = col / dh, d0 = col - h * dh;
+      const int64_t o = (((int64_t)b * H + h) * n_dst + n_off + n) * dh + d0;
+      unpack8(*(const u32x4_t*)(dq + o), gq[j]);
+      unpack8(*(const u32x4_t*)(dk + o), gk[j]);
+      if (dv) unpack8(*(const u32x4_t*)(dv + o), gv[j]);
+      if (d0 < rot) {  // transpose of the rotation
+        const f32x4_t cc = *(const f32x4_t*)(cs + (int64_t)nt * (rot >> 1) + (d0 >> 1));
+        const f32x4_t ss = *(const f32x4_t*)(sn + (int64_t)nt * (rot >> 1) + (d0 >> 1));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float qa = gq[j][2 * i], qb = gq[j][2 * i + 1], ka = gk[j][2 * i], kb = gk[j][2 * i + 1];
+          gq[j][2 * i] = qa * cc[i] + qb * ss[i];
+          gq[j][2 * i + 1] = -qa * ss[i] + qb * cc[i];
+          gk[j][2 * i] = ka * cc[i] + kb * ss[i];
+          gk[j][2 * i + 1] = -ka * ss[i] + kb * cc[i];
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        aq[j][e] += gq[j][e] * xq[j][e] * rq;  // dscale
+        ak[j][e] += gk[j][e] * xk[j][e] * rk;
+        gq[j][e] *= wq[j][e];                  // s * dy
+        gk[j][e] *= wk[j][e];
+        s[0] += gq[j][e] * xq[j][e];
+        s[1] += gk[j][e] * xk[j][e];
+      }
+    }
+    rows_sum<2>(s, red, slot);
+    const float mq = s[0] * invD * rq * rq * rq, mk = s[1] * invD * rk * rk * rk;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        gq[j][e] = rq * gq[j][e] - xq[j][e] * mq;
+        gk[j][e] = rk * gk[j][e] - xk[j][e] * mk;
+      }
+    bf16_t* o = dqkv + row * 3 * D;
+    store_row<NJ, 256>(o, D8, tid, gq);
+    store_row<NJ, 256>(o + D, D8, tid, gk);
+    if (dv) store_row<NJ, 256>(o + 2 * D, D8, tid, gv);
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = tid + 256 * j;
+    if (c >= D8) continue;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      unsafeAtomicAdd(&dscale[c * 8 + e], aq[j][e]);
+      unsafeAtomicAdd(&dscale[D + c * 8 + e], ak[j][e]);
+    }
+  }
+}
+
 extern "C" int dl_qk_norm_rope_bwd_ex(const void* dq, const void* dk, const void* dv, const void* qkv,
                                    const float* scale_q, const float* scale_k, const float* cos, const float* sin,
                                    const float* rrms, void* dqkv, float* dscale, int64_t B, int64_t N, int64_t H,
@@ -783,14 +1330,28 @@ extern "C" int dl_qk_norm_rope_bwd_ex(const void* dq, const void* dk, const void
   DL_CHECK_ARG(dq && dk && qkv && scale_q && scale_k && cos && sin && rrms && dqkv && dscale && B > 0 && N > 0,
                "dl_qk_norm_rope_bwd: null operand");
   const int64_t D = H * dh;
-  DL_CHECK_ARG(dh % 8 == 0 && rot % 8 == 0 && rot <= dh && D <= 512 * MAXJ && n_off >= 0 && n_off + N <= n_dst,
-               "dl_qk_norm_rope_bwd: bad dims");
+  DL_CHECK_ARG(H > 0 && D <= ROW_MAX_D, "dl_qk_norm_rope_bwd: inner width H * dh = %lld (at most 4096)", (long long)D);
+  DL_CHECK_ARG(dh % 8 == 0 && rot % 8 == 0 && rot <= dh && n_off >= 0 && n_off + N <= n_dst,
+               "dl_qk_norm_rope_bwd: bad dims (dh=%lld rot=%lld, rows [%lld, %lld) of n_dst=%lld)", (long long)dh, (long long)rot,
+               (long long)n_off, (long long)(n_off + N), (long long)n_dst);
   const int64_t M = B * N;
   // >= 16 rows per wave so the atomics are amortised; a few thousand rows would leave half the chip idle that way: 4 rows per wave
   int grid = cdiv(M, M >= 32768 ? 4 * 16 : 4 * 4);
   if (grid > 1024) grid = 1024;
   if (grid < 1) grid = 1;
   const int nj = cdiv(D, 512);
+  if (nj > 2) {  // 1024 < D <= 4096: >= 16 rows per workgroup, at most four workgroups per CU
+    const int grid_r = (int)(cdiv(M, 16) < 1024 ? cdiv(M, 16) : 1024);
+#define LAUNCH_ROWS(NJ)                                                                                                        \
+  hipLaunchKernelGGL(qk_norm_rope_bwd_rows_k<NJ>, grid_r, 256, 0, (hipStream_t)stream, (const bf16_t*)dq, (const bf16_t*)dk, \
+                     (const bf16_t*)dv, (const bf16_t*)qkv, scale_q, scale_k, cos, sin, rrms, (bf16_t*)dqkv, dscale, M,       \
+                     (int)N, (int)H, (int)dh, (int)rot, pos, (int)n_dst, (int)n_off)
+    if (D <= 2048) LAUNCH_ROWS(1);
+    else LAUNCH_ROWS(2);
+#undef LAUNCH_ROWS
+    DL_LAUNCH_CHECK();
+    return DL_OK;
+  }
   const size_t lds = (size_t)4 * 2 * D * sizeof(float);
 #define QKB_KERN_1 qk_norm_rope_bwd_k
 #define QKB_KERN_2 qk_norm_rope_bwd_wide_k

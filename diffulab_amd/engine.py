@@ -45,6 +45,10 @@ def _rup(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+ROW_MAX_DIM = 4096  # widest token row of the bf16 regime's row kernels (csrc/norm.hip: one wave per row up to 1024, one workgroup above)
+F32_MAX_DIM = 1024  # widest token row of the fp32 regime (csrc/f32.hip, one wave per row)
+
+
 @dataclass
 class DiTDims:
     input_channels: int = 4
@@ -76,8 +80,8 @@ class DiTDims:
             raise NotImplementedError(f"HIP attention kernels are built for head_dim 64 (got {self.head_dim})")
         if D % 64 or E % 64 or self.frequency_embedding % 64:
             raise NotImplementedError("inner_dim, embedding_dim and frequency_embedding must be multiples of 64")
-        if D > 1024:
-            raise NotImplementedError("row kernels support inner_dim <= 1024")
+        if D > ROW_MAX_DIM:
+            raise NotImplementedError(f"the bf16 regime's row kernels take inner_dim <= {ROW_MAX_DIM} (got {D})")
         if sum(self.rope_axes_dim) > self.head_dim or sum(self.rope_axes_dim) % 8:
             raise NotImplementedError("rotary width must be a multiple of 8 and <= head_dim")
         if len(self.rope_axes_dim) != 2:
@@ -382,9 +386,9 @@ class DiTEngine:
             w["dh1"] = z(Bp, E, dtype=f32)
             w["dpre1"] = z(Bp, E)
             # partial slabs of the grouped weight-gradient launch (dl_gemm_tn_group: the four linears of a block in one atomics-free
-            # launch): 8 token ranges x (4 + 3 mlp_ratio) D^2 floats; one set, the side stream runs the blocks one after the other
+            # launch): 8 token ranges (fewer above D = 1024) x (4 + 3 mlp_ratio) D^2 floats; one set, the side stream runs the blocks one after the other
             if self._grouped_wgrad(M):
-                w["tn_slab"] = torch.empty(8 * (4 + 3 * d.mlp_ratio) * D * D, device=dev, dtype=f32)
+                w["tn_slab"] = torch.empty(ops.WgradGroups.slab_floats(D, d.mlp_ratio * D), device=dev, dtype=f32)
             # scratch of the bit-reproducible small GEMMs / column sums of the head and the conditioning path (partial images per
             # split, folded in a fixed order: ops.gemm_tn / gemm_nt / colsum with scratch=): two images of the stacked adaLN
             # weight gradient is the largest user

@@ -18,7 +18,7 @@ import torch
 from torch import Tensor
 
 from . import ops, tuning
-from .engine import DiTDims, DiTEngine, _rup
+from .engine import ROW_MAX_DIM, DiTDims, DiTEngine, _rup
 
 STREAMS = ("input", "context")
 
@@ -35,8 +35,9 @@ class JointDims(DiTDims):
         D, E = self.inner_dim, self.embedding_dim
         if self.head_dim != 64:
             raise NotImplementedError(f"HIP attention kernels are built for head_dim 64 (got {self.head_dim})")
-        if D % 64 or E % 64 or self.frequency_embedding % 64 or D > 1024:
-            raise NotImplementedError("inner_dim (<= 1024), embedding_dim and frequency_embedding must be multiples of 64")
+        if D % 64 or E % 64 or self.frequency_embedding % 64 or D > ROW_MAX_DIM:
+            raise NotImplementedError(f"inner_dim (<= {ROW_MAX_DIM}), embedding_dim and frequency_embedding must be multiples of 64 "
+                                      f"(got inner_dim {D})")
         if len(self.rope_axes_dim) != 3 or any(a % 2 for a in self.rope_axes_dim) or sum(self.rope_axes_dim) % 8 or \
                 sum(self.rope_axes_dim) > self.head_dim:
             raise NotImplementedError("joint blocks use a 3-axis RoPE (text position, row, col) with even axis widths whose sum is "

@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 from ... import tuning
+from ...engine import F32_MAX_DIM
 
 try:  # python >= 3.11
     from typing import NotRequired, Required
@@ -95,6 +96,10 @@ class FlatArenaDenoiser(Denoiser):
     #      precision_type="no", trainers/common.py:76,105).  Denoisers that have an fp32 engine list it in `precisions`.
     precisions: tuple[str, ...] = ("bf16",)
 
+    def _fp32_width_ok(self) -> bool:
+        """the fp32 engines keep one wave per token row: inner_dim <= F32_MAX_DIM (wider models are bf16-only)"""
+        return getattr(getattr(self, "dims", None), "inner_dim", 0) <= F32_MAX_DIM
+
     @property
     def precision(self) -> str:
         return self.__dict__.get("_precision", "bf16")
@@ -102,6 +107,10 @@ class FlatArenaDenoiser(Denoiser):
     def set_precision(self, precision: str) -> "FlatArenaDenoiser":
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision must be 'bf16' or 'fp32' (got {precision!r})")
+        if precision == "fp32" and not self._fp32_width_ok():
+            raise NotImplementedError(f"diffulab_amd.{type(self).__name__}: the fp32 regime's row kernels take inner_dim <= {F32_MAX_DIM} "
+                                      f"(got {self.dims.inner_dim}); this width runs in the bf16 regime only (set_precision('bf16'), "
+                                      "trainer precision_type='bf16')")
         if precision not in self.precisions:
             raise NotImplementedError(f"diffulab_amd.{type(self).__name__} has no {precision} launch sequence (built: "
                                       f"{', '.join(self.precisions)}); the fp32-class regime exists for the class-conditional forms (MMDiT / SprintDiT simple_dit=True, DDT simple_ddt=True) and UNetModel")

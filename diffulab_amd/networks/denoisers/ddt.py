@@ -121,7 +121,7 @@ class DDT(FlatArenaDenoiser):
 
     @property
     def precisions(self) -> tuple[str, ...]:  # the fp32-class regime exists for the class-conditional form (ddt_engine_f32.py)
-        return ("bf16", "fp32") if self.simple_ddt else ("bf16",)
+        return ("bf16", "fp32") if self.simple_ddt and self._fp32_width_ok() else ("bf16",)
 
     def _make_engine(self, device: torch.device):
         if self.precision == "fp32":

@@ -246,7 +246,7 @@ class MMDiT(FlatArenaDenoiser):
 
     @property
     def precisions(self) -> tuple[str, ...]:  # the fp32-class regime is built for the class-conditional DiT (engine_f32.py)
-        return ("bf16", "fp32") if self.simple_dit else ("bf16",)
+        return ("bf16", "fp32") if self.simple_dit and self._fp32_width_ok() else ("bf16",)
 
     def _make_engine(self, device: torch.device) -> DiTEngine:
         if self.simple_dit:

@@ -141,7 +141,7 @@ class SprintDiT(FlatArenaDenoiser):
 
     @property
     def precisions(self) -> tuple[str, ...]:  # the fp32-class regime exists for the class-conditional form
-        return ("bf16", "fp32") if self.simple_dit else ("bf16",)
+        return ("bf16", "fp32") if self.simple_dit and self._fp32_width_ok() else ("bf16",)
 
     def _make_engine(self, device: torch.device):
         if self.precision == "fp32":

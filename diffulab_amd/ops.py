@@ -395,9 +395,14 @@ class WgradGroups:
         self.pending: dict[int, list[tuple[Tensor, Tensor, Tensor]]] = {}
 
     @staticmethod
-    def slab_floats(D: int, F: int, ranges: int = 8) -> int:
-        """scratch for the four linears of a block with inner width D and MLP width F (qkv, proj, up, down) at `ranges` token ranges"""
-        return ranges * (4 * D * D + 3 * D * F)
+    def slab_floats(D: int, F: int, ranges: int | None = None) -> int:
+        """scratch for the four linears of a block with inner width D and MLP width F (qkv, proj, up, down) at `ranges` token ranges.
+        Default: 8 up to D = 1024; wider blocks have enough 384 x 192 tiles to fill 256 CUs with fewer token ranges (the launch splits
+        by the CUs per tile and by what the slab holds), so the slab stops growing with 8 D^2 (8.6 GB at D = 4096)"""
+        per = 4 * D * D + 3 * D * F
+        if ranges is None:
+            ranges = 8 if D <= 1024 else max(1, min(8, 256 * 384 * 192 // per))
+        return ranges * per
 
     @staticmethod
     def widths_ok(D: int, F: int) -> bool:

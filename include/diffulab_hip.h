@@ -195,6 +195,9 @@ DL_API int dl_colsum_det(const void* x, int dtype, int64_t ld, float* out, int64
                          int64_t scratch_floats, dl_stream_t stream);
 
 /* ------------------------------------------------------------------ adaLN / norms */
+/* Width of the row kernels below (dl_ln_modulate_fwd / _bwd / _bwd_tok, dl_gate_bwd, dl_qk_norm_rope_fwd[_ex] / _bwd[_ex]): D % 8 == 0
+ * and D <= 4096 (for QK-norm D = H * dh).  One 64-lane wave owns a row up to D = 1024; wider rows are owned by one 256-thread
+ * workgroup (row statistics summed across its four waves in a fixed order).  Wider calls return DL_ERR_INVALID before any launch. */
 /* modulate(LayerNorm(x)) mmdit.py:299,305,547 + nn.py:539:  out = (LN(x) * w + b) * (1 + scale) + shift.
  * w/b f32 [D] or NULL (norm_final has no affine); scale/shift bf16 rows with stride ld_mod, one row per
  * rows_per_mod tokens.  mean/rstd f32 [M] saved for the backward.
@@ -210,7 +213,7 @@ DL_API int dl_ln_modulate_fwd(const void* x, const float* w, const float* b, con
  *   dscale[g,:] += sum_{m in g} dout * (xhat*w+b) ; dshift[g,:] += sum dout     (f32 rows, stride ld_dmod: the f32 image
  *                  of the modulation-gradient matrix, zeroed by the caller once per step, cast to bf16 once at the end)
  *   dwb_partial f32 [groups, 2, D] += per-group sums of dw, db (NULL when w == NULL); folded by dl_reduce_rows_f32.
- * The workgroups that share a sample meet in these accumulators through f32 atomics (no second pass).
+ * The workgroups that share a sample meet in these accumulators through f32 atomics (no second pass), at every D <= 4096.
  * Optional fused backward of the gated residual that follows in the backward chain (gate_t != NULL; the same arithmetic as
  * dl_gate_bwd on the dx just produced): dt[m,:] = gate[g,:] * dx[m,:] (bf16), dgate[g,:] += sum_{m in g} dx[m,:] * gate_t[m,:]
  * (f32, row stride ld_dmod). */
@@ -266,7 +269,7 @@ DL_API int dl_ddt_cond_fwd(const void* enc, int64_t ld, const float* temb, int64
 DL_API int dl_ddt_cond_bwd(const void* dsz, const void* enc, int64_t ld, const float* temb, int64_t ld_t, int64_t B, int64_t N,
                            int64_t D, void* denc, float* dtemb, dl_stream_t stream);
 /* x_new = x + gate * t backward (mmdit.py:296-307): dt = gate * dout (bf16) ; dgate[g,:] = sum_{m in g} dout * t (f32,
- * written, row stride ld_dmod) */
+ * written, row stride ld_dmod).  D % 8 == 0, D <= 4096. */
 DL_API int dl_gate_bwd(const void* dout, const void* t, const void* gate, int64_t ld_mod, int64_t rows_per_mod,
                        void* dt, float* dgate, int64_t ld_dmod, int64_t M, int64_t D, dl_stream_t stream);
 /* QKNorm (nn.py:427-431,473-475: RMS over the FULL inner dim, eps 1e-6) + N-D RoPE on interleaved pairs
@@ -276,7 +279,7 @@ DL_API int dl_gate_bwd(const void* dout, const void* t, const void* gate, int64_
 DL_API int dl_qk_norm_rope_fwd(const void* qkv, const float* scale_q, const float* scale_k, const float* cos,
                                const float* sin, void* q, void* k, void* v, float* rrms, int64_t B, int64_t N,
                                int64_t H, int64_t dh, int64_t rot, float eps, dl_stream_t stream);
-/* dscale f32 [2, D] is atomically accumulated (caller zeroes once per step). */
+/* dscale f32 [2, D] is atomically accumulated (caller zeroes once per step).  D = H * dh <= 4096 (up to 64 heads of 64). */
 DL_API int dl_qk_norm_rope_bwd(const void* dq, const void* dk, const void* dv, const void* qkv,
                                const float* scale_q, const float* scale_k, const float* cos, const float* sin,
                                const float* rrms, void* dqkv, float* dscale, int64_t B, int64_t N, int64_t H,

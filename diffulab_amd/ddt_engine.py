@@ -9,14 +9,13 @@ gradients as bf16 rows straight into the gradient matrix of that GEMM (dl_ln_mod
 
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 
 import torch
 from torch import Tensor
 
 from . import ops, tuning
-from .engine import DiTDims, _must, _rup, rope_grid_tables
+from .engine import ArenaLayout, DiTDims, SideWork, _must, _rup, rope_grid_tables
 from .sprint_engine import SprintEngine
 
 N_PART = 32  # partial slabs of the affine LayerNorm gradients of a per-token LayerNorm backward
@@ -33,21 +32,13 @@ class DDTDims(DiTDims):
         self.depth = self.encoder_depth + self.decoder_depth
 
 
-class DDTLayout:
-    def __init__(self, d: DDTDims) -> None:
-        D, p = d.inner_dim, d.patch_size
+class DDTLayout(ArenaLayout):
+    def _place(self, d: DDTDims) -> None:
+        D, p, add = d.inner_dim, d.patch_size, self.add
         E = D
-        self.entries: dict[str, tuple[int, tuple[int, ...]]] = {}
-        self.size = 0
         enc = [f"layers.{i}." for i in range(d.encoder_depth)]
         dec = [f"decoder_layers.{i}." for i in range(d.decoder_depth)]
         self.prefixes = enc + dec
-
-        def add(name: str, shape: tuple[int, ...], align: int = 64) -> None:
-            self.size = _rup(self.size, align)
-            self.entries[name] = (self.size, shape)
-            self.size += math.prod(shape)
-
         for suffix, shp in (("weight", lambda r: (r, E)), ("bias", lambda r: (r,))):
             for i, pre in enumerate(enc):  # per-sample adaLN of the encoder blocks: one [ne*6D, E] matrix
                 add(pre + "modulation.lin." + suffix, shp(6 * D), align=1 if i else 64)
@@ -70,21 +61,7 @@ class DDTLayout:
         add("last_layer.linear.bias", (p * p * d.output_channels,))
         self.block_first = [pre + "norm_1.weight" for pre in self.prefixes]
         for pre in self.prefixes:
-            add(pre + "norm_1.weight", (D,))
-            add(pre + "norm_1.bias", (D,), align=1)
-            add(pre + "norm_2.weight", (D,))
-            add(pre + "norm_2.bias", (D,), align=1)
-            add(pre + "attention.qk_norm.query_norm.scale", (D,))
-            add(pre + "attention.qk_norm.key_norm.scale", (D,), align=1)
-            add(pre + "attention.qkv.weight", (3 * D, D))
-            add(pre + "attention.proj_out.weight", (D, D))
-            add(pre + "mlp_input.0.weight", (2 * d.mlp_ratio * D, D))
-            add(pre + "mlp_input.2.weight", (D, d.mlp_ratio * D))
-        self.size = _rup(self.size, 64)
-
-    def view(self, flat: Tensor, name: str) -> Tensor:
-        off, shape = self.entries[name]
-        return flat[off : off + math.prod(shape)].view(shape)
+            self.add_dit_block(pre, D, d.mlp_ratio * D)
 
 
 class PerTokenDecoder:
@@ -150,7 +127,7 @@ class PerTokenDecoder:
         ops.unpatchify(w["otok"], w["pred"], d.patch_size)
         return w["pred"]
 
-    def _decoder_bwd(self, dpred: Tensor, first: int, nd: int, cos: Tensor, sin: Tensor, s: dict, wgrad, fold, side) -> Tensor:
+    def _decoder_bwd(self, dpred: Tensor, first: int, nd: int, cos: Tensor, sin: Tensor, s: dict, sw: SideWork) -> Tensor:
         """backward of _decoder_fwd.  s: chain scratch for N tokens (dxa, dxb, dxm, da, dh, dq, dk, dv); returns the gradient of
         ws["enc_out"] (ws["denc"]); ws["dtemb"] receives the decoder's gradient of the time embedding"""
         d, w, sh = self.d, self.ws, self.sh
@@ -160,17 +137,7 @@ class PerTokenDecoder:
         ne, L = first, first + nd
         tm, dtm = w["tmod"], w["dtmod"]
         inplace_qk = ops.qk_inplace_ok(w, B, N)
-        Fo8 = _rup(Fo, 8)
-        ops.patchify(dpred, w["dO"], d.patch_size, ops.PATCH_PPC)
-        gl = self.G("last_layer.linear.weight")
-        if Fo == Fo8:
-            ops.gemm_tn(w["dO"], w["xf"], gl, M=Fo, N=D)
-        else:
-            w["scr_last"].zero_()
-            ops.gemm_tn(w["dO"], w["xf"], w["scr_last"], M=Fo8, N=D)
-            ops.reduce_rows_f32(w["scr_last"], gl, 1, Fo * D)
-        ops.colsum(w["dO"], self.G("last_layer.linear.bias"), M, Fo)
-        ops.gemm_nt(w["dO"], sh["last_layer.linear.weight|t"], s["dxm"], M=M, N=D, K=self._ko)
+        self._head_bwd(dpred, s["dxm"])
         mo = nd * 6 * D
         ml = (nd - 1) * 6 * D
         al = w["blk"][L - 1]
@@ -183,17 +150,17 @@ class PerTokenDecoder:
             bi = ne + j
             a, pre, mo = w["blk"][bi], self.prefixes[bi], j * 6 * D
             g = a["wg"]
-            wgrad(g["dt2"], a["h"], pre + "mlp_input.2.weight")
+            sw.wgrad(g["dt2"], a["h"], pre + "mlp_input.2.weight")
             ops.mlp_swiglu_bwd(g["dt2"], sh[pre + "mlp_input.2.weight|t"], a["xm2"], sh[pre + "mlp_input.0.weight|g"], a["u"], s["dh"], g["du"])
-            wgrad(g["du"], a["xm2"], pre + "mlp_input.0.weight")
+            sw.wgrad(g["du"], a["xm2"], pre + "mlp_input.0.weight")
             ops.gemm_nt(g["du"], sh[pre + "mlp_input.0.weight|t"], s["dxm"])
             ops.ln_modulate_bwd_tok(s["dxm"], a["x1"], self.P(pre + "norm_2.weight"), self.P(pre + "norm_2.bias"),
                                     tm[:, mo + 3 * D : mo + 4 * D], a["mean2"], a["rstd2"], dx, dx_alt, dtm[:, mo + 3 * D : mo + 4 * D],
                                     dtm[:, mo + 4 * D : mo + 5 * D], a["dwbp"][1], gate_t=a["t1"], gate=tm[:, mo + 2 * D : mo + 3 * D],
                                     dt=g["dt1"], dgate=dtm[:, mo + 2 * D : mo + 3 * D])
-            fold(a["dwbp"][1], pre + "norm_2.weight", N_PART)
+            sw.fold(a["dwbp"][1], pre + "norm_2.weight", N_PART)
             dx, dx_alt = dx_alt, dx
-            wgrad(g["dt1"], a["a"], pre + "attention.proj_out.weight")
+            sw.wgrad(g["dt1"], a["a"], pre + "attention.proj_out.weight")
             ops.gemm_nt(g["dt1"], sh[pre + "attention.proj_out.weight|t"], s["da"])
             if inplace_qk:  # dQ, dK, dV token-major into dqkv; the QK-norm backward transforms the q / k thirds in place
                 ops.attn_bwd_tok(a["q"], a["k"], a["qkv"], a["a"], s["da"], a["lse"], g["dqkv"], B, Hh, N, 64, 64**-0.5)
@@ -215,7 +182,7 @@ class PerTokenDecoder:
                                      self.P(pre + "attention.qk_norm.query_norm.scale"),
                                      self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], g["dqkv"],
                                      self.G(pre + "attention.qk_norm.query_norm.scale"), B, N, Hh, 64, rot)
-            wgrad(g["dqkv"], a["xm1"], pre + "attention.qkv.weight")
+            sw.wgrad(g["dqkv"], a["xm1"], pre + "attention.qkv.weight")
             ops.gemm_nt(g["dqkv"], sh[pre + "attention.qkv.weight|t"], s["dxm"])
             nxt = {}
             if j > 0:
@@ -225,11 +192,9 @@ class PerTokenDecoder:
             ops.ln_modulate_bwd_tok(s["dxm"], a["xin"], self.P(pre + "norm_1.weight"), self.P(pre + "norm_1.bias"), tm[:, mo : mo + D],
                                     a["mean1"], a["rstd1"], dx, dx_alt, dtm[:, mo : mo + D], dtm[:, mo + D : mo + 2 * D], a["dwbp"][0],
                                     **nxt)
-            fold(a["dwbp"][0], pre + "norm_1.weight", N_PART)
+            sw.fold(a["dwbp"][0], pre + "norm_1.weight", N_PART)
             dx, dx_alt = dx_alt, dx
-            getattr(wgrad, "flush", lambda: None)()
-            if self.reducer is not None:
-                self.reducer.ready(*self.layer_ranges[bi], extra_events=(side.record_event(),))
+            self._end_block(sw, bi)
         # decoder patch embedding
         Fi = d.input_channels * d.patch_size**2
         gc = self.G("conv_proj_decoder.weight").view(D, Fi)
@@ -273,13 +238,9 @@ class DDTEngine(SprintEngine, PerTokenDecoder):
 
     # ------------------------------------------------------------------ workspace
     def _alloc(self, B: int, H: int, W: int, train: bool, k: int | None = None) -> None:  # type: ignore[override]
-        d, dev = self.d, self.dev
+        d, z = self.d, self._z
         key = (B, H, W, train)
-        if key == self._ws_key:
-            return
-        if key in self._ws_cache:
-            self.ws, self.geo = self._ws_cache[key]
-            self._ws_key = key
+        if self._cached(key):
             return
         D, E, p, L = d.inner_dim, d.embedding_dim, d.patch_size, d.depth
         gh, gw = H // p, W // p
@@ -287,29 +248,16 @@ class DDTEngine(SprintEngine, PerTokenDecoder):
         if N % 64 or (N > 256 and (N % 256 or N > ops.ATTN_MAX_TOKENS)):
             raise NotImplementedError(f"DDT HIP path: token grid {gh}x{gw} must give a multiple of 64 tokens up to 256, or of 256 up "
                                       f"to {ops.ATTN_MAX_TOKENS}")
-        M, Bp, Fo, F = B * N, _rup(B, 64), p * p * d.output_channels, d.mlp_ratio * D
+        M, Bp, F = B * N, _rup(B, 64), d.mlp_ratio * D
         ops.check_row_extent(M, max(2 * F, 6 * D, self.layout.tmod_rows), "DDT HIP path")
-        bf, f32 = torch.bfloat16, torch.float32
+        f32 = torch.float32
         R = self.layout.tmod_rows
-
-        def z(*shape, dtype=bf):
-            with torch.inference_mode(False):
-                return torch.zeros(*shape, device=dev, dtype=dtype)
-
-        def zr(rows, *rest, dtype=bf):  # row buffer: zero rows pad it to a multiple of 64 for the weight-gradient GEMMs
-            return z(_rup(rows, 64), *rest, dtype=dtype)[:rows]
-
-        w: dict[str, object] = {"tokP": z(M, self._ki), "temb": z(Bp, d.frequency_embedding), "pre1": z(Bp, E), "h1": z(Bp, E),
-                                "e": z(Bp, E, dtype=f32), "emb": z(Bp, E, dtype=f32), "se": z(Bp, E),
-                                "mod": z(Bp, self.layout.mod_rows)}
+        w: dict[str, object] = {}
+        self._cond_buffers(w, B, H, W, train, train and self._grouped_widths())
         blk = []
         for _ in range(L):
-            a = {"x0": z(M, D), "mean1": z(M, dtype=f32), "rstd1": z(M, dtype=f32), "xm1": z(M, D), "qkv": z(M, 3 * D),
-                 "q": z(B, d.num_heads, N, 64), "k": z(B, d.num_heads, N, 64), "v": z(B, d.num_heads, N, 64),
-                 "rrms": z(M, 2, dtype=f32), "a": z(M, D), "lse": z(B, d.num_heads, N, dtype=f32), "t1": z(M, D), "x1": z(M, D),
-                 "mean2": z(M, dtype=f32), "rstd2": z(M, dtype=f32), "xm2": z(M, D), "u": ops.mlp_u_buffer(z, M, D, F, train), "h": z(M, F), "t2": z(M, D)}
+            a = self._dit_block_buffers(B, N, train)
             if train:
-                a["wg"] = {"dt2": z(M, D), "du": z(M, 2 * F), "dt1": z(M, D), "dqkv": z(M, 3 * D)}
                 a["dwb"] = z(2, B, 2, D, dtype=f32)        # encoder blocks: per-sample partials
                 a["dwbp"] = z(2, N_PART, 2, D, dtype=f32)  # decoder blocks: slab partials of the per-token LayerNorm backward
             blk.append(a)
@@ -318,37 +266,17 @@ class DDTEngine(SprintEngine, PerTokenDecoder):
         w["xdec_in"], w["enc_out"], w["sz"] = z(M, D), z(M, D), z(M, D)
         w["tmod"] = z(M, R)
         w["xl"] = z(M, D)
-        w["meanf"], w["rstdf"], w["xf"] = z(M, dtype=f32), z(M, dtype=f32), z(M, D)
-        w["otok"] = z(M, _rup(Fo, 8), dtype=f32)
-        w["pred"] = z(B, d.output_channels, H, W, dtype=f32)
         if train:
-            w["dO"] = z(M, self._ko)
-            w[f"s{N}"] = {"dxa": z(M, D), "dxb": z(M, D), "dxm": z(M, D), "da": z(M, D), "dh": z(M, F),
-                          "dq": z(B, d.num_heads, N, 64), "dk": z(B, d.num_heads, N, 64), "dv": z(B, d.num_heads, N, 64)}
+            w[f"s{N}"] = self._dit_chain_buffers(B, N)
             w["dtmod"] = z(M, R)
             if ops.wgrad_tile_ok(R, D) and M % 32 == 0 and M >= 2048:  # two token ranges of the stacked per-token adaLN weight gradient
                 w["tmod_slab"] = torch.empty(2 * R * D, device=self.dev, dtype=torch.float32)
             w["dsz"], w["denc"] = z(M, D), z(M, D)
             w["dtemb"] = z(Bp, E, dtype=f32)
-            w["dmod"] = z(Bp, self.layout.mod_rows)
-            w["dmod32"] = z(Bp, self.layout.mod_rows, dtype=f32)
-            w["dse"], w["demb"], w["demb16"] = z(Bp, E, dtype=f32), z(Bp, E, dtype=f32), z(Bp, E)
-            w["dh1"], w["dpre1"] = z(Bp, E, dtype=f32), z(Bp, E)
-            w["scr_last"], w["scr_conv"] = z(_rup(Fo, 8), D, dtype=f32), z(D, self._ki, dtype=f32)
-            # scratch of the bit-reproducible (and faster) small GEMMs / column sums of the conditioning backward (engine._cond_bwd)
-            w["det_scr"] = torch.empty(max(2 * self.layout.mod_rows * d.embedding_dim, 1 << 22), device=self.dev, dtype=f32)
-            if ops.WgradGroups.widths_ok(D, F) and tuning.on("DL_WGRAD_GROUP"):  # grouped weight gradients (ops.WgradGroups)
-                w["tn_slab"] = torch.empty(ops.WgradGroups.slab_floats(D, F), device=self.dev, dtype=f32)
             if D <= 512 and tuning.on("DL_QK_INPLACE"):  # scale-gradient partials of the in-place QK-norm backward (ops.qk_inplace_ok)
                 w["qk_part"] = torch.empty(1024 * 2 * D, device=self.dev, dtype=f32)
-        self.ws, self._ws_key = w, key
-        self.geo = (B, H, W, gh, gw, N, M, Bp, Fo)
-        if len(self._ws_cache) >= 8:
-            self._ws_cache.pop(next(iter(self._ws_cache)))
-        self._ws_cache[key] = (w, self.geo)
-        if (gh, gw) not in self._rope:
-            c, s = rope_grid_tables(gh, gw, d.rope_axes_dim, d.rope_base)
-            self._rope[(gh, gw)] = (c.to(dev), s.to(dev))
+        self._publish(w, key, (B, H, W, gh, gw, N, M, Bp, p * p * d.output_channels), (gh, gw),
+                      lambda: rope_grid_tables(gh, gw, d.rope_axes_dim, d.rope_base))
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: Tensor, t: Tensor, y_eff: Tensor | None, train: bool = True, refresh: bool = True) -> Tensor:  # type: ignore[override]
@@ -388,32 +316,10 @@ class DDTEngine(SprintEngine, PerTokenDecoder):
         dfe = {kb: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb, g in (dfeats or {}).items()}
         cos, sin = self._rope[(gh, gw)]
         w["dmod32"][:B].zero_()
-        main = torch.cuda.current_stream()
-        side = self._side_stream()
-        side.wait_stream(main)
-        side_wgs = tuning.integer("DL_SIDE_WGS", 128)
-
-        def on_side(fn) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                fn()
-
-        wgrad = ops.grouped_wgrad_fn(self.G, w.get("tn_slab"), on_side, side_wgs)  # (one atomics-free launch per block where the tile divides)
-
-        def fold(partial: Tensor, gname: str, groups: int) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                ops.reduce_rows_f32(partial, self.G(gname), groups, 2 * D, clear=True)
-
-        denc = self._decoder_bwd(dpred, ne, L - ne, cos, sin, w[f"s{N}"], wgrad, fold, side)
-
-        def fold_norm(partial: Tensor, gname: str) -> None:
-            fold(partial, gname, B)
-
-        dx0 = self._stage_bwd(range(0, ne), denc, N, None, dfe, wgrad, fold_norm, side)
-        main.wait_stream(side)
+        sw = SideWork(self)
+        denc = self._decoder_bwd(dpred, ne, L - ne, cos, sin, w[f"s{N}"], sw)
+        dx0 = self._stage_bwd(range(0, ne), denc, N, None, dfe, sw)
+        sw.join()
         self._cond_bwd(dx0, extra_demb=w["dtemb"])
 
 
@@ -437,22 +343,14 @@ class DDTJointDims(JointDims):
                 + [(f"decoder_layers.{i}.", "D") for i in range(self.decoder_depth)])
 
 
-class DDTJointLayout:
-    def __init__(self, d: DDTJointDims) -> None:
-        D, p = d.inner_dim, d.patch_size
+class DDTJointLayout(ArenaLayout):
+    def _place(self, d: DDTJointDims) -> None:
+        D, p, add = d.inner_dim, d.patch_size, self.add
         E, F = D, d.mlp_ratio * D
-        self.entries: dict[str, tuple[int, tuple[int, ...]]] = {}
-        self.size = 0
         kinds = d.kinds()
         self.prefixes = [pre for pre, _ in kinds]
         enc = [pre for pre, k in kinds if k == "J"]
         dec = [pre for pre, k in kinds if k == "D"]
-
-        def add(name: str, shape: tuple[int, ...], align: int = 64) -> None:
-            self.size = _rup(self.size, align)
-            self.entries[name] = (self.size, shape)
-            self.size += math.prod(shape)
-
         for suffix, shp in (("weight", lambda r: (r, E)), ("bias", lambda r: (r,))):
             first = True
             for pre in enc:  # per-sample adaLN of the joint encoder blocks: [input 6D | context 6D] each
@@ -480,33 +378,10 @@ class DDTJointLayout:
         for pre, kind in kinds:
             if kind == "J":
                 self.block_first.append(pre + "input_norm_1.weight")
-                for st in STREAMS:
-                    for n in (1, 2):
-                        add(pre + f"{st}_norm_{n}.weight", (D,))
-                        add(pre + f"{st}_norm_{n}.bias", (D,), align=1)
-                    add(pre + f"attention.qk_norm_{st}.query_norm.scale", (D,))
-                    add(pre + f"attention.qk_norm_{st}.key_norm.scale", (D,), align=1)
-                    add(pre + f"attention.qkv_{st}.weight", (3 * D, D))
-                    add(pre + f"attention.{st}_proj_out.weight", (D, D))
-                    add(pre + f"mlp_{st}.0.weight", (2 * F, D))
-                    add(pre + f"mlp_{st}.2.weight", (D, F))
+                self.add_joint_block(pre, D, F)
             else:
                 self.block_first.append(pre + "norm_1.weight")
-                add(pre + "norm_1.weight", (D,))
-                add(pre + "norm_1.bias", (D,), align=1)
-                add(pre + "norm_2.weight", (D,))
-                add(pre + "norm_2.bias", (D,), align=1)
-                add(pre + "attention.qk_norm.query_norm.scale", (D,))
-                add(pre + "attention.qk_norm.key_norm.scale", (D,), align=1)
-                add(pre + "attention.qkv.weight", (3 * D, D))
-                add(pre + "attention.proj_out.weight", (D, D))
-                add(pre + "mlp_input.0.weight", (2 * F, D))
-                add(pre + "mlp_input.2.weight", (D, F))
-        self.size = _rup(self.size, 64)
-
-    def view(self, flat: Tensor, name: str) -> Tensor:
-        off, shape = self.entries[name]
-        return flat[off : off + math.prod(shape)].view(shape)
+                self.add_dit_block(pre, D, F)
 
 
 class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
@@ -539,13 +414,9 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
         return super()._src(name, shape)
 
     def _alloc(self, B: int, H: int, W: int, train: bool, Lc: int = 0, k: int = 0) -> None:  # type: ignore[override]
-        d, dev = self.d, self.dev
+        d, z, zr = self.d, self._z, self._zr
         key = (B, H, W, train, Lc)
-        if key == self._ws_key:
-            return
-        if key in self._ws_cache:
-            self.ws, self.geo = self._ws_cache[key]
-            self._ws_key = key
+        if self._cached(key):
             return
         D, E, p = d.inner_dim, d.embedding_dim, d.patch_size
         gh, gw = H // p, W // p
@@ -557,21 +428,12 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
                                       f"multiple of 64 (got {B} * {N})")
         pad = ops.attn_needs_padding(N)  # decoder attention on rows padded to a multiple of 256 with masked pad keys (_decoder_fwd)
         Nd = _rup(N, 256) if pad else N
-        M, Bp, Fo, F = B * N, _rup(B, 64), p * p * d.output_channels, d.mlp_ratio * D
+        M, Bp, F = B * N, _rup(B, 64), d.mlp_ratio * D
         ops.check_row_extent(B * Tpf, max(2 * F, 6 * D, self.layout.tmod_rows), "joint DDT HIP path")
-        bf, f32 = torch.bfloat16, torch.float32
+        f32 = torch.float32
         Hh, R = d.num_heads, self.layout.tmod_rows
-
-        def z(*shape, dtype=bf):
-            with torch.inference_mode(False):
-                return torch.zeros(*shape, device=dev, dtype=dtype)
-
-        def zr(rows, *rest, dtype=bf):  # row buffer: zero rows pad it to a multiple of 64 for the weight-gradient GEMMs
-            return z(_rup(rows, 64), *rest, dtype=dtype)[:rows]
-
-        w: dict[str, object] = {"tokP": z(M, self._ki), "temb": z(Bp, d.frequency_embedding), "pre1": z(Bp, E), "h1": z(Bp, E),
-                                "e": z(Bp, E, dtype=f32), "emb": z(Bp, E, dtype=f32), "se": z(Bp, E),
-                                "mod": z(Bp, self.layout.mod_rows)}
+        w: dict[str, object] = {}
+        self._cond_buffers(w, B, H, W, train, train and self._grouped_widths())
         w["ctxP"] = zr(B * Lc, _rup(d.context_dim, 64))
         w["x"] = [z(M, D)]
         w["c0"] = zr(B * Lc, D)
@@ -580,26 +442,14 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
         blk = []
         for _, kind in self.kinds:
             if kind == "J":
-                per: dict[str, object] = {"ao": z(B * Tpf, D), "lse": z(B, Hh, Tpf, dtype=f32), "q": z(B, Hh, Tpf, 64),
-                                          "k": z(B, Hh, Tpf, 64), "v": z(B, Hh, Tpf, 64)}
+                per = self._joint_attn_buffers(B, Tpf)
                 for st, nt in (("input", N), ("context", Lc)):
-                    mt = B * nt
-                    a = {"x0": zr(mt, D), "mean1": zr(mt, dtype=f32), "rstd1": zr(mt, dtype=f32), "xm1": zr(mt, D), "qkv": zr(mt, 3 * D),
-                         "rrms": zr(mt, 2, dtype=f32), "a": zr(mt, D), "t1": zr(mt, D), "x1": zr(mt, D), "mean2": zr(mt, dtype=f32),
-                         "rstd2": zr(mt, dtype=f32), "xm2": zr(mt, D), "u": ops.mlp_u_buffer(zr, mt, D, F, train), "h": zr(mt, F), "t2": zr(mt, D)}
-                    if train:
-                        a["wg"] = {"dt2": zr(mt, D), "du": zr(mt, 2 * F), "dt1": zr(mt, D), "dqkv": zr(mt, 3 * D)}
-                        a["dwb"] = z(2, B, 2, D, dtype=f32)
-                    per[st] = a
+                    per[st] = self._joint_stream_buffers(B, nt, train)
             else:
-                per = {"x0": z(M, D), "mean1": z(M, dtype=f32), "rstd1": z(M, dtype=f32), "xm1": z(M, D), "qkv": z(M, 3 * D),
-                       "q": z(B, Hh, Nd, 64), "k": z(B, Hh, Nd, 64), "v": z(B, Hh, Nd, 64), "rrms": z(M, 2, dtype=f32), "a": z(M, D),
-                       "lse": z(B, Hh, Nd, dtype=f32), "t1": z(M, D), "x1": z(M, D), "mean2": z(M, dtype=f32), "rstd2": z(M, dtype=f32),
-                       "xm2": z(M, D), "u": ops.mlp_u_buffer(z, M, D, F, train), "h": z(M, F), "t2": z(M, D)}
+                per = self._dit_block_buffers(B, N, train, nq=Nd)
                 if pad:
                     per["ao"] = z(B * Nd, D)
                 if train:
-                    per["wg"] = {"dt2": z(M, D), "du": z(M, 2 * F), "dt1": z(M, D), "dqkv": z(M, 3 * D)}
                     per["dwbp"] = z(2, N_PART, 2, D, dtype=f32)
             blk.append(per)
         if pad:
@@ -609,11 +459,7 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
         w["xdec_in"], w["enc_out"], w["sz"] = z(M, D), z(M, D), z(M, D)
         w["tmod"] = z(M, R)
         w["xl"] = z(M, D)
-        w["meanf"], w["rstdf"], w["xf"] = z(M, dtype=f32), z(M, dtype=f32), z(M, D)
-        w["otok"] = z(M, _rup(Fo, 8), dtype=f32)
-        w["pred"] = z(B, d.output_channels, H, W, dtype=f32)
         if train:
-            w["dO"] = z(M, self._ko)
             w[f"s_x{N}"] = {"dxa": z(M, D), "dxb": z(M, D), "dxm": z(M, D), "dxm2": z(M, D), "da": z(M, D), "dh": z(M, F),
                             "dq": z(B, Hh, Nd, 64), "dk": z(B, Hh, Nd, 64), "dv": z(B, Hh, Nd, 64)}
             if pad:
@@ -626,25 +472,10 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
                 w["tmod_slab"] = torch.empty(2 * R * D, device=self.dev, dtype=torch.float32)
             w["dsz"], w["denc"] = z(M, D), z(M, D)
             w["dtemb"] = z(Bp, E, dtype=f32)
-            w["dmod"] = z(Bp, self.layout.mod_rows)
-            w["dmod32"] = z(Bp, self.layout.mod_rows, dtype=f32)
-            w["dse"], w["demb"], w["demb16"] = z(Bp, E, dtype=f32), z(Bp, E, dtype=f32), z(Bp, E)
-            w["dh1"], w["dpre1"] = z(Bp, E, dtype=f32), z(Bp, E)
-            w["scr_last"], w["scr_conv"] = z(_rup(Fo, 8), D, dtype=f32), z(D, self._ki, dtype=f32)
-            # scratch of the bit-reproducible (and faster) small GEMMs / column sums of the conditioning backward (engine._cond_bwd)
-            w["det_scr"] = torch.empty(max(2 * self.layout.mod_rows * d.embedding_dim, 1 << 22), device=self.dev, dtype=f32)
-            if ops.WgradGroups.widths_ok(D, F) and tuning.on("DL_WGRAD_GROUP"):  # grouped weight gradients (ops.WgradGroups)
-                w["tn_slab"] = torch.empty(ops.WgradGroups.slab_floats(D, F), device=self.dev, dtype=f32)
             if D <= 512 and tuning.on("DL_QK_INPLACE") and not pad:  # scale-gradient partials of the in-place QK-norm backward (ops.qk_inplace_ok)
                 w["qk_part"] = torch.empty(1024 * 2 * D, device=self.dev, dtype=f32)
-        self.ws, self._ws_key = w, key
-        self.geo = (B, H, W, gh, gw, N, M, Bp, Fo)
-        if len(self._ws_cache) >= 8:
-            self._ws_cache.pop(next(iter(self._ws_cache)))
-        self._ws_cache[key] = (w, self.geo)
-        if (Lc, gh, gw) not in self._rope:
-            c, s = joint_rope_tables(Lc, gh, gw, d.rope_axes_dim, d.rope_base)
-            self._rope[(Lc, gh, gw)] = (c.to(dev), s.to(dev))
+        self._publish(w, key, (B, H, W, gh, gw, N, M, Bp, p * p * d.output_channels), (Lc, gh, gw),
+                      lambda: joint_rope_tables(Lc, gh, gw, d.rope_axes_dim, d.rope_base))
 
     def forward(self, x: Tensor, t: Tensor, y_eff: Tensor | None = None, train: bool = True, refresh: bool = True) -> Tensor:
         d = self.d
@@ -688,28 +519,9 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
         dfe = {kb_: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb_, g in (dfeats or {}).items()}
         cos, sin = self._tabs
         w["dmod32"][:B].zero_()
-        main = torch.cuda.current_stream()
-        side = self._side_stream()
-        side.wait_stream(main)
-        side_wgs = tuning.integer("DL_SIDE_WGS", 128)
-
-        def on_side(fn) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                fn()
-
-        wgrad = ops.grouped_wgrad_fn(self.G, w.get("tn_slab"), on_side, side_wgs)  # (one atomics-free launch per block where the tile divides)
-
-        def fold(partial: Tensor, gname: str, groups: int) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                ops.reduce_rows_f32(partial, self.G(gname), groups, 2 * D, clear=True)
-
-        denc = self._decoder_bwd(dpred, ne, d.decoder_depth, cos[Lc:], sin[Lc:], w[f"s_x{N}"], wgrad, fold, side)
-        dx0, dc0 = self._jstage_bwd(range(0, ne), denc, None, N, None, w["kb_f"], "f", dfe,
-                                    (wgrad, lambda partial, gname: fold(partial, gname, B), side))
-        main.wait_stream(side)
+        sw = SideWork(self)
+        denc = self._decoder_bwd(dpred, ne, d.decoder_depth, cos[Lc:], sin[Lc:], w[f"s_x{N}"], sw)
+        dx0, dc0 = self._jstage_bwd(range(0, ne), denc, None, N, None, w["kb_f"], "f", dfe, sw)
+        sw.join()
         ops.gemm_tn(dc0, w["ctxP"], self.G("context_embed.weight"), M=D, N=Cd)
         self._cond_bwd(dx0, extra_demb=w["dtemb"])

@@ -45,6 +45,7 @@ def _rup(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+STREAMS = ("input", "context")  # the two token streams of a joint (MMDiT) block: image, text
 ROW_MAX_DIM = 4096  # widest token row of the bf16 regime's row kernels (csrc/norm.hip: one wave per row up to 1024, one workgroup above)
 F32_MAX_DIM = 1024  # widest token row of the fp32 regime (csrc/f32.hip, one wave per row)
 
@@ -101,23 +102,64 @@ def rope_grid_tables(gh: int, gw: int, axes_dim: list[int], base: float) -> tupl
     return torch.cat(cs, 1).contiguous(), torch.cat(sn, 1).contiguous()
 
 
-class ParamLayout:
-    """name -> (offset, shape) inside the flat f32 arena.  Order: adaLN weights of all blocks + last layer
-    (one [L*6D+2D, E] matrix), their biases, then everything else; every entry starts on a 256-byte boundary."""
+class ArenaLayout:
+    """name -> (offset, shape) inside the flat f32 arena.  A subclass places its entries in `_place` with `add`; every entry starts
+    on a 256-byte boundary unless placed with align=1 (adjacent to the one before), and the arena ends on one."""
 
-    def __init__(self, d: DiTDims, prefixes: list[str] | None = None, extra: tuple[tuple[str, tuple[int, ...]], ...] = ()) -> None:
-        """prefixes: state_dict prefix of every adaLN-zero block in execution order (default ``layers.{i}.``);
-        extra: further non-block parameters (SPRINT's mask token and fuse linear), placed with the stem / head entries"""
-        D, E, p = d.inner_dim, d.embedding_dim, d.patch_size
+    def __init__(self, *args, **kwargs) -> None:
         self.entries: dict[str, tuple[int, tuple[int, ...]]] = {}
         self.size = 0
+        self._place(*args, **kwargs)
+        self.size = _rup(self.size, 64)
+
+    def _place(self, *args, **kwargs) -> None:
+        raise NotImplementedError
+
+    def add(self, name: str, shape: tuple[int, ...], align: int = 64) -> None:
+        self.size = _rup(self.size, align)
+        self.entries[name] = (self.size, shape)
+        self.size += math.prod(shape)
+
+    def add_dit_block(self, pre: str, D: int, F: int) -> None:
+        """the parameters of a DiTBlock except its adaLN linear"""
+        self.add(pre + "norm_1.weight", (D,))
+        self.add(pre + "norm_1.bias", (D,), align=1)  # [w; b] adjacent: one reduce writes both gradients
+        self.add(pre + "norm_2.weight", (D,))
+        self.add(pre + "norm_2.bias", (D,), align=1)
+        self.add(pre + "attention.qk_norm.query_norm.scale", (D,))
+        self.add(pre + "attention.qk_norm.key_norm.scale", (D,), align=1)
+        self.add(pre + "attention.qkv.weight", (3 * D, D))
+        self.add(pre + "attention.proj_out.weight", (D, D))
+        self.add(pre + "mlp_input.0.weight", (2 * F, D))
+        self.add(pre + "mlp_input.2.weight", (D, F))
+
+    def add_joint_block(self, pre: str, D: int, F: int) -> None:
+        """the parameters of an MMDiTBlock (both token streams) except its adaLN linears"""
+        for st in STREAMS:
+            for n in (1, 2):
+                self.add(pre + f"{st}_norm_{n}.weight", (D,))
+                self.add(pre + f"{st}_norm_{n}.bias", (D,), align=1)
+            self.add(pre + f"attention.qk_norm_{st}.query_norm.scale", (D,))
+            self.add(pre + f"attention.qk_norm_{st}.key_norm.scale", (D,), align=1)
+            self.add(pre + f"attention.qkv_{st}.weight", (3 * D, D))
+            self.add(pre + f"attention.{st}_proj_out.weight", (D, D))
+            self.add(pre + f"mlp_{st}.0.weight", (2 * F, D))
+            self.add(pre + f"mlp_{st}.2.weight", (D, F))
+
+    def view(self, flat: Tensor, name: str) -> Tensor:
+        off, shape = self.entries[name]
+        return flat[off : off + math.prod(shape)].view(shape)
+
+
+class ParamLayout(ArenaLayout):
+    """Order: adaLN weights of all blocks + last layer (one [L*6D+2D, E] matrix), their biases, then everything else."""
+
+    def _place(self, d: DiTDims, prefixes: list[str] | None = None, extra: tuple[tuple[str, tuple[int, ...]], ...] = ()) -> None:
+        """prefixes: state_dict prefix of every adaLN-zero block in execution order (default ``layers.{i}.``);
+        extra: further non-block parameters (SPRINT's mask token and fuse linear), placed with the stem / head entries"""
+        D, E, p, add = d.inner_dim, d.embedding_dim, d.patch_size, self.add
         self.prefixes = prefixes = list(prefixes) if prefixes is not None else [f"layers.{i}." for i in range(d.depth)]
         nb = len(prefixes)
-
-        def add(name: str, shape: tuple[int, ...], align: int = 64) -> None:
-            self.size = _rup(self.size, align)
-            self.entries[name] = (self.size, shape)
-            self.size += math.prod(shape)
 
         # -- contiguous adaLN matrix / bias (rows are multiples of 64*... so no padding is inserted between them)
         for i, pre in enumerate(prefixes):
@@ -141,21 +183,7 @@ class ParamLayout:
         for name, shape in extra:
             add(name, shape)
         for pre in prefixes:
-            add(pre + "norm_1.weight", (D,))
-            add(pre + "norm_1.bias", (D,), align=1)  # [w; b] adjacent: one reduce writes both gradients
-            add(pre + "norm_2.weight", (D,))
-            add(pre + "norm_2.bias", (D,), align=1)
-            add(pre + "attention.qk_norm.query_norm.scale", (D,))
-            add(pre + "attention.qk_norm.key_norm.scale", (D,), align=1)
-            add(pre + "attention.qkv.weight", (3 * D, D))
-            add(pre + "attention.proj_out.weight", (D, D))
-            add(pre + "mlp_input.0.weight", (2 * d.mlp_ratio * D, D))
-            add(pre + "mlp_input.2.weight", (D, d.mlp_ratio * D))
-        self.size = _rup(self.size, 64)
-
-    def view(self, flat: Tensor, name: str) -> Tensor:
-        off, shape = self.entries[name]
-        return flat[off : off + math.prod(shape)].view(shape)
+            self.add_dit_block(pre, D, d.mlp_ratio * D)
 
 
 class DiTEngine:
@@ -286,16 +314,120 @@ class DiTEngine:
         self.manual_version += 1
 
     # ------------------------------------------------------------------ workspace
-    def _alloc(self, B: int, H: int, W: int, train: bool) -> None:
-        key = (B, H, W, train)
+    def _z(self, *shape, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+        with torch.inference_mode(False):  # workspaces outlive an inference_mode() sampler loop
+            return torch.zeros(*shape, device=self.dev, dtype=dtype)
+
+    def _zr(self, rows: int, *rest, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+        """row buffer: zero rows pad it to a multiple of 64 for the weight-gradient GEMMs"""
+        return self._z(_rup(rows, 64), *rest, dtype=dtype)[:rows]
+
+    def _cached(self, key: tuple) -> bool:
+        """select the workspace of `key` if it exists (workspaces are kept per shape: captured hipGraphs have their addresses baked in)"""
         if key == self._ws_key:
-            return
-        if key in self._ws_cache:  # workspaces are kept per shape: captured hipGraphs have their addresses baked in
+            return True
+        if key in self._ws_cache:
             self.ws, self.geo = self._ws_cache[key]
             self._ws_key = key
+            return True
+        return False
+
+    def _publish(self, w: dict, key: tuple, geo: tuple, rope_key: tuple, rope_fn) -> None:
+        """make w the current workspace and cache it; rope_fn() -> the (cos, sin) tables of rope_key if they are not built yet"""
+        self.ws, self._ws_key, self.geo = w, key, geo
+        if len(self._ws_cache) >= 8:  # bound the cache: drop the oldest shape (its graphs are dropped by the module too)
+            self._ws_cache.pop(next(iter(self._ws_cache)))
+        self._ws_cache[key] = (w, geo)
+        if rope_key not in self._rope:
+            c, s = rope_fn()
+            self._rope[rope_key] = (c.to(self.dev), s.to(self.dev))
+
+    def _cond_buffers(self, w: dict, B: int, H: int, W: int, train: bool, grouped: bool) -> None:
+        """stem, conditioning path and head of a B x H x W batch.  grouped: the block weight gradients run as atomics-free grouped
+        launches (dl_gemm_tn_group) through the partial slabs of ws["tn_slab"]"""
+        d, z, f32 = self.d, self._z, torch.float32
+        D, E, p = d.inner_dim, d.embedding_dim, d.patch_size
+        M, Bp, Fo, R = B * (H // p) * (W // p), _rup(B, 64), p * p * d.output_channels, self.layout.mod_rows
+        w["tokP"] = z(M, self._ki)  # patchified input, K padded to 64
+        w["temb"], w["pre1"], w["h1"] = z(Bp, d.frequency_embedding), z(Bp, E), z(Bp, E)
+        w["e"], w["emb"], w["se"] = z(Bp, E, dtype=f32), z(Bp, E, dtype=f32), z(Bp, E)
+        w["mod"] = z(Bp, R)
+        w["meanf"], w["rstdf"], w["xf"] = z(M, dtype=f32), z(M, dtype=f32), z(M, D)
+        w["otok"] = z(M, _rup(Fo, 8), dtype=f32)
+        w["pred"] = z(B, d.output_channels, H, W, dtype=f32)
+        if not train:
             return
-        d, dev = self.d, self.dev
-        D, E, p, L = d.inner_dim, d.embedding_dim, d.patch_size, d.depth
+        w["dO"] = z(M, self._ko)
+        w["dmod"] = z(Bp, R)                  # bf16 operand of the modulation GEMMs' backward
+        w["dmod32"] = z(Bp, R, dtype=f32)     # f32 accumulator the block kernels add into
+        w["dse"], w["demb"], w["demb16"] = z(Bp, E, dtype=f32), z(Bp, E, dtype=f32), z(Bp, E)
+        w["dh1"], w["dpre1"] = z(Bp, E, dtype=f32), z(Bp, E)
+        w["scr_last"], w["scr_conv"] = z(_rup(Fo, 8), D, dtype=f32), z(D, self._ki, dtype=f32)
+        # scratch of the bit-reproducible small GEMMs / column sums of the head and the conditioning path (partial images per split,
+        # folded in a fixed order: ops.gemm_tn / gemm_nt / colsum with scratch=): two images of the stacked adaLN weight gradient is
+        # the largest user
+        w["det_scr"] = torch.empty(max(2 * R * E, 1 << 22), device=self.dev, dtype=f32)
+        # partial slabs of the grouped weight-gradient launch (the linears of a block in one atomics-free launch): 8 token ranges
+        # (fewer above D = 1024) x (4 + 3 mlp_ratio) D^2 floats; one set, the side stream runs the blocks one after the other
+        if grouped:
+            w["tn_slab"] = torch.empty(ops.WgradGroups.slab_floats(D, d.mlp_ratio * D), device=self.dev, dtype=f32)
+
+    def _grouped_widths(self) -> bool:
+        """the linears of a block are whole tiles of the grouped weight-gradient launch (ops.WgradGroups); DL_WGRAD_GROUP=0 is the
+        A/B switch back to one atomic launch per linear"""
+        return ops.WgradGroups.widths_ok(self.d.inner_dim, self.d.mlp_ratio * self.d.inner_dim) and tuning.on("DL_WGRAD_GROUP")
+
+    def _dit_block_buffers(self, B: int, nt: int, train: bool, nq: int | None = None) -> dict:
+        """what a DiT block of a staged engine (SPRINT, DDT) keeps of its forward over B * nt tokens; q / k / v / lse hold nq >= nt
+        rows per (sample, head) (padded attention).  Training adds the inputs of the weight-gradient GEMMs (wg)."""
+        d, z, f32 = self.d, self._z, torch.float32
+        D, Hh, F, mt = d.inner_dim, d.num_heads, d.mlp_ratio * d.inner_dim, B * nt
+        nq = nt if nq is None else nq
+        a = {"x0": z(mt, D), "mean1": z(mt, dtype=f32), "rstd1": z(mt, dtype=f32), "xm1": z(mt, D), "qkv": z(mt, 3 * D),
+             "q": z(B, Hh, nq, 64), "k": z(B, Hh, nq, 64), "v": z(B, Hh, nq, 64), "rrms": z(mt, 2, dtype=f32), "a": z(mt, D),
+             "lse": z(B, Hh, nq, dtype=f32), "t1": z(mt, D), "x1": z(mt, D), "mean2": z(mt, dtype=f32), "rstd2": z(mt, dtype=f32),
+             "xm2": z(mt, D), "u": ops.mlp_u_buffer(z, mt, D, F, train), "h": z(mt, F), "t2": z(mt, D)}
+        if train:
+            a["wg"] = {"dt2": z(mt, D), "du": z(mt, 2 * F), "dt1": z(mt, D), "dqkv": z(mt, 3 * D)}
+        return a
+
+    def _joint_stream_buffers(self, B: int, nt: int, train: bool) -> dict:
+        """what one token stream of a joint (MMDiT) block keeps of its forward over B * nt tokens (row buffers: a stream's token count
+        need not be a multiple of 64)"""
+        d, zr, f32 = self.d, self._zr, torch.float32
+        D, F, mt = d.inner_dim, d.mlp_ratio * d.inner_dim, B * nt
+        a = {"x0": zr(mt, D), "mean1": zr(mt, dtype=f32), "rstd1": zr(mt, dtype=f32), "xm1": zr(mt, D), "qkv": zr(mt, 3 * D),
+             "rrms": zr(mt, 2, dtype=f32), "a": zr(mt, D), "t1": zr(mt, D), "x1": zr(mt, D), "mean2": zr(mt, dtype=f32),
+             "rstd2": zr(mt, dtype=f32), "xm2": zr(mt, D), "u": ops.mlp_u_buffer(zr, mt, D, F, train), "h": zr(mt, F), "t2": zr(mt, D)}
+        if train:
+            a["wg"] = {"dt2": zr(mt, D), "du": zr(mt, 2 * F), "dt1": zr(mt, D), "dqkv": zr(mt, 3 * D)}
+            a["dwb"] = self._z(2, B, 2, D, dtype=f32)
+        return a
+
+    def _single_stream_buffers(self, B: int, T: int, train: bool) -> dict:
+        """what a single-stream (MMDiTSingleStreamBlock) block keeps of its forward over the B * T concatenated tokens"""
+        d, zr, f32 = self.d, self._zr, torch.float32
+        D, F, mt = d.inner_dim, d.mlp_ratio * d.inner_dim, B * T
+        a = {"x0": zr(mt, D), "mean": zr(mt, dtype=f32), "rstd": zr(mt, dtype=f32), "m": zr(mt, D), "qkv": zr(mt, 3 * D),
+             "rrms": zr(mt, 2, dtype=f32), "a": zr(mt, D), "ta": zr(mt, D), "u": ops.mlp_u_buffer(zr, mt, D, F, train), "h": zr(mt, F),
+             "t": zr(mt, D)}
+        if train:
+            a["wg"] = {"dt": zr(mt, D), "du": zr(mt, 2 * F), "dqkv": zr(mt, 3 * D)}
+            a["dwb"] = self._z(1, B, 2, D, dtype=f32)
+        return a
+
+    def _joint_attn_buffers(self, B: int, Tp: int) -> dict:
+        """q / k / v, output and log-sum-exp of an attention over Tp (padded) joint tokens per sample"""
+        z, Hh = self._z, self.d.num_heads
+        return {"ao": z(B * Tp, self.d.inner_dim), "lse": z(B, Hh, Tp, dtype=torch.float32), "q": z(B, Hh, Tp, 64),
+                "k": z(B, Hh, Tp, 64), "v": z(B, Hh, Tp, 64)}
+
+    def _alloc(self, B: int, H: int, W: int, train: bool) -> None:
+        key = (B, H, W, train)
+        if self._cached(key):
+            return
+        d, z = self.d, self._z
+        D, p, L = d.inner_dim, d.patch_size, d.depth
         gh, gw = H // p, W // p
         N = gh * gw
         M = B * N
@@ -313,21 +445,9 @@ class DiTEngine:
         Bp = _rup(B, 64)
         Fo = p * p * d.output_channels
         ops.check_row_extent(B * Nd, max(2 * d.mlp_ratio * D, 6 * D), "DiT bf16 path")
-        bf, f32 = torch.bfloat16, torch.float32
-
-        def z(*shape, dtype=bf):
-            with torch.inference_mode(False):  # workspaces outlive an inference_mode() sampler loop
-                return torch.zeros(*shape, device=dev, dtype=dtype)
-
+        f32 = torch.float32
         w: dict[str, object] = {}
-        w["tokP"] = z(M, self._ki)                      # patchified input, K padded to 64
-        w["temb"] = z(Bp, d.frequency_embedding)
-        w["pre1"] = z(Bp, E)
-        w["h1"] = z(Bp, E)
-        w["e"] = z(Bp, E, dtype=f32)
-        w["emb"] = z(Bp, E, dtype=f32)
-        w["se"] = z(Bp, E)
-        w["mod"] = z(Bp, self.layout.mod_rows)
+        self._cond_buffers(w, B, H, W, train, train and self._grouped_wgrad(M))
         nl = L if train else 1                    # inference reuses one block's buffers for every layer
         # MLP backward with recomputed pre-activations (csrc/mlp_bwd.hip): the training forward then stores h only and no
         # [M, 2F] pre-activation buffer exists (403 MB per block at B = 256); shapes without that kernel keep u
@@ -354,12 +474,7 @@ class DiTEngine:
             w["kb"][:, N:] = float("-inf")
         if self._qkn_on_load(M, N):
             w["ssq_all"] = z(L, M, 2, dtype=f32)
-        w["meanf"], w["rstdf"] = z(M, dtype=f32), z(M, dtype=f32)
-        w["xf"] = z(M, D)
-        w["otok"] = z(M, _rup(Fo, 8), dtype=f32)
-        w["pred"] = z(B, d.output_channels, H, W, dtype=f32)
         if train:
-            w["dO"] = z(M, self._ko)
             w["dxa"], w["dxb"] = z(M, D), z(M, D)
             w["dxm"], w["da"] = z(M, D), z(M, D)
             w["dh"] = z(M, d.mlp_ratio * D)
@@ -370,39 +485,15 @@ class DiTEngine:
             # backward works in place (its per-workgroup scale-gradient partials land in qk_part): no dq / dk buffers
             # (from 32768 token rows: at the CIFAR config's 8192 rows the in-place pair is 5 % of a 6.7 ms step SLOWER)
             if ops.v_in_place(N) and D <= 512 and M >= 32768 and type(self) is DiTEngine and tuning.on("DL_QK_INPLACE"):
-                w["qk_part"] = torch.empty(1024 * 2 * D, device=dev, dtype=f32)
+                w["qk_part"] = torch.empty(1024 * 2 * D, device=self.dev, dtype=f32)
                 w["dq"] = w["dk"] = None
             else:
                 w["dq"], w["dk"] = z(B, d.num_heads, Nd, 64), z(B, d.num_heads, Nd, 64)
             w["dv"] = None if ops.v_in_place(N) else z(B, d.num_heads, Nd, 64)
             if pad:
                 w["dao"] = z(B * Nd, D)
-            w["dmod"] = z(Bp, self.layout.mod_rows)                  # bf16 operand of the modulation GEMMs' backward
-            w["dmod32"] = z(Bp, self.layout.mod_rows, dtype=f32)     # f32 accumulator the block kernels add into
             w["dwb"] = z(2 * L, B, 2, D, dtype=f32)  # per-norm partials: folded on the side stream, cleared while read
-            w["dse"] = z(Bp, E, dtype=f32)
-            w["demb"] = z(Bp, E, dtype=f32)
-            w["demb16"] = z(Bp, E)
-            w["dh1"] = z(Bp, E, dtype=f32)
-            w["dpre1"] = z(Bp, E)
-            # partial slabs of the grouped weight-gradient launch (dl_gemm_tn_group: the four linears of a block in one atomics-free
-            # launch): 8 token ranges (fewer above D = 1024) x (4 + 3 mlp_ratio) D^2 floats; one set, the side stream runs the blocks one after the other
-            if self._grouped_wgrad(M):
-                w["tn_slab"] = torch.empty(ops.WgradGroups.slab_floats(D, d.mlp_ratio * D), device=dev, dtype=f32)
-            # scratch of the bit-reproducible small GEMMs / column sums of the head and the conditioning path (partial images per
-            # split, folded in a fixed order: ops.gemm_tn / gemm_nt / colsum with scratch=): two images of the stacked adaLN
-            # weight gradient is the largest user
-            w["det_scr"] = torch.empty(max(2 * self.layout.mod_rows * E, 1 << 22), device=dev, dtype=f32)
-            w["scr_last"] = z(_rup(Fo, 8), D, dtype=f32)
-            w["scr_conv"] = z(D, self._ki, dtype=f32)
-        self.ws, self._ws_key = w, key
-        self.geo = (B, H, W, gh, gw, N, M, Bp, Fo)
-        if len(self._ws_cache) >= 8:  # bound the cache: drop the oldest shape (its graphs are dropped by the module too)
-            self._ws_cache.pop(next(iter(self._ws_cache)))
-        self._ws_cache[key] = (w, self.geo)
-        if (gh, gw) not in self._rope:
-            c, s = rope_grid_tables(gh, gw, d.rope_axes_dim, d.rope_base)
-            self._rope[(gh, gw)] = (c.to(dev), s.to(dev))
+        self._publish(w, key, (B, H, W, gh, gw, N, M, Bp, Fo), (gh, gw), lambda: rope_grid_tables(gh, gw, d.rope_axes_dim, d.rope_base))
 
     def _stem_fwd(self, x: Tensor, t: Tensor, y_eff: Tensor | None, x0: Tensor | None = None, patch_gemm: bool = True) -> Tensor:
         """patch embedding into ``x0`` (default ws["x"][0]) and the conditioning path: time MLP (+ label row) -> SiLU -> the
@@ -713,22 +804,10 @@ class DiTEngine:
         rot = sum(d.rope_axes_dim)
         mod, dmod, xs = w["mod"], w["dmod32"], w["x"]  # dmod: f32 accumulator, cast to bf16 (w["dmod"]) after the loop
         dmod[:B].zero_()
-        Fo8 = _rup(Fo, 8)
 
         # head: last linear + final adaLN
-        ops.patchify(dpred, w["dO"], d.patch_size, ops.PATCH_PPC)
-        gl = self.G("last_layer.linear.weight")
-        det = w.get("det_scr")
-        if Fo == Fo8:
-            ops.gemm_tn(w["dO"], w["xf"], gl, M=Fo, N=D, scratch=det)
-        else:
-            w["scr_last"].zero_()
-            ops.gemm_tn(w["dO"], w["xf"], w["scr_last"], M=Fo8, N=D, scratch=det)
-            ops.reduce_rows_f32(w["scr_last"], gl, 1, Fo * D)
-        ops.colsum(w["dO"], self.G("last_layer.linear.bias"), M, Fo, scratch=det)
         fused = self._row_gemms(M, N)
-        if not fused:
-            ops.gemm_nt(w["dO"], sh["last_layer.linear.weight|t"], w["dxm"], M=M, N=D, K=self._ko)
+        self._head_bwd(dpred, None if fused else w["dxm"], scratch=w["det_scr"])
         mo = L * 6 * D
         dx, dx_alt = w["dxa"], w["dxb"]
         # every LayerNorm-modulate backward also runs the backward of the gated residual that follows it in the chain
@@ -927,6 +1006,31 @@ class DiTEngine:
         if join_last:
             main.wait_stream(side)
 
+    def _head_bwd(self, dpred: Tensor, dxm: Tensor | None, scratch: Tensor | None = None) -> None:
+        """backward of the last linear: dpred patchified into ws["dO"], its weight gradient (through an f32 slab padded to 8 rows
+        when the output features are ragged) and bias gradient, and (dxm not None) the data gradient into dxm.  scratch: the
+        bit-reproducible forms of the small GEMM / column sum (ops.gemm_tn)"""
+        d, w = self.d, self.ws
+        M, Fo, D = self.geo[6], self.geo[8], d.inner_dim
+        ops.patchify(dpred, w["dO"], d.patch_size, ops.PATCH_PPC)
+        gl = self.G("last_layer.linear.weight")
+        if Fo % 8 == 0:
+            ops.gemm_tn(w["dO"], w["xf"], gl, M=Fo, N=D, scratch=scratch)
+        else:
+            w["scr_last"].zero_()
+            ops.gemm_tn(w["dO"], w["xf"], w["scr_last"], M=_rup(Fo, 8), N=D, scratch=scratch)
+            ops.reduce_rows_f32(w["scr_last"], gl, 1, Fo * D)
+        ops.colsum(w["dO"], self.G("last_layer.linear.bias"), M, Fo, scratch=scratch)
+        if dxm is not None:
+            ops.gemm_nt(w["dO"], self.sh["last_layer.linear.weight|t"], dxm, M=M, N=D, K=self._ko)
+
+    def _end_block(self, sw: "SideWork", bi: int) -> None:
+        """end of block bi's backward in a staged engine: its pending weight gradients are issued and, data parallel, its gradient
+        range is handed to the reducer behind the side stream's work so far"""
+        sw.flush()
+        if self.reducer is not None:
+            self.reducer.ready(*self.layer_ranges[bi], extra_events=(sw.side.record_event(),))
+
     def _cond_bwd(self, dx: Tensor, extra_demb: Tensor | None = None) -> None:
         """backward of _stem_fwd: dx = gradient of the patch-embedded tokens; the modulation gradient was accumulated in
         ws["dmod32"] by the block kernels.  extra_demb: f32 [>= B, E] further gradient of the time embedding (DDT's decoder)"""
@@ -981,3 +1085,46 @@ class DiTEngine:
             else:
                 self.reducer.ready(0, self.layer_ranges[0][0])
             self.reducer.finish()
+
+
+class SideWork:
+    """the side-stream half of a staged engine's backward (SPRINT, MMDiT, DDT and their joint forms).  The weight gradients and the
+    LayerNorm-affine folds are off the dependency chain, so they run on a side stream, each launch behind an event recorded on the main
+    stream when it is issued.  The linears of a block (per token stream) are collected and issued as ONE atomics-free
+    dl_gemm_tn_group launch where the workspace has a grouped-launch slab (ops.WgradGroups), else as one atomic launch each.
+    Built where the backward begins to issue side work: the side stream waits for everything the main stream has issued so far."""
+
+    def __init__(self, eng: DiTEngine) -> None:
+        self.G, self.width = eng.G, 2 * eng.d.inner_dim
+        self.main = torch.cuda.current_stream()
+        self.side = eng._side_stream()
+        self.side.wait_stream(self.main)
+        self.side_wgs = tuning.integer("DL_SIDE_WGS", 128)  # workgroup cap of the side-stream launches (of 256 CUs)
+        slab = eng.ws.get("tn_slab")
+        self.groups = ops.WgradGroups(slab, self.run, max_wgs=self.side_wgs) if slab is not None else None
+
+    def run(self, fn) -> None:
+        """fn() on the side stream, behind everything the main stream has issued so far"""
+        ev = self.main.record_event()
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(ev)
+            fn()
+
+    def wgrad(self, dy: Tensor, x: Tensor, name: str) -> None:
+        """G(name) += dy^T x"""
+        if self.groups is not None:
+            self.groups.add(dy, x, self.G(name))
+        else:
+            self.run(lambda: ops.gemm_tn(dy, x, self.G(name), max_wgs=self.side_wgs))
+
+    def flush(self) -> None:
+        """issue the grouped weight gradients still pending (at every block end)"""
+        if self.groups is not None:
+            self.groups.flush()
+
+    def fold(self, partial: Tensor, name: str, groups: int) -> None:
+        """[groups, 2, D] partial sums of a LayerNorm's affine gradients -> its adjacent [w; b] gradient (partials cleared)"""
+        self.run(lambda: ops.reduce_rows_f32(partial, self.G(name), groups, self.width, clear=True))
+
+    def join(self) -> None:
+        self.main.wait_stream(self.side)

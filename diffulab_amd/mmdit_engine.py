@@ -11,16 +11,13 @@ shape; the context stream of the LAST block feeds nothing (mmdit.py:838-842) and
 
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 
 import torch
 from torch import Tensor
 
-from . import ops, tuning
-from .engine import ROW_MAX_DIM, DiTDims, DiTEngine, _rup
-
-STREAMS = ("input", "context")
+from . import ops
+from .engine import ROW_MAX_DIM, STREAMS, ArenaLayout, DiTDims, DiTEngine, SideWork, _rup
 
 
 @dataclass
@@ -64,21 +61,13 @@ def joint_rope_tables(n_ctx: int, gh: int, gw: int, axes_dim: list[int], base: f
     return torch.cat(cs, 1).contiguous(), torch.cat(sn, 1).contiguous()
 
 
-class JointLayout:
-    """name -> (offset, shape) in the flat f32 arena: the stacked adaLN matrix ([input 6D | context 6D] per block, then the last
-    layer's 2D rows) and its bias first, then stem / head, then the blocks"""
+class JointLayout(ArenaLayout):
+    """the stacked adaLN matrix ([input 6D | context 6D] per block, then the last layer's 2D rows) and its bias first, then stem /
+    head, then the blocks"""
 
-    def __init__(self, d: JointDims) -> None:
-        D, E, p = d.inner_dim, d.embedding_dim, d.patch_size
-        self.entries: dict[str, tuple[int, tuple[int, ...]]] = {}
-        self.size = 0
+    def _place(self, d: JointDims) -> None:
+        D, E, p, add = d.inner_dim, d.embedding_dim, d.patch_size, self.add
         self.prefixes = [f"layers.{i}." for i in range(d.depth)]
-
-        def add(name: str, shape: tuple[int, ...], align: int = 64) -> None:
-            self.size = _rup(self.size, align)
-            self.entries[name] = (self.size, shape)
-            self.size += math.prod(shape)
-
         first = True
         for pre in self.prefixes:
             for st in STREAMS:
@@ -104,21 +93,7 @@ class JointLayout:
         self.block_first = []
         for pre in self.prefixes:
             self.block_first.append(pre + "input_norm_1.weight")
-            for st in STREAMS:
-                for n in (1, 2):
-                    add(pre + f"{st}_norm_{n}.weight", (D,))
-                    add(pre + f"{st}_norm_{n}.bias", (D,), align=1)  # [w; b] adjacent: one reduce writes both gradients
-                add(pre + f"attention.qk_norm_{st}.query_norm.scale", (D,))
-                add(pre + f"attention.qk_norm_{st}.key_norm.scale", (D,), align=1)
-                add(pre + f"attention.qkv_{st}.weight", (3 * D, D))
-                add(pre + f"attention.{st}_proj_out.weight", (D, D))
-                add(pre + f"mlp_{st}.0.weight", (2 * d.mlp_ratio * D, D))
-                add(pre + f"mlp_{st}.2.weight", (D, d.mlp_ratio * D))
-        self.size = _rup(self.size, 64)
-
-    def view(self, flat: Tensor, name: str) -> Tensor:
-        off, shape = self.entries[name]
-        return flat[off : off + math.prod(shape)].view(shape)
+            self.add_joint_block(pre, D, d.mlp_ratio * D)
 
 
 class JointEngine(DiTEngine):
@@ -142,15 +117,11 @@ class JointEngine(DiTEngine):
 
     # ------------------------------------------------------------------ workspace
     def _alloc(self, B: int, H: int, W: int, train: bool, Lc: int = 0) -> None:  # type: ignore[override]
-        d, dev = self.d, self.dev
+        d, z, zr = self.d, self._z, self._zr
         key = (B, H, W, train, Lc)
-        if key == self._ws_key:
+        if self._cached(key):
             return
-        if key in self._ws_cache:
-            self.ws, self.geo = self._ws_cache[key]
-            self._ws_key = key
-            return
-        D, E, p, L = d.inner_dim, d.embedding_dim, d.patch_size, d.depth
+        D, p, L = d.inner_dim, d.patch_size, d.depth
         gh, gw = H // p, W // p
         N = gh * gw
         T = Lc + N
@@ -158,20 +129,11 @@ class JointEngine(DiTEngine):
         if Tp > ops.ATTN_MAX_TOKENS or (B * N) % 64 or Lc < 1:
             raise NotImplementedError(f"joint MMDiT HIP path: context + image tokens <= {ops.ATTN_MAX_TOKENS} (got {Lc} + {N}), image tokens a "
                                       "multiple of 64")
-        M, Bp, Fo, F = B * N, _rup(B, 64), p * p * d.output_channels, d.mlp_ratio * D
+        M, F = B * N, d.mlp_ratio * D
         ops.check_row_extent(B * Tp, max(2 * F, 6 * D), "joint MMDiT HIP path")
-        bf, f32 = torch.bfloat16, torch.float32
-
-        def z(*shape, dtype=bf):
-            with torch.inference_mode(False):
-                return torch.zeros(*shape, device=dev, dtype=dtype)
-
-        def zr(rows, *rest, dtype=bf):  # row buffer: zero rows pad it to a multiple of 64 for the weight-gradient GEMMs
-            return z(_rup(rows, 64), *rest, dtype=dtype)[:rows]
-
-        w: dict[str, object] = {"tokP": z(M, self._ki), "temb": z(Bp, d.frequency_embedding), "pre1": z(Bp, E), "h1": z(Bp, E),
-                                "e": z(Bp, E, dtype=f32), "emb": z(Bp, E, dtype=f32), "se": z(Bp, E),
-                                "mod": z(Bp, self.layout.mod_rows)}
+        f32 = torch.float32
+        w: dict[str, object] = {}
+        self._cond_buffers(w, B, H, W, train, train and self._grouped_widths())
         w["ctxP"] = zr(B * Lc, _rup(d.context_dim, 64))
         w["x"] = [z(M, D)]
         w["c0"] = zr(B * Lc, D)
@@ -183,47 +145,21 @@ class JointEngine(DiTEngine):
         for _ in range(L):
             per = {"ao": z(B * Tp, D), "lse": z(B, d.num_heads, Tp, dtype=f32)}
             for st in STREAMS:
-                mt = B * ntok[st]
-                a = {"x0": zr(mt, D), "mean1": zr(mt, dtype=f32), "rstd1": zr(mt, dtype=f32), "xm1": zr(mt, D), "qkv": zr(mt, 3 * D),
-                     "rrms": zr(mt, 2, dtype=f32), "a": zr(mt, D), "t1": zr(mt, D), "x1": zr(mt, D), "mean2": zr(mt, dtype=f32),
-                     "rstd2": zr(mt, dtype=f32), "xm2": zr(mt, D), "u": ops.mlp_u_buffer(zr, mt, D, F, train), "h": zr(mt, F), "t2": zr(mt, D)}
-                if train:
-                    a["wg"] = {"dt2": zr(mt, D), "du": zr(mt, 2 * F), "dt1": zr(mt, D), "dqkv": zr(mt, 3 * D)}
-                    a["dwb"] = z(2, B, 2, D, dtype=f32)
-                per[st] = a
+                per[st] = self._joint_stream_buffers(B, ntok[st], train)
             if train:  # q / k / v of every block are kept for the backward
                 per["q"], per["k"], per["v"] = (z(B, d.num_heads, Tp, 64) for _ in range(3))
             blk.append(per)
         w["blk"] = blk
         w["xl"] = z(M, D)
-        w["meanf"], w["rstdf"], w["xf"] = z(M, dtype=f32), z(M, dtype=f32), z(M, D)
-        w["otok"] = z(M, _rup(Fo, 8), dtype=f32)
-        w["pred"] = z(B, d.output_channels, H, W, dtype=f32)
         if train:
-            w["dO"] = z(M, self._ko)
             for st in STREAMS:
                 mt = B * ntok[st]
                 w["s_" + st] = {"dxa": zr(mt, D), "dxb": zr(mt, D), "dxm": zr(mt, D), "da": zr(mt, D), "dh": zr(mt, F)}
             w["dao"] = z(B * Tp, D)
             w["dq"], w["dk"], w["dv"] = (z(B, d.num_heads, Tp, 64) for _ in range(3))
-            w["dmod"] = z(Bp, self.layout.mod_rows)
-            w["dmod32"] = z(Bp, self.layout.mod_rows, dtype=f32)
-            w["dse"], w["demb"], w["demb16"] = z(Bp, E, dtype=f32), z(Bp, E, dtype=f32), z(Bp, E)
-            w["dh1"], w["dpre1"] = z(Bp, E, dtype=f32), z(Bp, E)
-            w["scr_last"], w["scr_conv"] = z(_rup(Fo, 8), D, dtype=f32), z(D, self._ki, dtype=f32)
-            # scratch of the bit-reproducible (and faster) small GEMMs / column sums of the conditioning backward (engine._cond_bwd)
-            w["det_scr"] = torch.empty(max(2 * self.layout.mod_rows * d.embedding_dim, 1 << 22), device=self.dev, dtype=f32)
-            if ops.WgradGroups.widths_ok(D, F) and tuning.on("DL_WGRAD_GROUP"):
-                w["tn_slab"] = torch.empty(ops.WgradGroups.slab_floats(D, F), device=self.dev, dtype=f32)
-        self.ws, self._ws_key = w, key
-        self.geo = (B, H, W, gh, gw, N, M, Bp, Fo)
         self.jgeo = (Lc, T, Tp)
-        if len(self._ws_cache) >= 8:
-            self._ws_cache.pop(next(iter(self._ws_cache)))
-        self._ws_cache[key] = (w, self.geo)
-        if (Lc, gh, gw) not in self._rope:
-            c, s = joint_rope_tables(Lc, gh, gw, d.rope_axes_dim, d.rope_base)
-            self._rope[(Lc, gh, gw)] = (c.to(dev), s.to(dev))
+        self._publish(w, key, (B, H, W, gh, gw, N, M, _rup(B, 64), p * p * d.output_channels), (Lc, gh, gw),
+                      lambda: joint_rope_tables(Lc, gh, gw, d.rope_axes_dim, d.rope_base))
 
     def _streams(self, Lc: int, N: int):
         """(name, tokens, row offset in the joint sequence, column offset of its six modulation rows inside a block's 12D)"""
@@ -323,53 +259,17 @@ class JointEngine(DiTEngine):
         rot = sum(d.rope_axes_dim)
         mod, dmod = w["mod"], w["dmod32"]
         dmod[:B].zero_()
-        Fo8 = _rup(Fo, 8)
         streams = self._streams(Lc, N)
         si, sc = w["s_input"], w["s_context"]
 
-        ops.patchify(dpred, w["dO"], d.patch_size, ops.PATCH_PPC)
-        gl = self.G("last_layer.linear.weight")
-        if Fo == Fo8:
-            ops.gemm_tn(w["dO"], w["xf"], gl, M=Fo, N=D)
-        else:
-            w["scr_last"].zero_()
-            ops.gemm_tn(w["dO"], w["xf"], w["scr_last"], M=Fo8, N=D)
-            ops.reduce_rows_f32(w["scr_last"], gl, 1, Fo * D)
-        ops.colsum(w["dO"], self.G("last_layer.linear.bias"), M, Fo)
-        ops.gemm_nt(w["dO"], sh["last_layer.linear.weight|t"], si["dxm"], M=M, N=D, K=self._ko)
+        self._head_bwd(dpred, si["dxm"])
         mo = L * 12 * D
         ml = (L - 1) * 12 * D
         al = w["blk"][L - 1]["input"]
         ops.ln_modulate_bwd(si["dxm"], w["xl"], None, None, mod[:, mo : mo + D], N, w["meanf"], w["rstdf"], dfe.get(L - 1), si["dxa"],
                             dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], None, gate_t=al["t2"],
                             gate=mod[:, ml + 5 * D : ml + 6 * D], dt=al["wg"]["dt2"], dgate=dmod[:, ml + 5 * D : ml + 6 * D])
-
-        main = torch.cuda.current_stream()
-        side = self._side_stream()
-        side.wait_stream(main)
-        side_wgs = tuning.integer("DL_SIDE_WGS", 128)
-
-        def on_side(fn) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                fn()
-
-        # the four linears of a stream as ONE atomics-free launch once its last operand (dqkv) exists (ops.WgradGroups); widths the
-        # 384 x 192 tile does not divide keep one atomic launch per linear
-        groups = ops.WgradGroups(w["tn_slab"], on_side, max_wgs=side_wgs) if w.get("tn_slab") is not None else None
-
-        def wgrad(x_grad: Tensor, x_in: Tensor, gname: str) -> None:
-            if groups is not None:
-                groups.add(x_grad, x_in, self.G(gname))
-            else:
-                on_side(lambda: ops.gemm_tn(x_grad, x_in, self.G(gname), max_wgs=side_wgs))
-
-        def fold_norm(partial: Tensor, gname: str) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                ops.reduce_rows_f32(partial, self.G(gname), B, 2 * D, clear=True)
+        sw = SideWork(self)
 
         dx: dict[str, Tensor | None] = {"input": si["dxa"], "context": None}  # residual-stream gradients (None: zero so far)
         scr = {"input": si, "context": sc}
@@ -385,18 +285,18 @@ class JointEngine(DiTEngine):
                     continue
                 a, mo, s, g = per[st], base + mc, scr[st], per[st]["wg"]
                 # MLP branch (dt2 / dgate were produced by the LayerNorm backward that precedes this block in the chain)
-                wgrad(g["dt2"], a["h"], pre + f"mlp_{st}.2.weight")
+                sw.wgrad(g["dt2"], a["h"], pre + f"mlp_{st}.2.weight")
                 ops.mlp_swiglu_bwd(g["dt2"], sh[pre + f"mlp_{st}.2.weight|t"], a["xm2"], sh[pre + f"mlp_{st}.0.weight|g"], a["u"], s["dh"], g["du"])
-                wgrad(g["du"], a["xm2"], pre + f"mlp_{st}.0.weight")
+                sw.wgrad(g["du"], a["xm2"], pre + f"mlp_{st}.0.weight")
                 ops.gemm_nt(g["du"], sh[pre + f"mlp_{st}.0.weight|t"], s["dxm"])
                 nx = other(s, dx[st])
                 ops.ln_modulate_bwd(s["dxm"], a["x1"], self.P(pre + f"{st}_norm_2.weight"), self.P(pre + f"{st}_norm_2.bias"),
                                     mod[:, mo + 3 * D : mo + 4 * D], nt, a["mean2"], a["rstd2"], dx[st], nx,
                                     dmod[:, mo + 3 * D : mo + 4 * D], dmod[:, mo + 4 * D : mo + 5 * D], a["dwb"][1], gate_t=a["t1"],
                                     gate=mod[:, mo + 2 * D : mo + 3 * D], dt=g["dt1"], dgate=dmod[:, mo + 2 * D : mo + 3 * D])
-                fold_norm(a["dwb"][1], pre + f"{st}_norm_2.weight")
+                sw.fold(a["dwb"][1], pre + f"{st}_norm_2.weight", B)
                 dx[st] = nx
-                wgrad(g["dt1"], a["a"], pre + f"attention.{st}_proj_out.weight")
+                sw.wgrad(g["dt1"], a["a"], pre + f"attention.{st}_proj_out.weight")
                 ops.gemm_nt(g["dt1"], sh[pre + f"attention.{st}_proj_out.weight|t"], s["da"])
                 ops.copy_rows3d(s["da"], nt * D, D, w["dao"][off:], Tp * D, D, B, nt, D)
             ops.attn_bwd_ex(per["q"], per["k"], per["v"], per["ao"], w["dao"], per["lse"], w["dq"], w["dk"], w["dv"], B, Hh, Tp, Tp,
@@ -407,7 +307,7 @@ class JointEngine(DiTEngine):
                                      self.P(pre + f"attention.qk_norm_{st}.key_norm.scale"), cos[off:], sin[off:], a["rrms"],
                                      g["dqkv"], self.G(pre + f"attention.qk_norm_{st}.query_norm.scale"), B, nt, Hh, 64, rot,
                                      n_off=off)
-                wgrad(g["dqkv"], a["xm1"], pre + f"attention.qkv_{st}.weight")
+                sw.wgrad(g["dqkv"], a["xm1"], pre + f"attention.qkv_{st}.weight")
                 ops.gemm_nt(g["dqkv"], sh[pre + f"attention.qkv_{st}.weight|t"], s["dxm"])
                 if st == "input" and i - 1 in dfe and dx[st] is not None:
                     ops.add_bf16(dx[st], dfe[i - 1], dx[st])
@@ -421,13 +321,10 @@ class JointEngine(DiTEngine):
                 ops.ln_modulate_bwd(s["dxm"], a["xin"], self.P(pre + f"{st}_norm_1.weight"), self.P(pre + f"{st}_norm_1.bias"),
                                     mod[:, mo : mo + D], nt, a["mean1"], a["rstd1"], dx[st], nx, dmod[:, mo : mo + D],
                                     dmod[:, mo + D : mo + 2 * D], a["dwb"][0], **nxt)
-                fold_norm(a["dwb"][0], pre + f"{st}_norm_1.weight")
+                sw.fold(a["dwb"][0], pre + f"{st}_norm_1.weight", B)
                 dx[st] = nx
-            if groups is not None:
-                groups.flush()
-            if self.reducer is not None:
-                self.reducer.ready(*self.layer_ranges[i], extra_events=(side.record_event(),))
-        main.wait_stream(side)
+            self._end_block(sw, i)
+        sw.join()
         # context_embed (no gradient flows into the precomputed embeddings)
         ops.gemm_tn(dx["context"], w["ctxP"], self.G("context_embed.weight"), M=D, N=Cd)
         self._cond_bwd(dx["input"])

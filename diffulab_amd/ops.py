@@ -441,23 +441,6 @@ class WgradGroups:
             self._issue(key)
 
 
-def grouped_wgrad_fn(G, slab: Tensor | None, on_side, max_wgs: int = 0):
-    """the `wgrad(dy, x, parameter name)` hook of an engine's backward: with a slab the block's linears are collected and issued as
-    atomics-free dl_gemm_tn_group launches (WgradGroups; `wgrad.flush()` issues what is pending -- call it at every block end and
-    before the side stream is joined), without one each is a dl_gemm_tn_ex launch.  G(name) -> the f32 gradient view; on_side(fn)
-    runs fn where the engine wants its weight gradients (side stream behind an event of the main stream)."""
-    groups = WgradGroups(slab, on_side, max_wgs=max_wgs) if slab is not None else None
-
-    def wgrad(x_grad: Tensor, x_in: Tensor, gname: str) -> None:
-        if groups is not None:
-            groups.add(x_grad, x_in, G(gname))
-        else:
-            on_side(lambda: gemm_tn(x_grad, x_in, G(gname), max_wgs=max_wgs))
-
-    wgrad.flush = groups.flush if groups is not None else (lambda: None)
-    return wgrad
-
-
 # ------------------------------------------------------------------ block kernels
 def ln_modulate_fwd(x, w, b, scale, shift, rows_per_mod, eps, out, mean, rstd, t=None, gate=None, x_out=None):
     """out = modulate(LN(x')) with x' = x (+ gate * t, written to x_out, when the gated residual is fused in)"""

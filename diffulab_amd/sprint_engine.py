@@ -18,7 +18,7 @@ import torch
 from torch import Tensor
 
 from . import ops, tuning
-from .engine import DiTDims, DiTEngine, ParamLayout, _must, _rup, rope_grid_tables
+from .engine import DiTDims, DiTEngine, ParamLayout, SideWork, _must, _rup, rope_grid_tables
 
 
 @dataclass
@@ -62,48 +62,31 @@ class SprintEngine(DiTEngine):
 
     # ------------------------------------------------------------------ workspace
     def _alloc(self, B: int, H: int, W: int, train: bool, k: int | None = None) -> None:  # type: ignore[override]
-        d, dev = self.d, self.dev
+        d, z = self.d, self._z
         p = d.patch_size
         gh, gw = H // p, W // p
         N = gh * gw
         k = N if k is None else k
         key = (B, H, W, train, k)
-        if key == self._ws_key:
+        if self._cached(key):
             return
-        if key in self._ws_cache:
-            self.ws, self.geo = self._ws_cache[key]
-            self._ws_key = key
-            return
-        D, E, L = d.inner_dim, d.embedding_dim, d.depth
+        D = d.inner_dim
         for n in (N, k):
             if n % 64 or (n > 256 and (n % 256 or n > ops.ATTN_MAX_TOKENS)):
                 raise NotImplementedError(f"SprintDiT HIP path: token counts must be multiples of 64 up to 256, or of 256 up to "
                                           f"{ops.ATTN_MAX_TOKENS} (grid {gh}x{gw} = {N} tokens, {k} kept)")
-        M, Bp, Fo = B * N, _rup(B, 64), p * p * d.output_channels
-        bf, f32 = torch.bfloat16, torch.float32
+        M = B * N
         F = d.mlp_ratio * D
         ops.check_row_extent(M, max(2 * F, 6 * D), "SprintDiT HIP path")
-
-        def z(*shape, dtype=bf):
-            with torch.inference_mode(False):
-                return torch.zeros(*shape, device=dev, dtype=dtype)
-
-        w: dict[str, object] = {"tokP": z(M, self._ki), "temb": z(Bp, d.frequency_embedding), "pre1": z(Bp, E), "h1": z(Bp, E),
-                                "e": z(Bp, E, dtype=f32), "emb": z(Bp, E, dtype=f32), "se": z(Bp, E),
-                                "mod": z(Bp, self.layout.mod_rows)}
+        w: dict[str, object] = {}
+        self._cond_buffers(w, B, H, W, train, train and self._grouped_widths())
         ne, nd = d.encoder_depth, d.deep_layers_depth
         tokens = [N] * ne + [k] * nd + [N] * d.decoder_depth
         blk = []
         for nt in tokens:
-            mt = B * nt
-            a = {"x0": z(mt, D), "mean1": z(mt, dtype=f32), "rstd1": z(mt, dtype=f32), "xm1": z(mt, D), "qkv": z(mt, 3 * D),
-                 "q": z(B, d.num_heads, nt, 64), "k": z(B, d.num_heads, nt, 64), "v": z(B, d.num_heads, nt, 64),
-                 "rrms": z(mt, 2, dtype=f32), "a": z(mt, D), "lse": z(B, d.num_heads, nt, dtype=f32), "t1": z(mt, D),
-                 "x1": z(mt, D), "mean2": z(mt, dtype=f32), "rstd2": z(mt, dtype=f32), "xm2": z(mt, D), "u": ops.mlp_u_buffer(z, mt, D, F, train),
-                 "h": z(mt, F), "t2": z(mt, D)}
+            a = self._dit_block_buffers(B, nt, train)
             if train:
-                a["wg"] = {"dt2": z(mt, D), "du": z(mt, 2 * F), "dt1": z(mt, D), "dqkv": z(mt, 3 * D)}
-                a["dwb"] = z(2, B, 2, D, dtype=f32)
+                a["dwb"] = z(2, B, 2, D, dtype=torch.float32)
             blk.append(a)
         w["blk"] = blk
         w["x_stem"] = z(M, D)
@@ -111,35 +94,21 @@ class SprintEngine(DiTEngine):
         w["cat"] = z(M, 2 * D)               # [restored canvas | encoder output]
         w["xd0"], w["xd_out"] = z(B * k, D), z(B * k, D)
         w["xfuse"], w["xdec"] = z(M, D), z(M, D)
-        w["meanf"], w["rstdf"], w["xf"] = z(M, dtype=f32), z(M, dtype=f32), z(M, D)
-        w["otok"] = z(M, _rup(Fo, 8), dtype=f32)
-        w["pred"] = z(B, d.output_channels, H, W, dtype=f32)
         if train:
-            w["dO"] = z(M, self._ko)
             for nt in {N, k}:  # chain scratch per token count
-                mt = B * nt
-                w[f"s{nt}"] = {"dxa": z(mt, D), "dxb": z(mt, D), "dxm": z(mt, D), "da": z(mt, D), "dh": z(mt, F),
-                               "dq": z(B, d.num_heads, nt, 64), "dk": z(B, d.num_heads, nt, 64), "dv": z(B, d.num_heads, nt, 64)}
+                w[f"s{nt}"] = self._dit_chain_buffers(B, nt)
             w["dleft"], w["dright"], w["dxd"] = z(M, D), z(M, D), z(B * k, D)
-            w["dmod"] = z(Bp, self.layout.mod_rows)
-            w["dmod32"] = z(Bp, self.layout.mod_rows, dtype=f32)
-            w["dse"], w["demb"], w["demb16"] = z(Bp, E, dtype=f32), z(Bp, E, dtype=f32), z(Bp, E)
-            w["dh1"], w["dpre1"] = z(Bp, E, dtype=f32), z(Bp, E)
-            w["scr_last"], w["scr_conv"] = z(_rup(Fo, 8), D, dtype=f32), z(D, self._ki, dtype=f32)
-            # scratch of the bit-reproducible (and faster) small GEMMs / column sums of the conditioning backward (engine._cond_bwd)
-            w["det_scr"] = torch.empty(max(2 * self.layout.mod_rows * d.embedding_dim, 1 << 22), device=self.dev, dtype=f32)
-            if ops.WgradGroups.widths_ok(D, F) and tuning.on("DL_WGRAD_GROUP"):  # grouped weight gradients (ops.WgradGroups)
-                w["tn_slab"] = torch.empty(ops.WgradGroups.slab_floats(D, F), device=self.dev, dtype=f32)
             if D <= 512 and tuning.on("DL_QK_INPLACE"):  # scale-gradient partials of the in-place QK-norm backward (ops.qk_inplace_ok)
-                w["qk_part"] = torch.empty(1024 * 2 * D, device=self.dev, dtype=f32)
-        self.ws, self._ws_key = w, key
-        self.geo = (B, H, W, gh, gw, N, M, Bp, Fo)
-        if len(self._ws_cache) >= 8:
-            self._ws_cache.pop(next(iter(self._ws_cache)))
-        self._ws_cache[key] = (w, self.geo)
-        if (gh, gw) not in self._rope:
-            c, s = rope_grid_tables(gh, gw, d.rope_axes_dim, d.rope_base)
-            self._rope[(gh, gw)] = (c.to(dev), s.to(dev))
+                w["qk_part"] = torch.empty(1024 * 2 * D, device=self.dev, dtype=torch.float32)
+        self._publish(w, key, (B, H, W, gh, gw, N, M, _rup(B, 64), p * p * d.output_channels), (gh, gw),
+                      lambda: rope_grid_tables(gh, gw, d.rope_axes_dim, d.rope_base))
+
+    def _dit_chain_buffers(self, B: int, nt: int) -> dict:
+        """scratch of the backward chain over B * nt tokens (shared by every block with that token count)"""
+        d, z = self.d, self._z
+        D, Hh, mt = d.inner_dim, d.num_heads, B * nt
+        return {"dxa": z(mt, D), "dxb": z(mt, D), "dxm": z(mt, D), "da": z(mt, D), "dh": z(mt, d.mlp_ratio * D),
+                "dq": z(B, Hh, nt, 64), "dk": z(B, Hh, nt, 64), "dv": z(B, Hh, nt, 64)}
 
     # ------------------------------------------------------------------ stages
     def _stage_fwd(self, blocks: range, xin: Tensor, nt: int, pos: Tensor | None, out: Tensor) -> None:
@@ -185,8 +154,7 @@ class SprintEngine(DiTEngine):
             pend = (a["x1"], a["t2"], mod[:, mo + 5 * D : mo + 6 * D])
         ops.gated_residual_fwd(pend[0], pend[1], pend[2], nt, out)
 
-    def _stage_bwd(self, blocks: range, dx: Tensor, nt: int, pos: Tensor | None, dfe: dict[int, Tensor], wgrad, fold_norm,
-                   side) -> Tensor:
+    def _stage_bwd(self, blocks: range, dx: Tensor, nt: int, pos: Tensor | None, dfe: dict[int, Tensor], sw: SideWork) -> Tensor:
         """backward of _stage_fwd: dx = gradient at the stage output, contiguous bf16 [B*nt, D] (overwritten); returns the
         gradient at the stage input.  dfe: {block index: auxiliary-loss gradient at that block's output}"""
         d, w, sh = self.d, self.ws, self.sh
@@ -213,18 +181,18 @@ class SprintEngine(DiTEngine):
             bi = blocks[j]
             a, pre, mo = w["blk"][bi], self.prefixes[bi], bi * 6 * D
             g = a["wg"]
-            wgrad(g["dt2"], a["h"], pre + "mlp_input.2.weight")
+            sw.wgrad(g["dt2"], a["h"], pre + "mlp_input.2.weight")
             ops.mlp_swiglu_bwd(g["dt2"], sh[pre + "mlp_input.2.weight|t"], a["xm2"], sh[pre + "mlp_input.0.weight|g"], a["u"], s["dh"], g["du"])
-            wgrad(g["du"], a["xm2"], pre + "mlp_input.0.weight")
+            sw.wgrad(g["du"], a["xm2"], pre + "mlp_input.0.weight")
             ops.gemm_nt(g["du"], sh[pre + "mlp_input.0.weight|t"], s["dxm"])
             dx_alt = other(dx)
             ops.ln_modulate_bwd(s["dxm"], a["x1"], self.P(pre + "norm_2.weight"), self.P(pre + "norm_2.bias"),
                                 mod[:, mo + 3 * D : mo + 4 * D], nt, a["mean2"], a["rstd2"], dx, dx_alt, dmod[:, mo + 3 * D : mo + 4 * D],
                                 dmod[:, mo + 4 * D : mo + 5 * D], a["dwb"][1], gate_t=a["t1"], gate=mod[:, mo + 2 * D : mo + 3 * D],
                                 dt=g["dt1"], dgate=dmod[:, mo + 2 * D : mo + 3 * D])
-            fold_norm(a["dwb"][1], pre + "norm_2.weight")
+            sw.fold(a["dwb"][1], pre + "norm_2.weight", B)
             dx = dx_alt
-            wgrad(g["dt1"], a["a"], pre + "attention.proj_out.weight")
+            sw.wgrad(g["dt1"], a["a"], pre + "attention.proj_out.weight")
             ops.gemm_nt(g["dt1"], sh[pre + "attention.proj_out.weight|t"], s["da"])
             if inplace_qk:  # dQ, dK, dV token-major into dqkv; the QK-norm backward transforms the q / k thirds in place
                 ops.attn_bwd_tok(a["q"], a["k"], a["qkv"], a["a"], s["da"], a["lse"], g["dqkv"], B, Hh, nt, 64, 64**-0.5)
@@ -242,7 +210,7 @@ class SprintEngine(DiTEngine):
                                      self.P(pre + "attention.qk_norm.query_norm.scale"),
                                      self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], g["dqkv"],
                                      self.G(pre + "attention.qk_norm.query_norm.scale"), B, nt, Hh, 64, rot, pos=pos)
-            wgrad(g["dqkv"], a["xm1"], pre + "attention.qkv.weight")
+            sw.wgrad(g["dqkv"], a["xm1"], pre + "attention.qkv.weight")
             ops.gemm_nt(g["dqkv"], sh[pre + "attention.qkv.weight|t"], s["dxm"])
             nxt = {}
             if j > 0:
@@ -256,11 +224,9 @@ class SprintEngine(DiTEngine):
             ops.ln_modulate_bwd(s["dxm"], a["xin"], self.P(pre + "norm_1.weight"), self.P(pre + "norm_1.bias"), mod[:, mo : mo + D],
                                 nt, a["mean1"], a["rstd1"], dx, dx_alt, dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D],
                                 a["dwb"][0], **nxt)
-            fold_norm(a["dwb"][0], pre + "norm_1.weight")
+            sw.fold(a["dwb"][0], pre + "norm_1.weight", B)
             dx = dx_alt
-            getattr(wgrad, "flush", lambda: None)()
-            if self.reducer is not None:
-                self.reducer.ready(*self.layer_ranges[bi], extra_events=(side.record_event(),))
+            self._end_block(sw, bi)
         return dx
 
     # ------------------------------------------------------------------ forward
@@ -320,44 +286,15 @@ class SprintEngine(DiTEngine):
         dfe = {kb: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb, g in (dfeats or {}).items()}
         mod, dmod = w["mod"], w["dmod32"]
         dmod[:B].zero_()
-        Fo8 = _rup(Fo, 8)
         sN = w[f"s{N}"]
 
         # head
-        ops.patchify(dpred, w["dO"], d.patch_size, ops.PATCH_PPC)
-        gl = self.G("last_layer.linear.weight")
-        if Fo == Fo8:
-            ops.gemm_tn(w["dO"], w["xf"], gl, M=Fo, N=D)
-        else:
-            w["scr_last"].zero_()
-            ops.gemm_tn(w["dO"], w["xf"], w["scr_last"], M=Fo8, N=D)
-            ops.reduce_rows_f32(w["scr_last"], gl, 1, Fo * D)
-        ops.colsum(w["dO"], self.G("last_layer.linear.bias"), M, Fo)
-        ops.gemm_nt(w["dO"], sh["last_layer.linear.weight|t"], sN["dxm"], M=M, N=D, K=self._ko)
+        self._head_bwd(dpred, sN["dxm"])
         mo = L * 6 * D
         ops.ln_modulate_bwd(sN["dxm"], w["xdec"], None, None, mod[:, mo : mo + D], N, w["meanf"], w["rstdf"], None, sN["dxa"],
                             dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], None)
-
-        main = torch.cuda.current_stream()
-        side = self._side_stream()
-        side.wait_stream(main)
-        side_wgs = tuning.integer("DL_SIDE_WGS", 128)
-
-        def on_side(fn) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                fn()
-
-        wgrad = ops.grouped_wgrad_fn(self.G, w.get("tn_slab"), on_side, side_wgs)  # (one atomics-free launch per block where the tile divides)
-
-        def fold_norm(partial: Tensor, gname: str) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                ops.reduce_rows_f32(partial, self.G(gname), B, 2 * D, clear=True)
-
-        dxf = self._stage_bwd(range(ne + nd, L), sN["dxa"], N, None, {}, wgrad, fold_norm, side)
+        sw = SideWork(self)
+        dxf = self._stage_bwd(range(ne + nd, L), sN["dxa"], N, None, {}, sw)
         # fuse: xfuse = [restored | enc] Wf^T
         ops.gemm_tn(dxf, w["cat"], self.G("fuse.weight"))  # (main stream: dxf is chain scratch that the next stage reuses)
         wt = sh["fuse.weight|t"]
@@ -366,11 +303,11 @@ class SprintEngine(DiTEngine):
         ops.masked_colsum(w["dleft"], route.inv.view(-1), self.G("mask_token").view(D), M, D)
         if not route.skip_deep:
             ops.gather_tokens(w["dleft"], route.idx, w["dxd"], B, N, k, D, keep=route.keep)
-            dxd0 = self._stage_bwd(range(ne, ne + nd), w["dxd"], k, route.idx.view(-1), {}, wgrad, fold_norm, side)
+            dxd0 = self._stage_bwd(range(ne, ne + nd), w["dxd"], k, route.idx.view(-1), {}, sw)
             ops.scatter_tokens_add(dxd0, route.idx, w["dright"], B, N, k, D)
         elif self.reducer is not None:
             for bi in reversed(range(ne, ne + nd)):
                 self.reducer.ready(*self.layer_ranges[bi])
-        dx0 = self._stage_bwd(range(0, ne), w["dright"], N, None, dfe, wgrad, fold_norm, side)
-        main.wait_stream(side)
+        dx0 = self._stage_bwd(range(0, ne), w["dright"], N, None, dfe, sw)
+        sw.join()
         self._cond_bwd(dx0)

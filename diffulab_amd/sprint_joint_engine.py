@@ -14,14 +14,13 @@ is the identity); RoPE rows of the kept tokens come from a position index, the k
 
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 
 import torch
 from torch import Tensor
 
-from . import ops, tuning
-from .engine import DiTEngine, _rup
+from . import ops
+from .engine import ArenaLayout, DiTEngine, SideWork, _rup
 from .mmdit_engine import STREAMS, JointDims, joint_rope_tables
 from .sprint_engine import Route
 
@@ -49,19 +48,12 @@ class SprintJointDims(JointDims):
                 + [(f"decoder_layers.{i}.", "J") for i in range(self.decoder_depth)])
 
 
-class SprintJointLayout:
-    def __init__(self, d: "SprintJointDims | JointStackDims", sprint: bool = True) -> None:
-        D, E, p = d.inner_dim, d.embedding_dim, d.patch_size
+class SprintJointLayout(ArenaLayout):
+    def _place(self, d: "SprintJointDims | JointStackDims", sprint: bool = True) -> None:
+        D, E, p, add = d.inner_dim, d.embedding_dim, d.patch_size, self.add
         F = d.mlp_ratio * D
-        self.entries: dict[str, tuple[int, tuple[int, ...]]] = {}
-        self.size = 0
         kinds = d.kinds()
         self.prefixes = [pre for pre, _ in kinds]
-
-        def add(name: str, shape: tuple[int, ...], align: int = 64) -> None:
-            self.size = _rup(self.size, align)
-            self.entries[name] = (self.size, shape)
-            self.size += math.prod(shape)
 
         def mods(suffix: str, width) -> list[str]:
             names = []
@@ -104,16 +96,7 @@ class SprintJointLayout:
         for pre, kind in kinds:
             if kind == "J":
                 self.block_first.append(pre + "input_norm_1.weight")
-                for st in STREAMS:
-                    for n in (1, 2):
-                        add(pre + f"{st}_norm_{n}.weight", (D,))
-                        add(pre + f"{st}_norm_{n}.bias", (D,), align=1)
-                    add(pre + f"attention.qk_norm_{st}.query_norm.scale", (D,))
-                    add(pre + f"attention.qk_norm_{st}.key_norm.scale", (D,), align=1)
-                    add(pre + f"attention.qkv_{st}.weight", (3 * D, D))
-                    add(pre + f"attention.{st}_proj_out.weight", (D, D))
-                    add(pre + f"mlp_{st}.0.weight", (2 * F, D))
-                    add(pre + f"mlp_{st}.2.weight", (D, F))
+                self.add_joint_block(pre, D, F)
             else:
                 self.block_first.append(pre + "norm.weight")
                 add(pre + "norm.weight", (D,))
@@ -124,11 +107,6 @@ class SprintJointLayout:
                 add(pre + "attention.proj_out.weight", (D, D))
                 add(pre + "mlp.0.weight", (2 * F, D))
                 add(pre + "mlp.2.weight", (D, F))
-        self.size = _rup(self.size, 64)
-
-    def view(self, flat: Tensor, name: str) -> Tensor:
-        off, shape = self.entries[name]
-        return flat[off : off + math.prod(shape)].view(shape)
 
 
 class SprintJointEngine(DiTEngine):
@@ -160,15 +138,11 @@ class SprintJointEngine(DiTEngine):
 
     # ------------------------------------------------------------------ workspace
     def _alloc(self, B: int, H: int, W: int, train: bool, Lc: int = 0, k: int = 0) -> None:  # type: ignore[override]
-        d, dev = self.d, self.dev
+        d, z, zr = self.d, self._z, self._zr
         key = (B, H, W, train, Lc, k)
-        if key == self._ws_key:
+        if self._cached(key):
             return
-        if key in self._ws_cache:
-            self.ws, self.geo = self._ws_cache[key]
-            self._ws_key = key
-            return
-        D, E, p = d.inner_dim, d.embedding_dim, d.patch_size
+        D, p = d.inner_dim, d.patch_size
         gh, gw = H // p, W // p
         N = gh * gw
         Tf, Td = Lc + N, Lc + k
@@ -176,21 +150,12 @@ class SprintJointEngine(DiTEngine):
         if Tpf > ops.ATTN_MAX_TOKENS or (B * N) % 64 or Lc < 1:
             raise NotImplementedError(f"joint SprintDiT HIP path: context + image tokens <= {ops.ATTN_MAX_TOKENS} (got {Lc} + {N}), batch * tokens of "
                                       f"each stream a multiple of 64 (kept {k})")
-        M, Bp, Fo, F = B * N, _rup(B, 64), p * p * d.output_channels, d.mlp_ratio * D
+        M, F = B * N, d.mlp_ratio * D
         ops.check_row_extent(B * Tpf, max(2 * F, 6 * D), "joint SprintDiT HIP path")
-        bf, f32 = torch.bfloat16, torch.float32
+        f32 = torch.float32
         Hh = d.num_heads
-
-        def z(*shape, dtype=bf):
-            with torch.inference_mode(False):
-                return torch.zeros(*shape, device=dev, dtype=dtype)
-
-        def zr(rows, *rest, dtype=bf):  # row buffer: zero rows pad it to a multiple of 64 for the weight-gradient GEMMs
-            return z(_rup(rows, 64), *rest, dtype=dtype)[:rows]
-
-        w: dict[str, object] = {"tokP": z(M, self._ki), "temb": z(Bp, d.frequency_embedding), "pre1": z(Bp, E), "h1": z(Bp, E),
-                                "e": z(Bp, E, dtype=f32), "emb": z(Bp, E, dtype=f32), "se": z(Bp, E),
-                                "mod": z(Bp, self.layout.mod_rows)}
+        w: dict[str, object] = {}
+        self._cond_buffers(w, B, H, W, train, train and self._grouped_widths())
         w["ctxP"] = zr(B * Lc, _rup(d.context_dim, 64))
         w["x"] = [z(M, D)]
         w["c0"] = zr(B * Lc, D)
@@ -202,25 +167,12 @@ class SprintJointEngine(DiTEngine):
         for bi, (_, kind) in enumerate(self.kinds):
             deep = ne <= bi < ne + nd
             nx, Tp = (k, Tpd) if deep else (N, Tpf)
-            per: dict[str, object] = {"ao": z(B * Tp, D), "lse": z(B, Hh, Tp, dtype=f32), "q": z(B, Hh, Tp, 64), "k": z(B, Hh, Tp, 64),
-                                      "v": z(B, Hh, Tp, 64)}
+            per = self._joint_attn_buffers(B, Tp)
             if kind == "J":
                 for st, nt in (("input", nx), ("context", Lc)):
-                    mt = B * nt
-                    a = {"x0": zr(mt, D), "mean1": zr(mt, dtype=f32), "rstd1": zr(mt, dtype=f32), "xm1": zr(mt, D), "qkv": zr(mt, 3 * D),
-                         "rrms": zr(mt, 2, dtype=f32), "a": zr(mt, D), "t1": zr(mt, D), "x1": zr(mt, D), "mean2": zr(mt, dtype=f32),
-                         "rstd2": zr(mt, dtype=f32), "xm2": zr(mt, D), "u": ops.mlp_u_buffer(zr, mt, D, F, train), "h": zr(mt, F), "t2": zr(mt, D)}
-                    if train:
-                        a["wg"] = {"dt2": zr(mt, D), "du": zr(mt, 2 * F), "dt1": zr(mt, D), "dqkv": zr(mt, 3 * D)}
-                        a["dwb"] = z(2, B, 2, D, dtype=f32)
-                    per[st] = a
+                    per[st] = self._joint_stream_buffers(B, nt, train)
             else:
-                mt = B * Td
-                per.update({"x0": zr(mt, D), "mean": zr(mt, dtype=f32), "rstd": zr(mt, dtype=f32), "m": zr(mt, D), "qkv": zr(mt, 3 * D),
-                            "rrms": zr(mt, 2, dtype=f32), "a": zr(mt, D), "ta": zr(mt, D), "u": ops.mlp_u_buffer(zr, mt, D, F, train), "h": zr(mt, F), "t": zr(mt, D)})
-                if train:
-                    per["wg"] = {"dt": zr(mt, D), "du": zr(mt, 2 * F), "dqkv": zr(mt, 3 * D)}
-                    per["dwb"] = z(1, B, 2, D, dtype=f32)
+                per.update(self._single_stream_buffers(B, Td, train))
             blk.append(per)
         w["blk"] = blk
         w["cat"], w["ccat"] = z(M, 2 * D), zr(B * Lc, 2 * D)   # [restored | encoder image], [deep context | encoder context]
@@ -229,11 +181,7 @@ class SprintJointEngine(DiTEngine):
         w["xj"], w["cj"] = z(B * k, D), zr(B * Lc, D)           # outputs of the deep joint sub-stage
         w["lat0"], w["lat_out"] = zr(B * Td, D), zr(B * Td, D)
         w["xfuse"], w["cfuse"], w["xdec"] = z(M, D), zr(B * Lc, D), z(M, D)
-        w["meanf"], w["rstdf"], w["xf"] = z(M, dtype=f32), z(M, dtype=f32), z(M, D)
-        w["otok"] = z(M, _rup(Fo, 8), dtype=f32)
-        w["pred"] = z(B, d.output_channels, H, W, dtype=f32)
         if train:
-            w["dO"] = z(M, self._ko)
             for name, mt in ((f"x{N}", M), (f"x{k}", B * k), ("c", B * Lc), ("l", B * Td)):
                 w["s_" + name] = {"dxa": zr(mt, D), "dxb": zr(mt, D), "dxm": zr(mt, D), "dxm2": zr(mt, D), "da": zr(mt, D), "dh": zr(mt, F)}
             for tag, Tp in (("f", Tpf), ("d", Tpd)):
@@ -242,23 +190,8 @@ class SprintJointEngine(DiTEngine):
             w["dleft"], w["dright"], w["dcl"], w["dcr"] = z(M, D), z(M, D), zr(B * Lc, D), zr(B * Lc, D)
             w["dxd"], w["dlat"], w["dxj"], w["dcj"] = z(B * k, D), zr(B * Td, D), z(B * k, D), zr(B * Lc, D)
             w["dxdec"] = z(M, D)
-            w["dmod"] = z(Bp, self.layout.mod_rows)
-            w["dmod32"] = z(Bp, self.layout.mod_rows, dtype=f32)
-            w["dse"], w["demb"], w["demb16"] = z(Bp, E, dtype=f32), z(Bp, E, dtype=f32), z(Bp, E)
-            w["dh1"], w["dpre1"] = z(Bp, E, dtype=f32), z(Bp, E)
-            w["scr_last"], w["scr_conv"] = z(_rup(Fo, 8), D, dtype=f32), z(D, self._ki, dtype=f32)
-            # scratch of the bit-reproducible (and faster) small GEMMs / column sums of the conditioning backward (engine._cond_bwd)
-            w["det_scr"] = torch.empty(max(2 * self.layout.mod_rows * d.embedding_dim, 1 << 22), device=self.dev, dtype=f32)
-            if ops.WgradGroups.widths_ok(D, F) and tuning.on("DL_WGRAD_GROUP"):  # grouped weight gradients (ops.WgradGroups)
-                w["tn_slab"] = torch.empty(ops.WgradGroups.slab_floats(D, F), device=self.dev, dtype=f32)
-        self.ws, self._ws_key = w, key
-        self.geo = (B, H, W, gh, gw, N, M, Bp, Fo)
-        if len(self._ws_cache) >= 8:
-            self._ws_cache.pop(next(iter(self._ws_cache)))
-        self._ws_cache[key] = (w, self.geo)
-        if (Lc, gh, gw) not in self._rope:
-            c, s = joint_rope_tables(Lc, gh, gw, d.rope_axes_dim, d.rope_base)
-            self._rope[(Lc, gh, gw)] = (c.to(dev), s.to(dev))
+        self._publish(w, key, (B, H, W, gh, gw, N, M, _rup(B, 64), p * p * d.output_channels), (Lc, gh, gw),
+                      lambda: joint_rope_tables(Lc, gh, gw, d.rope_axes_dim, d.rope_base))
 
     # ------------------------------------------------------------------ joint stage
     def _jstage_fwd(self, blocks, x_in: Tensor, c_in: Tensor, nx: int, pos: Tensor | None, kb: Tensor, x_out: Tensor,
@@ -314,11 +247,11 @@ class SprintJointEngine(DiTEngine):
         if c_out is not None:
             ops.gated_residual_fwd(pend["context"][0], pend["context"][1], pend["context"][2], Lc, c_out)
 
-    def _jstage_bwd(self, blocks, dx_x: Tensor, dx_c: Tensor | None, nx: int, pos: Tensor | None, kb: Tensor, tag: str, dfe, hooks):
+    def _jstage_bwd(self, blocks, dx_x: Tensor, dx_c: Tensor | None, nx: int, pos: Tensor | None, kb: Tensor, tag: str, dfe,
+                    sw: SideWork):
         """backward of _jstage_fwd.  dx_x / dx_c: gradients at the stage outputs (contiguous, overwritten; dx_c None: the context output
         was not produced).  Returns the gradients at the stage inputs (image, context)."""
         d, w, sh = self.d, self.ws, self.sh
-        wgrad, fold_norm, side = hooks
         B = self.geo[0]
         Lc = self._Lc
         D, Hh = d.inner_dim, d.num_heads
@@ -352,18 +285,18 @@ class SprintJointEngine(DiTEngine):
                 if st == "context" and skip_ctx_last and bi == last:
                     continue
                 a, mo, s, g = per[st], base + mc, scr[st], per[st]["wg"]
-                wgrad(g["dt2"], a["h"], pre + f"mlp_{st}.2.weight")
+                sw.wgrad(g["dt2"], a["h"], pre + f"mlp_{st}.2.weight")
                 ops.mlp_swiglu_bwd(g["dt2"], sh[pre + f"mlp_{st}.2.weight|t"], a["xm2"], sh[pre + f"mlp_{st}.0.weight|g"], a["u"], s["dh"], g["du"])
-                wgrad(g["du"], a["xm2"], pre + f"mlp_{st}.0.weight")
+                sw.wgrad(g["du"], a["xm2"], pre + f"mlp_{st}.0.weight")
                 ops.gemm_nt(g["du"], sh[pre + f"mlp_{st}.0.weight|t"], s["dxm"])
                 nx_ = other(s, dx[st])
                 ops.ln_modulate_bwd(s["dxm"], a["x1"], self.P(pre + f"{st}_norm_2.weight"), self.P(pre + f"{st}_norm_2.bias"),
                                     mod[:, mo + 3 * D : mo + 4 * D], nt, a["mean2"], a["rstd2"], dx[st], nx_,
                                     dmod[:, mo + 3 * D : mo + 4 * D], dmod[:, mo + 4 * D : mo + 5 * D], a["dwb"][1], gate_t=a["t1"],
                                     gate=mod[:, mo + 2 * D : mo + 3 * D], dt=g["dt1"], dgate=dmod[:, mo + 2 * D : mo + 3 * D])
-                fold_norm(a["dwb"][1], pre + f"{st}_norm_2.weight")
+                sw.fold(a["dwb"][1], pre + f"{st}_norm_2.weight", B)
                 dx[st] = nx_
-                wgrad(g["dt1"], a["a"], pre + f"attention.{st}_proj_out.weight")
+                sw.wgrad(g["dt1"], a["a"], pre + f"attention.{st}_proj_out.weight")
                 ops.gemm_nt(g["dt1"], sh[pre + f"attention.{st}_proj_out.weight|t"], s["da"])
                 ops.copy_rows3d(s["da"], nt * D, D, dao[off:], Tp * D, D, B, nt, D)
             ops.attn_bwd_ex(per["q"], per["k"], per["v"], per["ao"], dao, per["lse"], dq, dk, dv, B, Hh, Tp, Tp, 64, 64**-0.5, kb)
@@ -372,7 +305,7 @@ class SprintJointEngine(DiTEngine):
                 ops.qk_norm_rope_bwd(dq, dk, dv, a["qkv"], self.P(pre + f"attention.qk_norm_{st}.query_norm.scale"),
                                      self.P(pre + f"attention.qk_norm_{st}.key_norm.scale"), cos[off:], sin[off:], a["rrms"], g["dqkv"],
                                      self.G(pre + f"attention.qk_norm_{st}.query_norm.scale"), B, nt, Hh, 64, rot, pos=ps, n_off=off)
-                wgrad(g["dqkv"], a["xm1"], pre + f"attention.qkv_{st}.weight")
+                sw.wgrad(g["dqkv"], a["xm1"], pre + f"attention.qkv_{st}.weight")
                 ops.gemm_nt(g["dqkv"], sh[pre + f"attention.qkv_{st}.weight|t"], s["dxm"])
                 nxt = {}
                 if j > 0:
@@ -387,11 +320,9 @@ class SprintJointEngine(DiTEngine):
                 ops.ln_modulate_bwd(s["dxm"], a["xin"], self.P(pre + f"{st}_norm_1.weight"), self.P(pre + f"{st}_norm_1.bias"),
                                     mod[:, mo : mo + D], nt, a["mean1"], a["rstd1"], dx[st], nx_, dmod[:, mo : mo + D],
                                     dmod[:, mo + D : mo + 2 * D], a["dwb"][0], **nxt)
-                fold_norm(a["dwb"][0], pre + f"{st}_norm_1.weight")
+                sw.fold(a["dwb"][0], pre + f"{st}_norm_1.weight", B)
                 dx[st] = nx_
-            getattr(wgrad, "flush", lambda: None)()  # (grouped weight gradients: whatever of this block is still pending)
-            if self.reducer is not None:
-                self.reducer.ready(*self.layer_ranges[bi], extra_events=(side.record_event(),))
+            self._end_block(sw, bi)
         return dx["input"], dx["context"]
 
     # ------------------------------------------------------------------ single-stream stage
@@ -430,9 +361,8 @@ class SprintJointEngine(DiTEngine):
             pend = (xcur, a["t"], mod[:, mo + 2 * D : mo + 3 * D])
         ops.gated_residual_fwd(pend[0], pend[1], pend[2], T, out)
 
-    def _sstage_bwd(self, blocks, dlat: Tensor, T: int, pos: Tensor, kb: Tensor, hooks) -> Tensor:
+    def _sstage_bwd(self, blocks, dlat: Tensor, T: int, pos: Tensor, kb: Tensor, sw: SideWork) -> Tensor:
         d, w, sh = self.d, self.ws, self.sh
-        wgrad, fold_norm, side = hooks
         B = self.geo[0]
         D, Hh = d.inner_dim, d.num_heads
         cos, sin = self._tabs
@@ -451,10 +381,10 @@ class SprintJointEngine(DiTEngine):
             bi = blocks[j]
             a, pre, mo = w["blk"][bi], self.prefixes[bi], self.layout.mod_off[bi]
             g = a["wg"]
-            wgrad(g["dt"], a["h"], pre + "mlp.2.weight")
-            wgrad(g["dt"], a["a"], pre + "attention.proj_out.weight")
+            sw.wgrad(g["dt"], a["h"], pre + "mlp.2.weight")
+            sw.wgrad(g["dt"], a["a"], pre + "attention.proj_out.weight")
             ops.mlp_swiglu_bwd(g["dt"], sh[pre + "mlp.2.weight|t"], a["m"], sh[pre + "mlp.0.weight|g"], a["u"], s["dh"], g["du"])
-            wgrad(g["du"], a["m"], pre + "mlp.0.weight")
+            sw.wgrad(g["du"], a["m"], pre + "mlp.0.weight")
             ops.gemm_nt(g["du"], sh[pre + "mlp.0.weight|t"], s["dxm"])
             ops.gemm_nt(g["dt"], sh[pre + "attention.proj_out.weight|t"], s["da"])
             dao.zero_()
@@ -463,7 +393,7 @@ class SprintJointEngine(DiTEngine):
             ops.qk_norm_rope_bwd(dq, dk, dv, a["qkv"], self.P(pre + "attention.qk_norm.query_norm.scale"),
                                  self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], g["dqkv"],
                                  self.G(pre + "attention.qk_norm.query_norm.scale"), B, T, Hh, 64, rot, pos=pos, n_off=0)
-            wgrad(g["dqkv"], a["m"], pre + "attention.qkv.weight")
+            sw.wgrad(g["dqkv"], a["m"], pre + "attention.qkv.weight")
             ops.gemm_nt(g["dqkv"], sh[pre + "attention.qkv.weight|t"], s["dxm2"], resid=s["dxm"])
             nxt = {}
             if j > 0:
@@ -474,11 +404,9 @@ class SprintJointEngine(DiTEngine):
             nx_ = s["dxb"] if dx.data_ptr() == s["dxa"].data_ptr() else s["dxa"]
             ops.ln_modulate_bwd(s["dxm2"], a["xin"], self.P(pre + "norm.weight"), self.P(pre + "norm.bias"), mod[:, mo : mo + D], T,
                                 a["mean"], a["rstd"], dx, nx_, dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], a["dwb"][0], **nxt)
-            fold_norm(a["dwb"][0], pre + "norm.weight")
+            sw.fold(a["dwb"][0], pre + "norm.weight", B)
             dx = nx_
-            getattr(wgrad, "flush", lambda: None)()  # (grouped weight gradients: whatever of this block is still pending)
-            if self.reducer is not None:
-                self.reducer.ready(*self.layer_ranges[bi], extra_events=(side.record_event(),))
+            self._end_block(sw, bi)
         return dx
 
     # ------------------------------------------------------------------ forward
@@ -566,54 +494,14 @@ class SprintJointEngine(DiTEngine):
         dfe = {kb_: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb_, g in (dfeats or {}).items()}
         mod, dmod = w["mod"], w["dmod32"]
         dmod[:B].zero_()
-        Fo8 = _rup(Fo, 8)
         sN = w[f"s_x{N}"]
 
-        ops.patchify(dpred, w["dO"], d.patch_size, ops.PATCH_PPC)
-        gl = self.G("last_layer.linear.weight")
-        if Fo == Fo8:
-            ops.gemm_tn(w["dO"], w["xf"], gl, M=Fo, N=D)
-        else:
-            w["scr_last"].zero_()
-            ops.gemm_tn(w["dO"], w["xf"], w["scr_last"], M=Fo8, N=D)
-            ops.reduce_rows_f32(w["scr_last"], gl, 1, Fo * D)
-        ops.colsum(w["dO"], self.G("last_layer.linear.bias"), M, Fo)
-        ops.gemm_nt(w["dO"], sh["last_layer.linear.weight|t"], sN["dxm"], M=M, N=D, K=self._ko)
+        self._head_bwd(dpred, sN["dxm"])
         mo = self.layout.mod_rows - 2 * D
         ops.ln_modulate_bwd(sN["dxm"], w["xdec"], None, None, mod[:, mo : mo + D], N, w["meanf"], w["rstdf"], None, w["dxdec"],
                             dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], None)
-
-        main = torch.cuda.current_stream()
-        side = self._side_stream()
-        side.wait_stream(main)
-        side_wgs = tuning.integer("DL_SIDE_WGS", 128)
-
-        def on_side(fn) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                fn()
-
-        # the linears of a block (per token stream) as ONE atomics-free launch (ops.WgradGroups) where the 384 x 192 tile divides
-        # them; the stages call wgrad.flush() at every block end
-        groups = ops.WgradGroups(w["tn_slab"], on_side, max_wgs=side_wgs) if w.get("tn_slab") is not None else None
-
-        def wgrad(x_grad: Tensor, x_in: Tensor, gname: str) -> None:
-            if groups is not None:
-                groups.add(x_grad, x_in, self.G(gname))
-            else:
-                on_side(lambda: ops.gemm_tn(x_grad, x_in, self.G(gname), max_wgs=side_wgs))
-
-        wgrad.flush = groups.flush if groups is not None else (lambda: None)
-
-        def fold_norm(partial: Tensor, gname: str) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                ops.reduce_rows_f32(partial, self.G(gname), B, 2 * D, clear=True)
-
-        hooks = (wgrad, fold_norm, side)
-        dxf, dcf = self._jstage_bwd(range(ne + nd, L), w["dxdec"], None, N, None, w["kb_f"], "f", {}, hooks)
+        sw = SideWork(self)
+        dxf, dcf = self._jstage_bwd(range(ne + nd, L), w["dxdec"], None, N, None, w["kb_f"], "f", {}, sw)
         # fuse / fuse_context (main stream: dxf / dcf are chain scratch that the next stages reuse)
         ops.gemm_tn(dxf, w["cat"], self.G("fuse.weight"))
         ops.gemm_tn(dcf, w["ccat"], self.G("fuse_context.weight"))
@@ -636,16 +524,16 @@ class SprintJointEngine(DiTEngine):
                 dlat = w["dlat"]
                 ops.copy_rows3d(gc, Lc * D, D, dlat, Td * D, D, B, Lc, D)
                 ops.copy_rows3d(gx, k * D, D, dlat[Lc:], Td * D, D, B, k, D)
-                dl = self._sstage_bwd(range(ne + nj, ne + nd), dlat, Td, route.pos_lat, w["kb_d"], hooks)
+                dl = self._sstage_bwd(range(ne + nj, ne + nd), dlat, Td, route.pos_lat, w["kb_d"], sw)
                 ops.copy_rows3d(dl[Lc:], Td * D, D, w["dxj"], k * D, D, B, k, D)
                 ops.copy_rows3d(dl, Td * D, D, w["dcj"], Lc * D, D, B, Lc, D)
                 gx, gc = w["dxj"], w["dcj"]
             if nj:
-                gx, gc = self._jstage_bwd(range(ne, ne + nj), gx, gc, k, pos_img, w["kb_d"], "d", {}, hooks)
+                gx, gc = self._jstage_bwd(range(ne, ne + nj), gx, gc, k, pos_img, w["kb_d"], "d", {}, sw)
             ops.scatter_tokens_add(gx, route.idx, w["dright"], B, N, k, D)
             ops.add_bf16(w["dcr"], gc, w["dcr"])
-        dx0, dc0 = self._jstage_bwd(range(0, ne), w["dright"], w["dcr"], N, None, w["kb_f"], "f", dfe, hooks)
-        main.wait_stream(side)
+        dx0, dc0 = self._jstage_bwd(range(0, ne), w["dright"], w["dcr"], N, None, w["kb_f"], "f", dfe, sw)
+        sw.join()
         ops.gemm_tn(dc0, w["ctxP"], self.G("context_embed.weight"), M=D, N=Cd)
         self._cond_bwd(dx0)
 
@@ -675,15 +563,11 @@ class JointStackEngine(SprintJointEngine):
         reg("context_embed.weight", self.d.inner_dim, self.d.context_dim, dgrad=False)
 
     def _alloc(self, B: int, H: int, W: int, train: bool, Lc: int = 0, k: int = 0) -> None:  # type: ignore[override]
-        d, dev = self.d, self.dev
+        d, z, zr = self.d, self._z, self._zr
         key = (B, H, W, train, Lc)
-        if key == self._ws_key:
+        if self._cached(key):
             return
-        if key in self._ws_cache:
-            self.ws, self.geo = self._ws_cache[key]
-            self._ws_key = key
-            return
-        D, E, p = d.inner_dim, d.embedding_dim, d.patch_size
+        D, p = d.inner_dim, d.patch_size
         gh, gw = H // p, W // p
         N = gh * gw
         T = Lc + N
@@ -691,21 +575,12 @@ class JointStackEngine(SprintJointEngine):
         if Tp > ops.ATTN_MAX_TOKENS or (B * N) % 64 or Lc < 1:
             raise NotImplementedError(f"joint MMDiT HIP path: context + image tokens <= {ops.ATTN_MAX_TOKENS} (got {Lc} + {N}), image tokens a "
                                       "multiple of 64")
-        M, Bp, Fo, F = B * N, _rup(B, 64), p * p * d.output_channels, d.mlp_ratio * D
+        M, F = B * N, d.mlp_ratio * D
         ops.check_row_extent(B * Tp, max(2 * F, 6 * D), "joint MMDiT HIP path")
-        bf, f32 = torch.bfloat16, torch.float32
+        f32 = torch.float32
         Hh = d.num_heads
-
-        def z(*shape, dtype=bf):
-            with torch.inference_mode(False):
-                return torch.zeros(*shape, device=dev, dtype=dtype)
-
-        def zr(rows, *rest, dtype=bf):
-            return z(_rup(rows, 64), *rest, dtype=dtype)[:rows]
-
-        w: dict[str, object] = {"tokP": z(M, self._ki), "temb": z(Bp, d.frequency_embedding), "pre1": z(Bp, E), "h1": z(Bp, E),
-                                "e": z(Bp, E, dtype=f32), "emb": z(Bp, E, dtype=f32), "se": z(Bp, E),
-                                "mod": z(Bp, self.layout.mod_rows)}
+        w: dict[str, object] = {}
+        self._cond_buffers(w, B, H, W, train, train and self._grouped_widths())
         w["ctxP"] = zr(B * Lc, _rup(d.context_dim, 64))
         w["x"] = [z(M, D)]
         w["c0"] = zr(B * Lc, D)
@@ -713,36 +588,18 @@ class JointStackEngine(SprintJointEngine):
         w["kb_f"][:, T:] = float("-inf")
         blk = []
         for _, kind in self.kinds:
-            per: dict[str, object] = {"ao": z(B * Tp, D), "lse": z(B, Hh, Tp, dtype=f32), "q": z(B, Hh, Tp, 64), "k": z(B, Hh, Tp, 64),
-                                      "v": z(B, Hh, Tp, 64)}
+            per = self._joint_attn_buffers(B, Tp)
             if kind == "J":
                 for st, nt in (("input", N), ("context", Lc)):
-                    mt = B * nt
-                    a = {"x0": zr(mt, D), "mean1": z(mt, dtype=f32), "rstd1": z(mt, dtype=f32), "xm1": zr(mt, D), "qkv": zr(mt, 3 * D),
-                         "rrms": z(mt, 2, dtype=f32), "a": zr(mt, D), "t1": zr(mt, D), "x1": zr(mt, D), "mean2": z(mt, dtype=f32),
-                         "rstd2": z(mt, dtype=f32), "xm2": zr(mt, D), "u": ops.mlp_u_buffer(zr, mt, D, F, train), "h": zr(mt, F), "t2": zr(mt, D)}
-                    if train:
-                        a["wg"] = {"dt2": zr(mt, D), "du": zr(mt, 2 * F), "dt1": zr(mt, D), "dqkv": zr(mt, 3 * D)}
-                        a["dwb"] = z(2, B, 2, D, dtype=f32)
-                    per[st] = a
+                    per[st] = self._joint_stream_buffers(B, nt, train)
             else:
-                mt = B * T
-                per.update({"x0": zr(mt, D), "mean": z(mt, dtype=f32), "rstd": z(mt, dtype=f32), "m": zr(mt, D), "qkv": zr(mt, 3 * D),
-                            "rrms": z(mt, 2, dtype=f32), "a": zr(mt, D), "ta": zr(mt, D), "u": ops.mlp_u_buffer(zr, mt, D, F, train), "h": zr(mt, F),
-                            "t": zr(mt, D)})
-                if train:
-                    per["wg"] = {"dt": zr(mt, D), "du": zr(mt, 2 * F), "dqkv": zr(mt, 3 * D)}
-                    per["dwb"] = z(1, B, 2, D, dtype=f32)
+                per.update(self._single_stream_buffers(B, T, train))
             blk.append(per)
         w["blk"] = blk
         w["xj"], w["cj"] = z(M, D), zr(B * Lc, D)
         w["lat0"], w["lat_out"] = zr(B * T, D), zr(B * T, D)
         w["xl"] = z(M, D)
-        w["meanf"], w["rstdf"], w["xf"] = z(M, dtype=f32), z(M, dtype=f32), z(M, D)
-        w["otok"] = z(M, _rup(Fo, 8), dtype=f32)
-        w["pred"] = z(B, d.output_channels, H, W, dtype=f32)
         if train:
-            w["dO"] = z(M, self._ko)
             for name, mt in ((f"x{N}", M), ("c", B * Lc), ("l", B * T)):
                 w["s_" + name] = {"dxa": zr(mt, D), "dxb": zr(mt, D), "dxm": zr(mt, D), "dxm2": zr(mt, D), "da": zr(mt, D),
                                   "dh": zr(mt, F)}
@@ -751,23 +608,8 @@ class JointStackEngine(SprintJointEngine):
             for n_ in ("dao", "dq", "dk", "dv"):  # (the single-stream stage addresses its attention scratch as "_d")
                 w[n_ + "_d"] = w[n_ + "_f"]
             w["dxl"], w["dlat"], w["dxj"], w["dcj"] = z(M, D), zr(B * T, D), z(M, D), zr(B * Lc, D)
-            w["dmod"] = z(Bp, self.layout.mod_rows)
-            w["dmod32"] = z(Bp, self.layout.mod_rows, dtype=f32)
-            w["dse"], w["demb"], w["demb16"] = z(Bp, E, dtype=f32), z(Bp, E, dtype=f32), z(Bp, E)
-            w["dh1"], w["dpre1"] = z(Bp, E, dtype=f32), z(Bp, E)
-            w["scr_last"], w["scr_conv"] = z(_rup(Fo, 8), D, dtype=f32), z(D, self._ki, dtype=f32)
-            # scratch of the bit-reproducible (and faster) small GEMMs / column sums of the conditioning backward (engine._cond_bwd)
-            w["det_scr"] = torch.empty(max(2 * self.layout.mod_rows * d.embedding_dim, 1 << 22), device=self.dev, dtype=f32)
-            if ops.WgradGroups.widths_ok(D, F) and tuning.on("DL_WGRAD_GROUP"):  # grouped weight gradients (ops.WgradGroups)
-                w["tn_slab"] = torch.empty(ops.WgradGroups.slab_floats(D, F), device=self.dev, dtype=f32)
-        self.ws, self._ws_key = w, key
-        self.geo = (B, H, W, gh, gw, N, M, Bp, Fo)
-        if len(self._ws_cache) >= 8:
-            self._ws_cache.pop(next(iter(self._ws_cache)))
-        self._ws_cache[key] = (w, self.geo)
-        if (Lc, gh, gw) not in self._rope:
-            c, s = joint_rope_tables(Lc, gh, gw, d.rope_axes_dim, d.rope_base)
-            self._rope[(Lc, gh, gw)] = (c.to(dev), s.to(dev))
+        self._publish(w, key, (B, H, W, gh, gw, N, M, _rup(B, 64), p * p * d.output_channels), (Lc, gh, gw),
+                      lambda: joint_rope_tables(Lc, gh, gw, d.rope_axes_dim, d.rope_base))
 
     def forward(self, x: Tensor, t: Tensor, y_eff: Tensor | None = None, train: bool = True, refresh: bool = True) -> Tensor:
         d = self.d
@@ -829,61 +671,21 @@ class JointStackEngine(SprintJointEngine):
         dfe = {kb_: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb_, g in (dfeats or {}).items()}
         mod, dmod = w["mod"], w["dmod32"]
         dmod[:B].zero_()
-        Fo8 = _rup(Fo, 8)
         sN = w[f"s_x{N}"]
-        ops.patchify(dpred, w["dO"], d.patch_size, ops.PATCH_PPC)
-        gl = self.G("last_layer.linear.weight")
-        if Fo == Fo8:
-            ops.gemm_tn(w["dO"], w["xf"], gl, M=Fo, N=D)
-        else:
-            w["scr_last"].zero_()
-            ops.gemm_tn(w["dO"], w["xf"], w["scr_last"], M=Fo8, N=D)
-            ops.reduce_rows_f32(w["scr_last"], gl, 1, Fo * D)
-        ops.colsum(w["dO"], self.G("last_layer.linear.bias"), M, Fo)
-        ops.gemm_nt(w["dO"], sh["last_layer.linear.weight|t"], sN["dxm"], M=M, N=D, K=self._ko)
+        self._head_bwd(dpred, sN["dxm"])
         mo = self.layout.mod_rows - 2 * D
         ops.ln_modulate_bwd(sN["dxm"], w["xl"], None, None, mod[:, mo : mo + D], N, w["meanf"], w["rstdf"], None, w["dxl"],
                             dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], None)
-
-        main = torch.cuda.current_stream()
-        side = self._side_stream()
-        side.wait_stream(main)
-        side_wgs = tuning.integer("DL_SIDE_WGS", 128)
-
-        def on_side(fn) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                fn()
-
-        # the linears of a block (per token stream) as ONE atomics-free launch (ops.WgradGroups) where the 384 x 192 tile divides
-        # them; the stages call wgrad.flush() at every block end
-        groups = ops.WgradGroups(w["tn_slab"], on_side, max_wgs=side_wgs) if w.get("tn_slab") is not None else None
-
-        def wgrad(x_grad: Tensor, x_in: Tensor, gname: str) -> None:
-            if groups is not None:
-                groups.add(x_grad, x_in, self.G(gname))
-            else:
-                on_side(lambda: ops.gemm_tn(x_grad, x_in, self.G(gname), max_wgs=side_wgs))
-
-        wgrad.flush = groups.flush if groups is not None else (lambda: None)
-
-        def fold_norm(partial: Tensor, gname: str) -> None:
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                ops.reduce_rows_f32(partial, self.G(gname), B, 2 * D, clear=True)
-
-        hooks = (wgrad, fold_norm, side)
+        sw = SideWork(self)
         dlat = w["dlat"]
         dlat.zero_()  # the context rows of the last block's output feed nothing
         ops.copy_rows3d(w["dxl"], N * D, D, dlat[Lc:], T * D, D, B, N, D)
-        dl = self._sstage_bwd(range(nj, L), dlat, T, None, w["kb_f"], hooks)
+        dl = self._sstage_bwd(range(nj, L), dlat, T, None, w["kb_f"], sw)
         ops.copy_rows3d(dl[Lc:], T * D, D, w["dxj"], N * D, D, B, N, D)
         ops.copy_rows3d(dl, T * D, D, w["dcj"], Lc * D, D, B, Lc, D)
         gx, gc = w["dxj"], w["dcj"]
         if nj:
-            gx, gc = self._jstage_bwd(range(0, nj), gx, gc, N, None, w["kb_f"], "f", dfe, hooks)
-        main.wait_stream(side)
+            gx, gc = self._jstage_bwd(range(0, nj), gx, gc, N, None, w["kb_f"], "f", dfe, sw)
+        sw.join()
         ops.gemm_tn(gc, w["ctxP"], self.G("context_embed.weight"), M=D, N=Cd)
         self._cond_bwd(gx)

@@ -137,6 +137,47 @@ def test_module_contract_and_layout():
         m(x=torch.zeros(1, 4, 32, 32), timesteps=torch.zeros(1), y=torch.zeros(1, dtype=torch.long))  # CPU: no fallback
 
 
+def _layout_cases():
+    from diffulab_amd.networks.denoisers import DDT, SprintDiT
+    from diffulab_amd.networks.embedders import PrecomputedEmbedder
+
+    emb = PrecomputedEmbedder(torch.zeros(1, 16, 96), null_embedding_seq_len=3)
+    small = dict(input_channels=4, inner_dim=128, num_heads=2, patch_size=2)
+    joint = dict(simple_dit=False, context_embedder=emb, embedding_dim=64, rope_axes_dim=[16, 24, 24], **small)
+    return {
+        "dit": lambda: MMDiT(simple_dit=True, embedding_dim=64, depth=2, n_classes=10, classifier_free=True, **small),
+        "sprint": lambda: SprintDiT(simple_dit=True, embedding_dim=64, encoder_depth=1, deep_layers_depth=2, decoder_depth=1,
+                                    n_classes=10, classifier_free=True, **small),
+        "ddt": lambda: DDT(simple_ddt=True, encoder_depth=2, decoder_depth=1, n_classes=10, classifier_free=True, **small),
+        "mmdit_joint": lambda: MMDiT(depth=2, **joint),
+        "mmdit_joint_stack": lambda: MMDiT(depth=3, n_single_stream_blocks=1, **joint),
+        "sprint_joint": lambda: SprintDiT(encoder_depth=1, deep_layers_depth=2, n_single_stream_blocks=1, decoder_depth=1, **joint),
+        "ddt_joint": lambda: DDT(encoder_depth=2, decoder_depth=1, context_embedder=emb, rope_axes_dim=[16, 24, 24], **small),
+    }
+
+
+@pytest.mark.parametrize("form", ["dit", "sprint", "ddt", "mmdit_joint", "mmdit_joint_stack", "sprint_joint", "ddt_joint"])
+def test_every_bf16_layout_matches_its_module(form):
+    """the arena layout of every bf16 engine names exactly the module's parameters, places them without overlap on 4-float
+    boundaries, and keeps the stacked adaLN matrix (and DDT's per-token one) contiguous"""
+    m = _layout_cases()[form]()
+    lay = m._make_engine(torch.device("meta")).layout
+    assert set(dict(m.named_parameters())) == set(lay.entries)
+    for name, p in m.named_parameters():
+        assert tuple(p.shape) == tuple(lay.entries[name][1]), name
+    spans = sorted((off, off + int(np.prod(shape))) for off, shape in lay.entries.values())
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), "overlapping parameters in the arena"
+    assert all(off % 4 == 0 for off, _ in lay.entries.values()) and spans[-1][1] <= lay.size and lay.size % 64 == 0
+    E = m.dims.embedding_dim
+    for w0, rows in ((lay.mod_w0, lay.mod_rows), (getattr(lay, "tmod_w0", None), getattr(lay, "tmod_rows", 0))):
+        if w0 is None:
+            continue
+        first = lay.entries[w0][0]
+        inside = sorted((off, int(np.prod(shape))) for off, shape in lay.entries.values() if first <= off < first + rows * E)
+        assert sum(n for _, n in inside) == rows * E, "adaLN matrix rows are not one contiguous block"
+        assert all(a[0] + a[1] == b[0] for a, b in zip(inside, inside[1:]))
+
+
 def test_bench_launches_its_own_ranks_without_touching_a_gpu():
     """`python bench.py --gpus N` (no external launcher): the parent spawns N children with RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* set on 127.0.0.1, never initialises the HIP runtime itself and returns the children's status."""

@@ -1,10 +1,11 @@
 """Host-side runtime of DDT with simple_ddt=True (reference networks/denoisers/ddt.py:346-464; configs/model/ddt.yaml).
 
-Encoder = a stage of DiT blocks with per-sample adaLN conditioning (the DiT engine's sequence).  Decoder = DiT blocks on a second
+Encoder = a stage of DiT blocks with per-sample adaLN conditioning (SprintEngine._stage_fwd over DiTEngine._dit_block_fwd).  Decoder = DiT blocks on a second
 patch embedding of the input whose conditioning is PER TOKEN, z = silu(encoder_output + time_embedding): the adaLN linears of all
 decoder blocks and of the last layer are stacked into ONE GEMM over the tokens ([B*N, D] x [D, 6D*depth + 2D]); the
 LayerNorm-modulate kernels read one modulation row per token (rows_per_mod = 1) and the backward writes the per-token modulation
-gradients as bf16 rows straight into the gradient matrix of that GEMM (dl_ln_modulate_bwd_tok).
+gradients as bf16 rows straight into the gradient matrix of that GEMM (dl_ln_modulate_bwd_tok).  The decoder blocks are the same
+DiTEngine._dit_block_fwd / _bwd with a per-token engine.Modulation.
 """
 
 from __future__ import annotations
@@ -15,7 +16,7 @@ import torch
 from torch import Tensor
 
 from . import ops, tuning
-from .engine import ArenaLayout, DiTDims, SideWork, _must, _rup, rope_grid_tables
+from .engine import ArenaLayout, DiTDims, Modulation, SideWork, _rup, rope_grid_tables
 from .sprint_engine import SprintEngine
 
 N_PART = 32  # partial slabs of the affine LayerNorm gradients of a per-token LayerNorm backward
@@ -71,12 +72,8 @@ class PerTokenDecoder:
     DiT-style per-block dicts ws["blk"][bi] (with "wg" and "dwbp" in training), layout.tmod_rows / tmod_w0 / tmod_b0."""
 
     def _decoder_fwd(self, first: int, nd: int, cos: Tensor, sin: Tensor) -> Tensor:
-        d, w, sh = self.d, self.ws, self.sh
-        B, _, _, _, _, N, M, _, Fo = self.geo
-        D, Hh = d.inner_dim, d.num_heads
-        rot = sum(d.rope_axes_dim)
-        train = self._train
-        ne, L = first, first + nd
+        w, sh, D = self.ws, self.sh, self.d.inner_dim
+        B, _, _, _, _, N, M, _, _ = self.geo
         # per-token conditioning of the decoder and the stacked adaLN GEMM of its blocks + last layer
         ops.ddt_cond_fwd(w["enc_out"], w["e"], B, N, w["sz"])
         R = self.layout.tmod_rows
@@ -84,126 +81,33 @@ class PerTokenDecoder:
         tm = w["tmod"]
         ops.gemm_nt(w["sz"], sh["@tmod|f"], tm, bias=tb, M=M, N=R, K=D)
         pend = None
-        for j in range(L - ne):
-            bi = ne + j
-            a, pre, mo = w["blk"][bi], self.prefixes[bi], j * 6 * D
-            n1w, n1b = self.P(pre + "norm_1.weight"), self.P(pre + "norm_1.bias")
-            if pend is None:
-                xcur = w["xdec_in"]
-                ops.ln_modulate_fwd(xcur, n1w, n1b, tm[:, mo : mo + D], tm[:, mo + D : mo + 2 * D], 1, 1e-5, a["xm1"], a["mean1"],
-                                    a["rstd1"])
-            else:
-                xcur = a["x0"]
-                ops.ln_modulate_fwd(pend[0], n1w, n1b, tm[:, mo : mo + D], tm[:, mo + D : mo + 2 * D], 1, 1e-5, a["xm1"], a["mean1"],
-                                    a["rstd1"], t=pend[1], gate=pend[2], x_out=xcur)
-            a["xin"] = xcur
-            ops.gemm_nt(a["xm1"], sh[pre + "attention.qkv.weight|f"], a["qkv"])
-            ops.qk_norm_rope_fwd(a["qkv"], self.P(pre + "attention.qk_norm.query_norm.scale"),
-                                 self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["q"], a["k"],
-                                 None if ops.v_in_place(N) else a["v"], a["rrms"], B, N, Hh,
-                                 64, rot)
-            if ops.attn_needs_padding(N):  # (multi-aspect-ratio buckets: 28 x 36, 24 x 40 ... tokens) q / k / v live in rows padded to a
-                # multiple of 256 per (sample, head); the pad keys are masked, the pad queries' outputs never copied out
-                Np = a["q"].shape[2]
-                ops.attn_fwd_ex(a["q"], a["k"], a["v"], a["ao"], a["lse"], B, Hh, Np, Np, 64, 64**-0.5, w["kb_d"])
-                ops.copy_rows3d(a["ao"], Np * D, D, a["a"], N * D, D, B, N, D)
-            elif ops.v_in_place(N):  # V read in place from the qkv rows (engine.py)
-                ops.attn_fwd_qkv(a["q"], a["k"], a["qkv"], a["a"], a["lse"], B, Hh, N, 64, 64**-0.5)
-            else:
-                ops.attn_fwd(a["q"], a["k"], a["v"], a["a"], a["lse"], B, Hh, N, 64, 64**-0.5)
-            ops.gemm_nt(a["a"], sh[pre + "attention.proj_out.weight|f"], a["t1"])
-            ops.ln_modulate_fwd(xcur, self.P(pre + "norm_2.weight"), self.P(pre + "norm_2.bias"), tm[:, mo + 3 * D : mo + 4 * D],
-                                tm[:, mo + 4 * D : mo + 5 * D], 1, 1e-5, a["xm2"], a["mean2"], a["rstd2"], t=a["t1"],
-                                gate=tm[:, mo + 2 * D : mo + 3 * D], x_out=a["x1"])
-            if not ops.gemm_nt_swiglu(a["xm2"], sh[pre + "mlp_input.0.weight|g"], a["u"] if train else None, a["h"]):
-                ops.gemm_nt(a["xm2"], sh[pre + "mlp_input.0.weight|f"], a["u"])
-                ops.swiglu_fwd(a["u"], a["h"])
-            ops.gemm_nt(a["h"], sh[pre + "mlp_input.2.weight|f"], a["t2"])
-            pend = (a["x1"], a["t2"], tm[:, mo + 5 * D : mo + 6 * D])
-        mo = (L - ne) * 6 * D
-        ops.ln_modulate_fwd(pend[0], None, None, tm[:, mo : mo + D], tm[:, mo + D : mo + 2 * D], 1, 1e-6, w["xf"], w["meanf"],
-                            w["rstdf"], t=pend[1], gate=pend[2], x_out=w["xl"])
-        ops.gemm_nt(w["xf"], sh["last_layer.linear.weight|f"], w["otok"], bias=self.P("last_layer.linear.bias"), M=M, N=Fo, K=D)
-        ops.unpatchify(w["otok"], w["pred"], d.patch_size)
-        return w["pred"]
+        for j in range(nd):
+            a = w["blk"][first + j]
+            a["xin"] = w["xdec_in"] if pend is None else a["x0"]
+            pend = self._dit_block_fwd(a, self.prefixes[first + j], a["xin"], pend, Modulation(tm, None, j * 6 * D, D, 1, tok=True), N,
+                                       cos, sin, kb=w.get("kb_d"))
+        return self._head_fwd(Modulation(tm, None, nd * 6 * D, D, 1, tok=True), w["xl"], pend)
 
     def _decoder_bwd(self, dpred: Tensor, first: int, nd: int, cos: Tensor, sin: Tensor, s: dict, sw: SideWork) -> Tensor:
         """backward of _decoder_fwd.  s: chain scratch for N tokens (dxa, dxb, dxm, da, dh, dq, dk, dv); returns the gradient of
         ws["enc_out"] (ws["denc"]); ws["dtemb"] receives the decoder's gradient of the time embedding"""
-        d, w, sh = self.d, self.ws, self.sh
-        B, _, _, _, _, N, M, _, Fo = self.geo
-        D, Hh = d.inner_dim, d.num_heads
-        rot = sum(d.rope_axes_dim)
-        ne, L = first, first + nd
+        w, sh, D = self.ws, self.sh, self.d.inner_dim
+        B, _, _, _, _, N, M, _, _ = self.geo
         tm, dtm = w["tmod"], w["dtmod"]
-        inplace_qk = ops.qk_inplace_ok(w, B, N)
         self._head_bwd(dpred, s["dxm"])
-        mo = nd * 6 * D
-        ml = (nd - 1) * 6 * D
-        al = w["blk"][L - 1]
-        dx, dx_alt = s["dxa"], s["dxb"]
-        ops.ln_modulate_bwd_tok(s["dxm"], w["xl"], None, None, tm[:, mo : mo + D], w["meanf"], w["rstdf"], None, dx,
-                                dtm[:, mo : mo + D], dtm[:, mo + D : mo + 2 * D], None, gate_t=al["t2"],
-                                gate=tm[:, ml + 5 * D : ml + 6 * D], dt=al["wg"]["dt2"], dgate=dtm[:, ml + 5 * D : ml + 6 * D])
-
+        al = w["blk"][first + nd - 1]
+        dx = s["dxa"]
+        Modulation(tm, dtm, nd * 6 * D, D, 1, tok=True).ln_bwd(s["dxm"], w["xl"], None, None, 0, w["meanf"], w["rstdf"], None, dx, None,
+                                                               gate=(al["t2"], (nd - 1) * 6 * D + 5 * D, al["wg"]["dt2"]))
         for j in reversed(range(nd)):
-            bi = ne + j
-            a, pre, mo = w["blk"][bi], self.prefixes[bi], j * 6 * D
-            g = a["wg"]
-            sw.wgrad(g["dt2"], a["h"], pre + "mlp_input.2.weight")
-            ops.mlp_swiglu_bwd(g["dt2"], sh[pre + "mlp_input.2.weight|t"], a["xm2"], sh[pre + "mlp_input.0.weight|g"], a["u"], s["dh"], g["du"])
-            sw.wgrad(g["du"], a["xm2"], pre + "mlp_input.0.weight")
-            ops.gemm_nt(g["du"], sh[pre + "mlp_input.0.weight|t"], s["dxm"])
-            ops.ln_modulate_bwd_tok(s["dxm"], a["x1"], self.P(pre + "norm_2.weight"), self.P(pre + "norm_2.bias"),
-                                    tm[:, mo + 3 * D : mo + 4 * D], a["mean2"], a["rstd2"], dx, dx_alt, dtm[:, mo + 3 * D : mo + 4 * D],
-                                    dtm[:, mo + 4 * D : mo + 5 * D], a["dwbp"][1], gate_t=a["t1"], gate=tm[:, mo + 2 * D : mo + 3 * D],
-                                    dt=g["dt1"], dgate=dtm[:, mo + 2 * D : mo + 3 * D])
-            sw.fold(a["dwbp"][1], pre + "norm_2.weight", N_PART)
-            dx, dx_alt = dx_alt, dx
-            sw.wgrad(g["dt1"], a["a"], pre + "attention.proj_out.weight")
-            ops.gemm_nt(g["dt1"], sh[pre + "attention.proj_out.weight|t"], s["da"])
-            if inplace_qk:  # dQ, dK, dV token-major into dqkv; the QK-norm backward transforms the q / k thirds in place
-                ops.attn_bwd_tok(a["q"], a["k"], a["qkv"], a["a"], s["da"], a["lse"], g["dqkv"], B, Hh, N, 64, 64**-0.5)
-                _must(ops.qk_norm_rope_bwd_inplace(a["qkv"], self.P(pre + "attention.qk_norm.query_norm.scale"),
-                                                    self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], g["dqkv"],
-                                                    self.G(pre + "attention.qk_norm.query_norm.scale"), w["qk_part"], B, N, Hh, 64, rot))
-            else:
-                if ops.attn_needs_padding(N):
-                    Np = a["q"].shape[2]
-                    ops.copy_rows3d(s["da"], N * D, D, w["dao_d"], Np * D, D, B, N, D)  # (the pad rows of dao_d stay zero)
-                    ops.attn_bwd_ex(a["q"], a["k"], a["v"], a["ao"], w["dao_d"], a["lse"], s["dq"], s["dk"], s["dv"], B, Hh, Np, Np, 64,
-                                    64**-0.5, w["kb_d"])
-                elif ops.v_in_place(N):
-                    ops.attn_bwd_qkv(a["q"], a["k"], a["qkv"], a["a"], s["da"], a["lse"], s["dq"], s["dk"], g["dqkv"], B, Hh, N, 64,
-                                     64**-0.5)
-                else:
-                    ops.attn_bwd(a["q"], a["k"], a["v"], a["a"], s["da"], a["lse"], s["dq"], s["dk"], s["dv"], B, Hh, N, 64, 64**-0.5)
-                ops.qk_norm_rope_bwd(s["dq"], s["dk"], None if ops.v_in_place(N) else s["dv"], a["qkv"],
-                                     self.P(pre + "attention.qk_norm.query_norm.scale"),
-                                     self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], g["dqkv"],
-                                     self.G(pre + "attention.qk_norm.query_norm.scale"), B, N, Hh, 64, rot)
-            sw.wgrad(g["dqkv"], a["xm1"], pre + "attention.qkv.weight")
-            ops.gemm_nt(g["dqkv"], sh[pre + "attention.qkv.weight|t"], s["dxm"])
-            nxt = {}
-            if j > 0:
-                mp = (j - 1) * 6 * D
-                ap = w["blk"][bi - 1]
-                nxt = dict(gate_t=ap["t2"], gate=tm[:, mp + 5 * D : mp + 6 * D], dt=ap["wg"]["dt2"], dgate=dtm[:, mp + 5 * D : mp + 6 * D])
-            ops.ln_modulate_bwd_tok(s["dxm"], a["xin"], self.P(pre + "norm_1.weight"), self.P(pre + "norm_1.bias"), tm[:, mo : mo + D],
-                                    a["mean1"], a["rstd1"], dx, dx_alt, dtm[:, mo : mo + D], dtm[:, mo + D : mo + 2 * D], a["dwbp"][0],
-                                    **nxt)
-            sw.fold(a["dwbp"][0], pre + "norm_1.weight", N_PART)
-            dx, dx_alt = dx_alt, dx
+            bi = first + j
+            a = w["blk"][bi]
+            prev = (w["blk"][bi - 1]["t2"], (j - 1) * 6 * D + 5 * D, w["blk"][bi - 1]["wg"]["dt2"]) if j > 0 else None
+            m = Modulation(tm, dtm, j * 6 * D, D, 1, tok=True, part=a["dwbp"], groups=N_PART)
+            dx = self._dit_block_bwd(a, a["wg"], self.prefixes[bi], a["xin"], dx, prev, None, s, m, N, cos, sin, sw, kb=w.get("kb_d"),
+                                     dao=w.get("dao_d"))
             self._end_block(sw, bi)
-        # decoder patch embedding
-        Fi = d.input_channels * d.patch_size**2
-        gc = self.G("conv_proj_decoder.weight").view(D, Fi)
-        if Fi % 8 == 0:
-            ops.gemm_tn(dx, w["tokP"], gc, M=D, N=Fi)
-        else:
-            w["scr_conv"].zero_()
-            ops.gemm_tn(dx, w["tokP"], w["scr_conv"], M=D, N=_rup(Fi, 8))
-            gc.add_(w["scr_conv"][:, :Fi])
+        self._patch_wgrad(dx, "conv_proj_decoder.weight", None)  # decoder patch embedding (the atomic form: no scratch)
         # stacked per-token adaLN GEMM: weight / bias gradients and the gradient of its input silu(z)
         R = self.layout.tmod_rows
         gw_ = self.grads[self.layout.entries[self.layout.tmod_w0][0] :][: R * D].view(R, D)
@@ -288,10 +192,9 @@ class DDTEngine(SprintEngine, PerTokenDecoder):
             self.refresh_shadows(force=train)
         w, sh = self.ws, self.sh
         _, _, _, gh, gw, N, M, Bp, Fo = self.geo
-        D, L, Hh = d.inner_dim, d.depth, d.num_heads
+        D, L = d.inner_dim, d.depth
         ne = d.encoder_depth
         cos, sin = self._rope[(gh, gw)]
-        rot = sum(d.rope_axes_dim)
         self._train, self._yeff = train, y_eff
         self._stem_fwd(x, t, y_eff)
         ops.gemm_nt(w["tokP"], sh["conv_proj_decoder.weight|f"], w["xdec_in"], M=M, N=D, K=self._ki)
@@ -310,10 +213,9 @@ class DDTEngine(SprintEngine, PerTokenDecoder):
     def backward(self, dpred: Tensor, dfeats: dict[int, Tensor] | None = None) -> None:
         assert self._train and self.grads is not None
         d, w = self.d, self.ws
-        B, H, W, gh, gw, N, M, Bp, Fo = self.geo
-        D, L = d.inner_dim, d.depth
-        ne = d.encoder_depth
-        dfe = {kb: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb, g in (dfeats or {}).items()}
+        B, _, _, gh, gw, N, _, _, _ = self.geo
+        L, ne = d.depth, d.encoder_depth
+        dfe = self._dfeat_rows(dfeats)
         cos, sin = self._rope[(gh, gw)]
         w["dmod32"][:B].zero_()
         sw = SideWork(self)
@@ -386,7 +288,7 @@ class DDTJointLayout(ArenaLayout):
 
 class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
     """DDT(simple_ddt=False) (ddt.py:274-344 + 404-464): joint text-image encoder stage (the MMDiTBlock sequence of
-    sprint_joint_engine.py; the context half of its last block feeds nothing), then the per-token-conditioned DDT decoder on the
+    DiTEngine._jstage_fwd; the context half of its last block feeds nothing), then the per-token-conditioned DDT decoder on the
     image rows of the 3-axis RoPE table"""
 
     _conv_name = "conv_proj_encoder.weight"
@@ -516,12 +418,12 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
         d, w = self.d, self.ws
         B, H, W, gh, gw, N, M, Bp, Fo = self.geo
         D, Cd, ne, Lc = d.inner_dim, d.context_dim, d.encoder_depth, self._Lc
-        dfe = {kb_: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb_, g in (dfeats or {}).items()}
+        dfe = self._dfeat_rows(dfeats)
         cos, sin = self._tabs
         w["dmod32"][:B].zero_()
         sw = SideWork(self)
         denc = self._decoder_bwd(dpred, ne, d.decoder_depth, cos[Lc:], sin[Lc:], w[f"s_x{N}"], sw)
-        dx0, dc0 = self._jstage_bwd(range(0, ne), denc, None, N, None, w["kb_f"], "f", dfe, sw)
+        dx0, dc0 = self._jstage_bwd(range(0, ne), denc, None, N, None, w["kb_f"], *self._jscratch(N, "f"), dfe, sw)
         sw.join()
         ops.gemm_tn(dc0, w["ctxP"], self.G("context_embed.weight"), M=D, N=Cd)
         self._cond_bwd(dx0, extra_demb=w["dtemb"])

@@ -10,12 +10,18 @@ MI355X-first choices:
     allocation and the launch sequence is static (hipGraph-capturable);
   * residual stream and GEMM operands are bf16, accumulation / norm statistics / gradients of parameters f32.
 
+One owner per launch sequence: the Python-issued DiT block (_dit_block_fwd / _dit_block_bwd, built from the halves _half1_* /
+_half2_* and the attention pair _attn_fwd / _attn_bwd) serves DiTEngine's plain path, the SPRINT / DDT stages and the DDT decoder;
+the joint (MMDiT) block stage (_jstage_fwd / _jstage_bwd) runs the same halves per token stream and serves every engine with joint
+blocks.  What differs between callers is data: buffers, parameter names (block_names) and the adaLN rows in force (Modulation).
+
 Reference sites restated by the sequences below: mmdit.py:853-928 (simple_dit_forward / forward),
 mmdit.py:288-309 (DiTBlock), mmdit.py:75-104 (DiTAttention), mmdit.py:542-549 (ModulatedLastLayer).
 """
 
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass, field
 
@@ -48,6 +54,62 @@ def _rup(x: int, m: int) -> int:
 STREAMS = ("input", "context")  # the two token streams of a joint (MMDiT) block: image, text
 ROW_MAX_DIM = 4096  # widest token row of the bf16 regime's row kernels (csrc/norm.hip: one wave per row up to 1024, one workgroup above)
 F32_MAX_DIM = 1024  # widest token row of the fp32 regime (csrc/f32.hip, one wave per row)
+
+
+@functools.lru_cache(maxsize=None)
+def block_names(pre: str, st: str | None = None) -> dict[str, str]:
+    """parameter name stems of the DiT block `pre` (st None) or of token stream `st` of the joint block `pre`: the two block kinds
+    run the same sub-layer sequence (DiTEngine._half1_fwd ...) under different names"""
+    if st is None:
+        n = dict(n1="norm_1", n2="norm_2", qk="attention.qk_norm", qkv="attention.qkv", proj="attention.proj_out", up="mlp_input.0",
+                 down="mlp_input.2")
+    else:
+        n = dict(n1=f"{st}_norm_1", n2=f"{st}_norm_2", qk=f"attention.qk_norm_{st}", qkv=f"attention.qkv_{st}",
+                 proj=f"attention.{st}_proj_out", up=f"mlp_{st}.0", down=f"mlp_{st}.2")
+    return {k: pre + v for k, v in n.items()}
+
+
+@dataclass(slots=True)
+class Modulation:
+    """the six adaLN chunks (scale1, shift1, gate1, scale2, shift2, gate2) a block's two LayerNorms and gated residuals read -- or
+    the two of the final LayerNorm -- as columns [off, off + 6D) of `mat`.  Per sample (`rows` tokens share a row of mat, gradients
+    accumulate into the f32 `dmat`, the LayerNorm-affine partials `part` [2, groups, 2, D] hold one group per sample) or per token
+    (DDT decoder: rows = 1, tok selects dl_ln_modulate_bwd_tok, which writes bf16 gradient rows into dmat and a fixed number of partial groups)"""
+    mat: Tensor
+    dmat: Tensor | None   # None: forward only
+    off: int
+    D: int
+    rows: int
+    tok: bool = False
+    part: Tensor | tuple | None = None   # part[0]: norm_1, part[1]: norm_2
+    groups: int = 0
+
+    def col(self, c: int) -> Tensor:
+        o = self.off + c * self.D
+        return self.mat[:, o : o + self.D]
+
+    def ln_bwd(self, dout: Tensor, x: Tensor, lnw: Tensor | None, lnb: Tensor | None, c: int, mean: Tensor, rstd: Tensor,
+               dres: Tensor | None, dx: Tensor, part: Tensor | None, gate: tuple | None = None) -> None:
+        """backward of the LayerNorm-modulate on chunks c (scale), c + 1 (shift): dx = dres + its data gradient.  Every
+        LayerNorm-modulate backward also runs the backward of the gated residual that follows it in the chain (x_new = x + gate * t):
+        it has the residual-stream gradient dx in registers, so dt = gate * dx and dgate += dx * t cost one extra row read / write
+        instead of a separate pass over dx.  gate = (t, column of that gate in mat, dt) or None"""
+        D, o, mat, dmat = self.D, self.off + c * self.D, self.mat, self.dmat
+        kw = {}
+        if gate is not None:
+            t, go, dt = gate
+            kw = dict(gate_t=t, gate=mat[:, go : go + D], dt=dt, dgate=dmat[:, go : go + D])
+        if self.tok:
+            ops.ln_modulate_bwd_tok(dout, x, lnw, lnb, mat[:, o : o + D], mean, rstd, dres, dx, dmat[:, o : o + D],
+                                    dmat[:, o + D : o + 2 * D], part, **kw)
+        else:
+            ops.ln_modulate_bwd(dout, x, lnw, lnb, mat[:, o : o + D], self.rows, mean, rstd, dres, dx, dmat[:, o : o + D],
+                                dmat[:, o + D : o + 2 * D], part, **kw)
+
+
+def _other(s: dict, cur: Tensor | None) -> Tensor:
+    """ping-pong target of the next LayerNorm backward in the chain scratch s (never the buffer it reads)"""
+    return s["dxb"] if (cur is not None and cur.data_ptr() == s["dxa"].data_ptr()) else s["dxa"]
 
 
 @dataclass
@@ -631,10 +693,9 @@ class DiTEngine:
         if refresh:  # (False while a hipGraph of this forward is being captured: the replay path refreshes eagerly)
             self.refresh_shadows(force=train)  # a training forward always follows a parameter update
         w, sh = self.ws, self.sh
-        _, _, _, gh, gw, N, M, Bp, Fo = self.geo
-        D, E, L, Hh = d.inner_dim, d.embedding_dim, d.depth, d.num_heads
+        _, _, _, gh, gw, N, M, _, _ = self.geo
+        D, L = d.inner_dim, d.depth
         cos, sin = self._rope[(gh, gw)]
-        rot = sum(d.rope_axes_dim)
         self._train = train
         self._yeff = y_eff
 
@@ -653,66 +714,155 @@ class DiTEngine:
                     ops.dit_block_fwd(self._block_args(i, train), train)
             else:
                 self._forward_row_gemms(mod, train)
-            ops.gemm_nt(w["xf"], sh["last_layer.linear.weight|f"], w["otok"], bias=self.P("last_layer.linear.bias"), M=M,
-                        N=Fo, K=D)
-            ops.unpatchify(w["otok"], w["pred"], d.patch_size)
-            return w["pred"]
+            return self._head_fwd(None, w["xf"])
 
-        # The gated residual of every sub-layer (x += gate * f(...)) is applied by the NEXT LayerNorm-modulate kernel, which
-        # has to read the residual stream anyway: the projection / MLP-down GEMMs stay plain stores (fast 256x384 tiles)
-        # and write t1 / t2, which the backward needs for the gate gradients.
-        pend = None  # (x_base, t, gate) of the sub-layer whose residual add is still pending
+        pend = None  # (x_base, t, gate) of the sub-layer whose residual add is still pending (_half1_fwd)
         native = self._native_blocks()
         for i in range(L):
+            a = w["layers"][i if train else 0]
             if native:
                 ops.dit_block_fwd(self._block_args(i, train), train)
-                a = w["layers"][i if train else 0]
                 pend = (a["x1"], a["t2"], mod[:, i * 6 * D + 5 * D : i * 6 * D + 6 * D])
                 continue
-            a = w["layers"][i if train else 0]
-            xin = xs[i] if train else xs[i & 1]
-            pre = f"layers.{i}."
-            mo = i * 6 * D
-            if pend is None:
-                ops.ln_modulate_fwd(xin, self.P(pre + "norm_1.weight"), self.P(pre + "norm_1.bias"), mod[:, mo : mo + D],
-                                    mod[:, mo + D : mo + 2 * D], N, 1e-5, a["xm1"], a["mean1"], a["rstd1"])
-            else:
-                ops.ln_modulate_fwd(pend[0], self.P(pre + "norm_1.weight"), self.P(pre + "norm_1.bias"), mod[:, mo : mo + D],
-                                    mod[:, mo + D : mo + 2 * D], N, 1e-5, a["xm1"], a["mean1"], a["rstd1"], t=pend[1],
-                                    gate=pend[2], x_out=xin)
-            ops.gemm_nt(a["xm1"], sh[pre + "attention.qkv.weight|f"], a["qkv"])
-            # up to 256 tokens the attention kernels address V (and dV) inside the token-major qkv (dqkv) rows: no V head split
-            v_in_place = ops.v_in_place(N)
-            ops.qk_norm_rope_fwd(a["qkv"], self.P(pre + "attention.qk_norm.query_norm.scale"),
-                                 self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["q"], a["k"],
-                                 None if v_in_place else a["v"], a["rrms"], B, N, Hh, 64, rot)
-            if a.get("ao") is not None:  # padded rows, masked pad keys (_alloc)
-                Np = a["q"].shape[2]
-                ops.attn_fwd_ex(a["q"], a["k"], a["v"], a["ao"], a["lse"], B, Hh, Np, Np, 64, 64**-0.5, w["kb"])
-                ops.copy_rows3d(a["ao"], Np * D, D, a["a"], N * D, D, B, N, D)
-            elif v_in_place:
-                ops.attn_fwd_qkv(a["q"], a["k"], a["qkv"], a["a"], a["lse"], B, Hh, N, 64, 64**-0.5)
-            else:
-                ops.attn_fwd(a["q"], a["k"], a["v"], a["a"], a["lse"], B, Hh, N, 64, 64**-0.5)
-            ops.gemm_nt(a["a"], sh[pre + "attention.proj_out.weight|f"], a["t1"])
-            ops.ln_modulate_fwd(xin, self.P(pre + "norm_2.weight"), self.P(pre + "norm_2.bias"),
-                                mod[:, mo + 3 * D : mo + 4 * D], mod[:, mo + 4 * D : mo + 5 * D], N, 1e-5, a["xm2"],
-                                a["mean2"], a["rstd2"], t=a["t1"], gate=mod[:, mo + 2 * D : mo + 3 * D], x_out=a["x1"])
-            if not ops.gemm_nt_swiglu(a["xm2"], sh[pre + "mlp_input.0.weight|g"], a["u"] if train else None, a["h"]):
-                assert a["u"] is not None, "the recompute mode is only chosen for shapes the fused MLP-up kernel serves"
-                ops.gemm_nt(a["xm2"], sh[pre + "mlp_input.0.weight|f"], a["u"])  # small / ragged shapes: unfused pair
-                ops.swiglu_fwd(a["u"], a["h"])
-            ops.gemm_nt(a["h"], sh[pre + "mlp_input.2.weight|f"], a["t2"])
-            pend = (a["x1"], a["t2"], mod[:, mo + 5 * D : mo + 6 * D])
+            pend = self._dit_block_fwd(a, f"layers.{i}.", xs[i] if train else xs[i & 1], pend, Modulation(mod, None, i * 6 * D, D, N), N,
+                                       cos, sin, kb=w.get("kb"))
+        return self._head_fwd(Modulation(mod, None, L * 6 * D, D, N), xs[L] if train else xs[L & 1], pend)
 
-        xl = xs[L] if train else xs[L & 1]
-        mo = L * 6 * D
-        ops.ln_modulate_fwd(pend[0], None, None, mod[:, mo : mo + D], mod[:, mo + D : mo + 2 * D], N, 1e-6, w["xf"], w["meanf"],
-                            w["rstdf"], t=pend[1], gate=pend[2], x_out=xl)
-        ops.gemm_nt(w["xf"], sh["last_layer.linear.weight|f"], w["otok"], bias=self.P("last_layer.linear.bias"), M=M,
-                    N=Fo, K=D)
-        ops.unpatchify(w["otok"], w["pred"], d.patch_size)
+    # ------------------------------------------------------------------ block launch sequences (every bf16 transformer engine)
+    def _half1_fwd(self, a: dict, nm: dict, xin: Tensor, pend: tuple | None, m: Modulation, nt: int, cos: Tensor, sin: Tensor,
+                   q: Tensor, k: Tensor, v: Tensor | None, pos: Tensor | None = None, n_off: int = 0) -> None:
+        """first half of a DiT block, or of one token stream of a joint block (nm: block_names), over nt tokens per sample:
+        LayerNorm-modulate -> qkv GEMM -> QK-norm + RoPE + head split into rows [n_off, n_off + nt) of q / k / v.
+        The gated residual of every sub-layer (x += gate * f(...)) is applied by the NEXT LayerNorm-modulate kernel, which has to read
+        the residual stream anyway: the projection / MLP-down GEMMs stay plain stores (fast 256x384 tiles) and write t1 / t2, which
+        the backward needs for the gate gradients.  pend = (x_base, t, gate) of that pending add (its sum is written to xin), or
+        None: xin holds the block input"""
+        n1w, n1b = self.P(nm["n1"] + ".weight"), self.P(nm["n1"] + ".bias")
+        if pend is None:
+            ops.ln_modulate_fwd(xin, n1w, n1b, m.col(0), m.col(1), m.rows, 1e-5, a["xm1"], a["mean1"], a["rstd1"])
+        else:
+            ops.ln_modulate_fwd(pend[0], n1w, n1b, m.col(0), m.col(1), m.rows, 1e-5, a["xm1"], a["mean1"], a["rstd1"], t=pend[1],
+                                gate=pend[2], x_out=xin)
+        ops.gemm_nt(a["xm1"], self.sh[nm["qkv"] + ".weight|f"], a["qkv"])
+        ops.qk_norm_rope_fwd(a["qkv"], self.P(nm["qk"] + ".query_norm.scale"), self.P(nm["qk"] + ".key_norm.scale"), cos, sin, q, k, v,
+                             a["rrms"], self.geo[0], nt, self.d.num_heads, 64, sum(self.d.rope_axes_dim), pos=pos, n_off=n_off)
+
+    def _half2_fwd(self, a: dict, nm: dict, xin: Tensor, m: Modulation) -> tuple:
+        """second half: attention output a["a"] -> projection -> LayerNorm-modulate (with the gated residual of the attention branch,
+        x1 = xin + gate1 * t1) -> SwiGLU MLP.  Returns the pending residual (x1, t2, gate2) for the next LayerNorm"""
+        sh = self.sh
+        ops.gemm_nt(a["a"], sh[nm["proj"] + ".weight|f"], a["t1"])
+        ops.ln_modulate_fwd(xin, self.P(nm["n2"] + ".weight"), self.P(nm["n2"] + ".bias"), m.col(3), m.col(4), m.rows, 1e-5, a["xm2"],
+                            a["mean2"], a["rstd2"], t=a["t1"], gate=m.col(2), x_out=a["x1"])
+        if not ops.gemm_nt_swiglu(a["xm2"], sh[nm["up"] + ".weight|g"], a["u"] if self._train else None, a["h"]):
+            assert a["u"] is not None, "the recompute mode is only chosen for shapes the fused MLP-up kernel serves"
+            ops.gemm_nt(a["xm2"], sh[nm["up"] + ".weight|f"], a["u"])  # small / ragged shapes: unfused pair
+            ops.swiglu_fwd(a["u"], a["h"])
+        ops.gemm_nt(a["h"], sh[nm["down"] + ".weight|f"], a["t2"])
+        return a["x1"], a["t2"], m.col(5)
+
+    def _attn_fwd(self, a: dict, nt: int, kb: Tensor | None) -> None:
+        """self-attention of a DiT block over nt tokens per sample, in the form the block has buffers for"""
+        B, Hh, D = self.geo[0], self.d.num_heads, self.d.inner_dim
+        if a.get("ao") is not None:  # token grids the kernels do not take as they are (multi-aspect-ratio buckets: 28 x 36, 24 x 40
+            # ...): q / k / v live in rows padded to a multiple of 256 per (sample, head); the pad keys are masked through the key
+            # bias kb, the pad queries' outputs never copied out
+            Np = a["q"].shape[2]
+            ops.attn_fwd_ex(a["q"], a["k"], a["v"], a["ao"], a["lse"], B, Hh, Np, Np, 64, 64**-0.5, kb)
+            ops.copy_rows3d(a["ao"], Np * D, D, a["a"], nt * D, D, B, nt, D)
+        elif ops.v_in_place(nt):  # up to 256 tokens the kernels address V (and dV) inside the token-major qkv (dqkv) rows
+            ops.attn_fwd_qkv(a["q"], a["k"], a["qkv"], a["a"], a["lse"], B, Hh, nt, 64, 64**-0.5)
+        else:
+            ops.attn_fwd(a["q"], a["k"], a["v"], a["a"], a["lse"], B, Hh, nt, 64, 64**-0.5)
+
+    def _dit_block_fwd(self, a: dict, pre: str, xin: Tensor, pend: tuple | None, m: Modulation, nt: int, cos: Tensor, sin: Tensor,
+                       pos: Tensor | None = None, kb: Tensor | None = None) -> tuple:
+        """one adaLN-zero DiT block `pre` issued from Python on the buffers a; pos: RoPE table row of every token (None: its index in
+        the sequence); kb: key bias of the padded attention.  Returns the pending residual of its MLP branch"""
+        nm = block_names(pre)
+        self._half1_fwd(a, nm, xin, pend, m, nt, cos, sin, a["q"], a["k"], None if ops.v_in_place(nt) else a["v"], pos)
+        self._attn_fwd(a, nt, kb)
+        return self._half2_fwd(a, nm, xin, m)
+
+    def _head_fwd(self, m: Modulation | None, x: Tensor, pend: tuple | None = None) -> Tensor:
+        """final LayerNorm-modulate of x (pend: of the pending residual, whose sum is written to x; m None: ws["xf"] is already
+        there) -> last linear -> unpatchify.  Returns ws["pred"]"""
+        w = self.ws
+        M, Fo = self.geo[6], self.geo[8]
+        if m is not None and pend is None:
+            ops.ln_modulate_fwd(x, None, None, m.col(0), m.col(1), m.rows, 1e-6, w["xf"], w["meanf"], w["rstdf"])
+        elif m is not None:
+            ops.ln_modulate_fwd(pend[0], None, None, m.col(0), m.col(1), m.rows, 1e-6, w["xf"], w["meanf"], w["rstdf"], t=pend[1],
+                                gate=pend[2], x_out=x)
+        ops.gemm_nt(w["xf"], self.sh["last_layer.linear.weight|f"], w["otok"], bias=self.P("last_layer.linear.bias"), M=M, N=Fo,
+                    K=self.d.inner_dim)
+        ops.unpatchify(w["otok"], w["pred"], self.d.patch_size)
         return w["pred"]
+
+    def _half2_bwd(self, a: dict, g: dict, nm: dict, s: dict, m: Modulation, dx: Tensor | None, sw: "SideWork") -> Tensor:
+        """backward of _half2_fwd.  g: the block's inputs of the weight-gradient GEMMs (g["dt2"] was produced by the LayerNorm
+        backward before this one in the chain); s: chain scratch; dx: residual-stream gradient (None: zero so far).  Leaves the
+        gradient of the attention output in s["da"] and returns the residual-stream gradient at x1's input"""
+        sh = self.sh
+        sw.wgrad(g["dt2"], a["h"], nm["down"] + ".weight")
+        ops.mlp_swiglu_bwd(g["dt2"], sh[nm["down"] + ".weight|t"], a["xm2"], sh[nm["up"] + ".weight|g"], a["u"], s["dh"], g["du"])
+        sw.wgrad(g["du"], a["xm2"], nm["up"] + ".weight")
+        ops.gemm_nt(g["du"], sh[nm["up"] + ".weight|t"], s["dxm"])
+        nx = _other(s, dx)
+        m.ln_bwd(s["dxm"], a["x1"], self.P(nm["n2"] + ".weight"), self.P(nm["n2"] + ".bias"), 3, a["mean2"], a["rstd2"], dx, nx,
+                 m.part[1], gate=(a["t1"], m.off + 2 * m.D, g["dt1"]))
+        sw.fold(m.part[1], nm["n2"] + ".weight", m.groups)
+        sw.wgrad(g["dt1"], a["a"], nm["proj"] + ".weight")
+        ops.gemm_nt(g["dt1"], sh[nm["proj"] + ".weight|t"], s["da"])
+        return nx
+
+    def _half1_bwd(self, a: dict, g: dict, nm: dict, s: dict, m: Modulation, xin: Tensor, dx: Tensor | None, prev: tuple | None,
+                   dres: Tensor | None, sw: "SideWork") -> Tensor:
+        """backward of _half1_fwd from g["dqkv"] on.  xin: the block input; prev = (t2, column of gate2, dt2) of the block before in
+        the chain, whose gated residual this LayerNorm absorbed (None: none did); dres: auxiliary-loss gradient on that block's
+        output (= this block's input).  Returns the residual-stream gradient at the block input"""
+        sw.wgrad(g["dqkv"], a["xm1"], nm["qkv"] + ".weight")
+        ops.gemm_nt(g["dqkv"], self.sh[nm["qkv"] + ".weight|t"], s["dxm"])
+        if dres is not None and dx is not None:
+            ops.add_bf16(dx, dres, dx)
+        nx = _other(s, dx)
+        m.ln_bwd(s["dxm"], xin, self.P(nm["n1"] + ".weight"), self.P(nm["n1"] + ".bias"), 0, a["mean1"], a["rstd1"], dx, nx, m.part[0],
+                 gate=prev)
+        sw.fold(m.part[0], nm["n1"] + ".weight", m.groups)
+        return nx
+
+    def _attn_bwd(self, a: dict, g: dict, nm: dict, s: dict, nt: int, cos: Tensor, sin: Tensor, pos: Tensor | None,
+                  kb: Tensor | None, dao: Tensor | None) -> None:
+        """s["da"] -> g["dqkv"]: backward of _attn_fwd and of QK-norm + RoPE.  dao: padded copy of da (padded attention)"""
+        w = self.ws
+        B, Hh, D, rot = self.geo[0], self.d.num_heads, self.d.inner_dim, sum(self.d.rope_axes_dim)
+        sq, sk = self.P(nm["qk"] + ".query_norm.scale"), self.P(nm["qk"] + ".key_norm.scale")
+        dscale = self.G(nm["qk"] + ".query_norm.scale")
+        if ops.qk_inplace_ok(w, B, nt):  # dQ, dK, dV token-major into dqkv; the QK-norm backward transforms the q / k thirds in place
+            ops.attn_bwd_tok(a["q"], a["k"], a["qkv"], a["a"], s["da"], a["lse"], g["dqkv"], B, Hh, nt, 64, 64**-0.5)
+            _must(ops.qk_norm_rope_bwd_inplace(a["qkv"], sq, sk, cos, sin, a["rrms"], g["dqkv"], dscale, w["qk_part"], B, nt, Hh, 64, rot,
+                                                pos=pos))
+            return
+        v_in_place = ops.v_in_place(nt)
+        if a.get("ao") is not None:
+            Np = a["q"].shape[2]
+            ops.copy_rows3d(s["da"], nt * D, D, dao, Np * D, D, B, nt, D)  # (the pad rows of dao stay zero)
+            ops.attn_bwd_ex(a["q"], a["k"], a["v"], a["ao"], dao, a["lse"], s["dq"], s["dk"], s["dv"], B, Hh, Np, Np, 64, 64**-0.5, kb)
+        elif v_in_place:  # dV goes straight into the v third of dqkv
+            ops.attn_bwd_qkv(a["q"], a["k"], a["qkv"], a["a"], s["da"], a["lse"], s["dq"], s["dk"], g["dqkv"], B, Hh, nt, 64, 64**-0.5)
+        else:
+            ops.attn_bwd(a["q"], a["k"], a["v"], a["a"], s["da"], a["lse"], s["dq"], s["dk"], s["dv"], B, Hh, nt, 64, 64**-0.5)
+        ops.qk_norm_rope_bwd(s["dq"], s["dk"], None if v_in_place else s["dv"], a["qkv"], sq, sk, cos, sin, a["rrms"], g["dqkv"], dscale,
+                             B, nt, Hh, 64, rot, pos=pos)
+
+    def _dit_block_bwd(self, a: dict, g: dict, pre: str, xin: Tensor, dx: Tensor, prev: tuple | None, dres: Tensor | None, s: dict,
+                       m: Modulation, nt: int, cos: Tensor, sin: Tensor, sw: "SideWork", pos: Tensor | None = None,
+                       kb: Tensor | None = None, dao: Tensor | None = None) -> Tensor:
+        """backward of _dit_block_fwd (arguments as in the halves): dx at the block output -> returned dx at the block input"""
+        nm = block_names(pre)
+        dx = self._half2_bwd(a, g, nm, s, m, dx, sw)
+        self._attn_bwd(a, g, nm, s, nt, cos, sin, pos, kb, dao)
+        return self._half1_bwd(a, g, nm, s, m, xin, dx, prev, dres, sw)
 
     def _grouped_wgrad(self, M: int) -> bool:
         """the four weight gradients of a block as ONE launch without atomics (csrc/gemm_w4.hip, dl_gemm_tn_group): every linear of
@@ -783,6 +933,101 @@ class DiTEngine:
                                             mod[:, mn : mn + D], mod[:, mn + D : mn + 2 * D], N, eps, a["t2"], xbuf(i + 1), xm_n, mu_n,
                                             rs_n))
 
+    # ------------------------------------------------------------------ joint (MMDiT) block stage
+    def _jstage_fwd(self, blocks, x_in: Tensor, c_in: Tensor, nx: int, pos: Tensor | None, kb: Tensor, x_out: Tensor | None,
+                    c_out: Tensor | None) -> tuple | None:
+        """MMDiTBlocks `blocks` on (image stream x_in [B*nx, D], context stream c_in [B*Lc, D]) of an engine with joint blocks
+        (self._Lc context tokens, self._tabs the joint RoPE tables, layout.mod_off the blocks' modulation columns).  Each stream
+        runs the DiT halves with its own weights and its own six modulation chunks; the streams meet in ONE attention launch over
+        the joint q / k / v rows ([0, Lc) context, [Lc, Lc + nx) image) with the key-padding mask as the additive key bias kb.
+        Outputs materialised into x_out / c_out (rows may be strided); c_out None: the context half of the last block feeds nothing
+        and is skipped; x_out None: the pending residual of the image stream is returned for the caller's next LayerNorm"""
+        d, w = self.d, self.ws
+        B, Lc = self.geo[0], self._Lc
+        D, Hh = d.inner_dim, d.num_heads
+        cos, sin = self._tabs
+        mod = w["mod"]
+        Tp = kb.shape[1]
+        streams = (("input", nx, Lc, 0, pos), ("context", Lc, 0, 6 * D, None))
+        cur = {"input": x_in, "context": c_in}
+        pend: dict[str, tuple | None] = {"input": None, "context": None}
+        blocks = list(blocks)
+        for bi in blocks:
+            per, pre, base = w["blk"][bi], self.prefixes[bi], self.layout.mod_off[bi]
+            q, k, v = (per["q"], per["k"], per["v"]) if "q" in per else (w["q"], w["k"], w["v"])  # (inference may share one set)
+            for st, nt, off, mc, ps in streams:
+                a = per[st]
+                a["xin"] = cur[st] if pend[st] is None else a["x0"]
+                self._half1_fwd(a, block_names(pre, st), a["xin"], pend[st], Modulation(mod, None, base + mc, D, nt), nt, cos[off:],
+                                sin[off:], q, k, v, ps, off)
+            ops.attn_fwd_ex(q, k, v, per["ao"], per["lse"], B, Hh, Tp, Tp, 64, 64**-0.5, kb)
+            for st, nt, off, mc, ps in streams:
+                if st == "context" and c_out is None and bi == blocks[-1]:  # (the reference computes and discards it)
+                    continue
+                a = per[st]
+                ops.copy_rows3d(per["ao"][off:], Tp * D, D, a["a"], nt * D, D, B, nt, D)
+                pend[st] = self._half2_fwd(a, block_names(pre, st), a["xin"], Modulation(mod, None, base + mc, D, nt))
+        if x_out is None:
+            return pend["input"]
+        ops.gated_residual_fwd(*pend["input"], nx, x_out)
+        if c_out is not None:
+            ops.gated_residual_fwd(*pend["context"], Lc, c_out)
+        return None
+
+    def _jstage_bwd(self, blocks, dx_x: Tensor, dx_c: Tensor | None, nx: int, pos: Tensor | None, kb: Tensor, scr: dict, att: tuple,
+                    dfe: dict, sw: "SideWork", pending: bool = False):
+        """backward of _jstage_fwd.  dx_x / dx_c: gradients at the stage outputs (contiguous, overwritten; dx_c None: the context output
+        was not produced); scr: chain scratch of each stream; att: (dao, dq, dk, dv) over the padded joint rows; pending: the image
+        output was handed on as a pending residual, whose backward the caller's LayerNorm backward has run (dfe of the last block
+        included).  Returns the gradients at the stage inputs (image, context)."""
+        d, w = self.d, self.ws
+        B, Lc = self.geo[0], self._Lc
+        D, Hh = d.inner_dim, d.num_heads
+        cos, sin = self._tabs
+        rot = sum(d.rope_axes_dim)
+        mod, dmod = w["mod"], w["dmod32"]
+        Tp = kb.shape[1]
+        streams = (("input", nx, Lc, 0, pos), ("context", Lc, 0, 6 * D, None))
+        dao, dq, dk, dv = att
+        blocks = list(blocks)
+        last = blocks[-1]
+        dx: dict[str, Tensor | None] = {"input": dx_x, "context": dx_c}  # residual-stream gradients (None: zero so far)
+        if not pending:
+            if last in dfe:
+                ops.add_bf16(dx_x, dfe[last], dx_x)
+            for st, nt, off, mc, ps in streams:  # backward of the materialised last residual of each stream
+                if dx[st] is None:
+                    continue
+                a, mo = w["blk"][last][st], self.layout.mod_off[last] + mc
+                ops.gate_bwd(dx[st], a["t2"], mod[:, mo + 5 * D : mo + 6 * D], nt, a["wg"]["dt2"], dmod[:, mo + 5 * D : mo + 6 * D])
+        skip_ctx_last = dx_c is None
+        for j in reversed(range(len(blocks))):
+            bi = blocks[j]
+            per, pre = w["blk"][bi], self.prefixes[bi]
+            ms = {st: Modulation(mod, dmod, self.layout.mod_off[bi] + mc, D, nt, part=per[st]["dwb"], groups=B) for st, nt, _, mc, _ in streams}
+            dao.zero_()
+            for st, nt, off, mc, ps in streams:
+                if st == "context" and skip_ctx_last and bi == last:
+                    continue
+                a, s = per[st], scr[st]
+                dx[st] = self._half2_bwd(a, a["wg"], block_names(pre, st), s, ms[st], dx[st], sw)
+                ops.copy_rows3d(s["da"], nt * D, D, dao[off:], Tp * D, D, B, nt, D)
+            ops.attn_bwd_ex(per["q"], per["k"], per["v"], per["ao"], dao, per["lse"], dq, dk, dv, B, Hh, Tp, Tp, 64, 64**-0.5, kb)
+            for st, nt, off, mc, ps in streams:
+                a, nm = per[st], block_names(pre, st)
+                ops.qk_norm_rope_bwd(dq, dk, dv, a["qkv"], self.P(nm["qk"] + ".query_norm.scale"), self.P(nm["qk"] + ".key_norm.scale"),
+                                     cos[off:], sin[off:], a["rrms"], a["wg"]["dqkv"], self.G(nm["qk"] + ".query_norm.scale"), B, nt, Hh,
+                                     64, rot, pos=ps, n_off=off)
+                prev = dres = None
+                if j > 0:
+                    bp = blocks[j - 1]
+                    ap = w["blk"][bp][st]
+                    prev = (ap["t2"], self.layout.mod_off[bp] + mc + 5 * D, ap["wg"]["dt2"])
+                    dres = dfe.get(bp) if st == "input" else None
+                dx[st] = self._half1_bwd(a, a["wg"], nm, scr[st], ms[st], a["xin"], dx[st], prev, dres, sw)
+            self._end_block(sw, bi)
+        return dx["input"], dx["context"]
+
     # ------------------------------------------------------------------ backward
     def feature(self, k: int) -> Tensor:
         """output of block k of the last train-mode forward: the residual stream after the block, bf16 [B, N, D] (a view of
@@ -795,25 +1040,20 @@ class DiTEngine:
         """accumulates d(loss)/d(param) into the flat gradient arena (+=) for the last train-mode forward.
         dfeats: {block index k: gradient of an auxiliary loss w.r.t. feature(k)} (RePA), added to the residual-stream gradient."""
         assert self._train and self.grads is not None
-        dfeats = {k: g.reshape(-1, self.d.inner_dim).to(torch.bfloat16).contiguous() for k, g in (dfeats or {}).items()}
+        dfeats = self._dfeat_rows(dfeats)
         d, w, sh = self.d, self.ws, self.sh
-        B, H, W, gh, gw, N, M, Bp, Fo = self.geo
-        D, E, L, Hh = d.inner_dim, d.embedding_dim, d.depth, d.num_heads
-        F = d.mlp_ratio * D
+        B, _, _, gh, gw, N, M, _, _ = self.geo
+        D, E, L = d.inner_dim, d.embedding_dim, d.depth
         cos, sin = self._rope[(gh, gw)]
-        rot = sum(d.rope_axes_dim)
         mod, dmod, xs = w["mod"], w["dmod32"], w["x"]  # dmod: f32 accumulator, cast to bf16 (w["dmod"]) after the loop
         dmod[:B].zero_()
+        s = {k: w[k] for k in ("dxa", "dxb", "dxm", "da", "dh", "dq", "dk", "dv")}  # chain scratch
 
-        # head: last linear + final adaLN
+        # head: last linear + final adaLN, which runs the gated residual backward of the last block's MLP branch
         fused = self._row_gemms(M, N)
         self._head_bwd(dpred, None if fused else w["dxm"], scratch=w["det_scr"])
-        mo = L * 6 * D
-        dx, dx_alt = w["dxa"], w["dxb"]
-        # every LayerNorm-modulate backward also runs the backward of the gated residual that follows it in the chain
-        # (x_new = x + gate * t): it has the residual-stream gradient dx in registers, so dt = gate * dx and dgate += dx * t
-        # cost one extra row read / write instead of a separate pass over dx
-        ml = (L - 1) * 6 * D
+        mo, ml = L * 6 * D, (L - 1) * 6 * D
+        dx = w["dxa"]
         if fused:  # (row-complete GEMMs: the LayerNorm backward is the epilogue of the data-gradient GEMM in front of it)
             _must(ops.ln_modulate_gemm_bwd(w["dO"], sh["last_layer.linear.weight|t"], xs[L], None, None, mod[:, mo : mo + D], N,
                                             w["meanf"], w["rstdf"], dfeats.get(L - 1), dx, dmod[:, mo : mo + D],
@@ -821,61 +1061,18 @@ class DiTEngine:
                                             gate=mod[:, ml + 5 * D : ml + 6 * D], dt=w["wg"][L - 1]["dt2"],
                                             dgate=dmod[:, ml + 5 * D : ml + 6 * D], K=self._ko))
         else:
-            ops.ln_modulate_bwd(w["dxm"], xs[L], None, None, mod[:, mo : mo + D], N, w["meanf"], w["rstdf"], dfeats.get(L - 1), dx,
-                                dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], None, gate_t=w["layers"][L - 1]["t2"],
-                                gate=mod[:, ml + 5 * D : ml + 6 * D], dt=w["wg"][L - 1]["dt2"],
-                                dgate=dmod[:, ml + 5 * D : ml + 6 * D])
+            Modulation(mod, dmod, mo, D, N).ln_bwd(w["dxm"], xs[L], None, None, 0, w["meanf"], w["rstdf"], dfeats.get(L - 1), dx, None,
+                                                   gate=(w["layers"][L - 1]["t2"], ml + 5 * D, w["wg"][L - 1]["dt2"]))
 
-        # The four weight-gradient GEMMs of a block are off the dependency chain (nothing downstream reads them), so they
-        # run on a SIDE HIP stream: they overlap the HBM-bound kernels of the main chain (gate/SwiGLU/adaLN/QK-norm
-        # backward), which leave the matrix pipes idle.  Their inputs (dt2, du, dt1, dqkv) live in per-block buffers so the
-        # main chain never overwrites something the side stream still reads.
-        main = torch.cuda.current_stream()
-        side = self._side_stream()
-        side.wait_stream(main)
-
-        # workgroup cap of the side-stream weight gradients (of 256 CUs).  Four atomic launches per block: 96: 24.5, 128: 24.1, 160:
+        # Workgroup cap of the side-stream weight gradients (of 256 CUs).  Four atomic launches per block: 96: 24.5, 128: 24.1, 160:
         # 24.4, 192: 24.8, 256: 25.8 ms/step (round 2).  The grouped launch (one per block, no atomics) wants the whole chip: every
         # kernel of the step is then one workgroup per CU and the two streams simply take turns (64: 23.8, 96: 22.4, 128: 22.3,
-        # 192: 22.1, 256: 21.7 ms/step; the same launches inline on the main stream: 21.9)
-        side_wgs = tuning.integer("DL_SIDE_WGS", 256 if w.get("tn_slab") is not None else 128)
-
-        serial = tuning.on("DL_WGRAD_SERIAL")  # A/B switch: weight gradients inline on the main stream
-
-        tn_slab = w.get("tn_slab")
-        pending: list[tuple[Tensor, Tensor, Tensor]] = []  # (dy, x, g) of the current block, launched together once dqkv exists
-
-        def wgrad(x_grad: Tensor, x_in: Tensor, gname: str) -> None:
-            if tn_slab is not None:
-                pending.append((x_grad, x_in, self.G(gname)))
-                return
-            if serial:
-                ops.gemm_tn(x_grad, x_in, self.G(gname))
-                return
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                ops.gemm_tn(x_grad, x_in, self.G(gname), max_wgs=side_wgs)
-
-        def wgrad_flush() -> None:  # the block's four weight gradients: one atomics-free launch + fold (dl_gemm_tn_group)
-            if not pending:
-                return
-            if serial:
-                _must(ops.gemm_tn_group(pending, tn_slab))
-            else:
-                ev = main.record_event()
-                with torch.cuda.stream(side):
-                    side.wait_event(ev)
-                    _must(ops.gemm_tn_group(pending, tn_slab, max_wgs=side_wgs))
-            pending.clear()
-
-        def fold_norm(partial: Tensor, gname: str) -> None:  # [B, 2, D] per-sample sums -> [w; b] gradients, off the chain
-            if defer_fold:
-                return
-            ev = main.record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                ops.reduce_rows_f32(partial, self.G(gname), B, 2 * D, clear=True)
+        # 192: 22.1, 256: 21.7 ms/step; the same launches inline on the main stream: 21.9).  strict: a grouped launch that declines
+        # raises instead of falling back to atomics (the B = 256 step is bit-reproducible).  DL_WGRAD_SERIAL is the A/B switch to
+        # weight gradients inline on the main stream
+        serial = tuning.on("DL_WGRAD_SERIAL")
+        sw = SideWork(self, grouped_wgs=256, serial=serial, strict=True)
+        main, side = sw.main, sw.side
 
         # Data parallel: the stacked adaLN matrix (L*6D x E, a quarter of the parameters) would only be final in _cond_bwd, i.e. its
         # 42 MB would be reduced after the backward has ended.  Every block's 6D rows of the modulation gradient are final when that
@@ -886,116 +1083,46 @@ class DiTEngine:
         self._early_mod_done = early_mod
         w_mod = self.layout.entries[self.mod_name][0]
         b_mod = self.layout.entries[self.layout.mod_b0][0]
-        E = d.embedding_dim
 
-        def block_done(i: int) -> None:
+        def early_mod_rows(r0: int, r1: int) -> None:
+            ops.cast2d_f32_to_bf16(w["dmod32"][:B, r0:r1], w["dmod"][:B, r0:r1])
+            ops.gemm_tn(w["dmod"][:, r0:r1], w["se"], self.grads[w_mod + r0 * E : w_mod + r1 * E].view(r1 - r0, E))
+            ops.colsum(w["dmod"][:, r0:r1], self.grads[b_mod + r0 : b_mod + r1], B, r1 - r0)
+
+        def block_done(i: int) -> None:  # this block's gradient range is final once BOTH streams are past this point
             if self.reducer is None:
                 return
             if early_mod:
-                r0, r1 = i * 6 * D, (i + 1) * 6 * D
-                ev = main.record_event()
-                with torch.cuda.stream(side):
-                    side.wait_event(ev)
-                    ops.cast2d_f32_to_bf16(w["dmod32"][:B, r0:r1], w["dmod"][:B, r0:r1])
-                    ops.gemm_tn(w["dmod"][:, r0:r1], w["se"], self.grads[w_mod + r0 * E : w_mod + r1 * E].view(r1 - r0, E))
-                    ops.colsum(w["dmod"][:, r0:r1], self.grads[b_mod + r0 : b_mod + r1], B, r1 - r0)
+                sw.run(lambda: early_mod_rows(i * 6 * D, (i + 1) * 6 * D))
             ev_side = side.record_event()
             self.reducer.ready(*self.layer_ranges[i], extra_events=(ev_side,))
             if early_mod:
                 self.reducer.ready(w_mod + i * 6 * D * E, w_mod + (i + 1) * 6 * D * E, flush=i < 3)
 
-        native = self._native_blocks() and not serial and dx is w["dxa"]
+        native = self._native_blocks() and not serial
         inline_wgrad = tuning.on("DL_WGRAD_INLINE")  # TUNING: the grouped weight gradients on the main stream
         defer_fold = fused and self.reducer is None  # LayerNorm-affine partials of every block: one batched fold after the loop
         for i in reversed(range(L)):
+            dres = dfeats.get(i - 1)  # auxiliary-loss gradient on the output of block i-1 (= this block's input)
             if native:
                 blk = self._block_args(i, True)
-                blk.set(dfeat=dfeats.get(i - 1))
-                ops.dit_block_bwd(blk, main.cuda_stream, main.cuda_stream if inline_wgrad else side.cuda_stream, side_wgs)
-                block_done(i)
-                continue
-            a = w["layers"][i]
-            g = w["wg"][i]
-            pre = f"layers.{i}."
-            mo = i * 6 * D
-            # MLP branch
-            wgrad(g["dt2"], a["h"], pre + "mlp_input.2.weight")  # dt2 / dgate: produced by the LayerNorm backward before
-            if a["u"] is None:  # no saved pre-activations: the u tile is recomputed next to the dh tile, neither is written
-                _must(ops.mlp_dswiglu_recompute(a["xm2"], sh[pre + "mlp_input.0.weight|g"], g["dt2"], sh[pre + "mlp_input.2.weight|t"],
-                                                 g["du"]))
+                blk.set(dfeat=dres)
+                ops.dit_block_bwd(blk, main.cuda_stream, main.cuda_stream if inline_wgrad else side.cuda_stream, sw.side_wgs)
+            elif fused:
+                dx = self._block_bwd_row_gemms(i, dx, dres, s, sw, not defer_fold)
             else:
-                ops.gemm_nt(g["dt2"], sh[pre + "mlp_input.2.weight|t"], w["dh"])
-                ops.swiglu_bwd(w["dh"], a["u"], g["du"])
-            wgrad(g["du"], a["xm2"], pre + "mlp_input.0.weight")
-            if fused:
-                _must(ops.ln_modulate_gemm_bwd(g["du"], sh[pre + "mlp_input.0.weight|t"], a["x1"], self.P(pre + "norm_2.weight"),
-                                                self.P(pre + "norm_2.bias"), mod[:, mo + 3 * D : mo + 4 * D], N, a["mean2"], a["rstd2"],
-                                                dx, dx_alt, dmod[:, mo + 3 * D : mo + 4 * D], dmod[:, mo + 4 * D : mo + 5 * D],
-                                                w["dwb"][2 * i + 1], gate_t=a["t1"], gate=mod[:, mo + 2 * D : mo + 3 * D], dt=g["dt1"],
-                                                dgate=dmod[:, mo + 2 * D : mo + 3 * D]))
-            else:
-                ops.gemm_nt(g["du"], sh[pre + "mlp_input.0.weight|t"], w["dxm"])
-                ops.ln_modulate_bwd(w["dxm"], a["x1"], self.P(pre + "norm_2.weight"), self.P(pre + "norm_2.bias"),
-                                    mod[:, mo + 3 * D : mo + 4 * D], N, a["mean2"], a["rstd2"], dx, dx_alt,
-                                    dmod[:, mo + 3 * D : mo + 4 * D], dmod[:, mo + 4 * D : mo + 5 * D], w["dwb"][2 * i + 1],
-                                    gate_t=a["t1"], gate=mod[:, mo + 2 * D : mo + 3 * D], dt=g["dt1"],
-                                    dgate=dmod[:, mo + 2 * D : mo + 3 * D])
-            fold_norm(w["dwb"][2 * i + 1], pre + "norm_2.weight")
-            dx, dx_alt = dx_alt, dx
-            # attention branch
-            wgrad(g["dt1"], a["a"], pre + "attention.proj_out.weight")
-            ops.gemm_nt(g["dt1"], sh[pre + "attention.proj_out.weight|t"], w["da"])
-            v_in_place = ops.v_in_place(N)
-            if w.get("qk_part") is not None:  # dQ, dK, dV token-major into dqkv; the QK-norm backward transforms q / k in place
-                ops.attn_bwd_tok(a["q"], a["k"], a["qkv"], a["a"], w["da"], a["lse"], g["dqkv"], B, Hh, N, 64, 64**-0.5)
-                _must(ops.qk_norm_rope_bwd_inplace(a["qkv"], self.P(pre + "attention.qk_norm.query_norm.scale"),
-                                                    self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], g["dqkv"],
-                                                    self.G(pre + "attention.qk_norm.query_norm.scale"), w["qk_part"], B, N, Hh, 64, rot))
-            else:
-                if a.get("ao") is not None:
-                    Np = a["q"].shape[2]
-                    ops.copy_rows3d(w["da"], N * D, D, w["dao"], Np * D, D, B, N, D)  # (the pad rows of dao stay zero)
-                    ops.attn_bwd_ex(a["q"], a["k"], a["v"], a["ao"], w["dao"], a["lse"], w["dq"], w["dk"], w["dv"], B, Hh, Np, Np, 64,
-                                    64**-0.5, w["kb"])
-                elif v_in_place:  # dV goes straight into the v third of dqkv
-                    ops.attn_bwd_qkv(a["q"], a["k"], a["qkv"], a["a"], w["da"], a["lse"], w["dq"], w["dk"], g["dqkv"], B, Hh, N, 64,
-                                     64**-0.5)
-                else:
-                    ops.attn_bwd(a["q"], a["k"], a["v"], a["a"], w["da"], a["lse"], w["dq"], w["dk"], w["dv"], B, Hh, N, 64,
-                                 64**-0.5)
-                ops.qk_norm_rope_bwd(w["dq"], w["dk"], None if v_in_place else w["dv"], a["qkv"],
-                                     self.P(pre + "attention.qk_norm.query_norm.scale"),
-                                     self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], g["dqkv"],
-                                     self.G(pre + "attention.qk_norm.query_norm.scale"), B, N, Hh, 64, rot)
-            wgrad(g["dqkv"], a["xm1"], pre + "attention.qkv.weight")
-            wgrad_flush()
-            if not fused:
-                ops.gemm_nt(g["dqkv"], sh[pre + "attention.qkv.weight|t"], w["dxm"])
-            if i - 1 in dfeats:  # auxiliary-loss gradient on the output of block i-1 (= this block's input)
-                ops.add_bf16(dx, dfeats[i - 1], dx)
-            nxt = {}
-            if i > 0:  # gated residual of the previous block's MLP branch
-                mp = (i - 1) * 6 * D
-                nxt = dict(gate_t=w["layers"][i - 1]["t2"], gate=mod[:, mp + 5 * D : mp + 6 * D], dt=w["wg"][i - 1]["dt2"],
-                           dgate=dmod[:, mp + 5 * D : mp + 6 * D])
-            if fused:
-                _must(ops.ln_modulate_gemm_bwd(g["dqkv"], sh[pre + "attention.qkv.weight|t"], xs[i], self.P(pre + "norm_1.weight"),
-                                                self.P(pre + "norm_1.bias"), mod[:, mo : mo + D], N, a["mean1"], a["rstd1"], dx, dx_alt,
-                                                dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], w["dwb"][2 * i], **nxt))
-            else:
-                ops.ln_modulate_bwd(w["dxm"], xs[i], self.P(pre + "norm_1.weight"), self.P(pre + "norm_1.bias"),
-                                    mod[:, mo : mo + D], N, a["mean1"], a["rstd1"], dx, dx_alt, dmod[:, mo : mo + D],
-                                    dmod[:, mo + D : mo + 2 * D], w["dwb"][2 * i], **nxt)
-            fold_norm(w["dwb"][2 * i], pre + "norm_1.weight")
-            dx, dx_alt = dx_alt, dx
-            block_done(i)  # this block's gradient range is final once BOTH streams are past this point
+                prev = (w["layers"][i - 1]["t2"], (i - 1) * 6 * D + 5 * D, w["wg"][i - 1]["dt2"]) if i > 0 else None
+                m = Modulation(mod, dmod, i * 6 * D, D, N, part=(w["dwb"][2 * i], w["dwb"][2 * i + 1]), groups=B)
+                dx = self._dit_block_bwd(w["layers"][i], w["wg"][i], f"layers.{i}.", xs[i], dx, prev, dres, s, m, N, cos, sin, sw,
+                                         kb=w.get("kb"), dao=w.get("dao"))
+            block_done(i)
         # Without a gradient reducer nothing reads the weight gradients before the optimizer, so the join with the side stream comes
         # LAST: the LayerNorm-affine fold and the conditioning backward (~0.3 ms of small main-stream kernels) run under the grouped
         # weight-gradient launch of the first block instead of behind it.  (Data parallel: _cond_bwd ends in reducer.finish(), which
         # must see every range final -- the join stays in front.)
         join_last = self.reducer is None and tuning.on("DL_JOIN_LAST")
         if not join_last:
-            main.wait_stream(side)
+            sw.join()
         if defer_fold:  # dwb [2L, B, 2, D]: rows 2i -> norm_1 of block i, 2i + 1 -> norm_2; [w; b] of a norm are adjacent in the arena
             ent = self.layout.entries
             stride = ent[self.prefixes[1] + "norm_1.weight"][0] - ent[self.prefixes[0] + "norm_1.weight"][0] if L > 1 else 0
@@ -1004,7 +1131,47 @@ class DiTEngine:
 
         self._cond_bwd(dx)
         if join_last:
-            main.wait_stream(side)
+            sw.join()
+
+    def _block_bwd_row_gemms(self, i: int, dx: Tensor, dres: Tensor | None, s: dict, sw: "SideWork", fold: bool) -> Tensor:
+        """backward of block i of _forward_row_gemms: the sequence of _dit_block_bwd with each LayerNorm-modulate backward as the
+        epilogue of the data-gradient GEMM in front of it (dl_ln_modulate_gemm_bwd).  fold False: the LayerNorm-affine partials stay
+        in ws["dwb"] for the caller's batched fold"""
+        d, w, sh = self.d, self.ws, self.sh
+        _, _, _, gh, gw, N, _, _, _ = self.geo
+        D = d.inner_dim
+        mod, dmod = w["mod"], w["dmod32"]
+        a, g, nm, mo = w["layers"][i], w["wg"][i], block_names(f"layers.{i}."), i * 6 * D
+        sw.wgrad(g["dt2"], a["h"], nm["down"] + ".weight")
+        ops.mlp_swiglu_bwd(g["dt2"], sh[nm["down"] + ".weight|t"], a["xm2"], sh[nm["up"] + ".weight|g"], a["u"], s["dh"], g["du"])
+        sw.wgrad(g["du"], a["xm2"], nm["up"] + ".weight")
+        nx = _other(s, dx)
+        _must(ops.ln_modulate_gemm_bwd(g["du"], sh[nm["up"] + ".weight|t"], a["x1"], self.P(nm["n2"] + ".weight"),
+                                        self.P(nm["n2"] + ".bias"), mod[:, mo + 3 * D : mo + 4 * D], N, a["mean2"], a["rstd2"], dx, nx,
+                                        dmod[:, mo + 3 * D : mo + 4 * D], dmod[:, mo + 4 * D : mo + 5 * D], w["dwb"][2 * i + 1],
+                                        gate_t=a["t1"], gate=mod[:, mo + 2 * D : mo + 3 * D], dt=g["dt1"],
+                                        dgate=dmod[:, mo + 2 * D : mo + 3 * D]))
+        if fold:
+            sw.fold(w["dwb"][2 * i + 1], nm["n2"] + ".weight", self.geo[0])
+        dx = nx
+        sw.wgrad(g["dt1"], a["a"], nm["proj"] + ".weight")
+        ops.gemm_nt(g["dt1"], sh[nm["proj"] + ".weight|t"], s["da"])
+        self._attn_bwd(a, g, nm, s, N, *self._rope[(gh, gw)], None, None, None)
+        sw.wgrad(g["dqkv"], a["xm1"], nm["qkv"] + ".weight")
+        if dres is not None:
+            ops.add_bf16(dx, dres, dx)
+        nxt = {}
+        if i > 0:  # gated residual of the previous block's MLP branch
+            mp = (i - 1) * 6 * D
+            nxt = dict(gate_t=w["layers"][i - 1]["t2"], gate=mod[:, mp + 5 * D : mp + 6 * D], dt=w["wg"][i - 1]["dt2"],
+                       dgate=dmod[:, mp + 5 * D : mp + 6 * D])
+        nx = _other(s, dx)
+        _must(ops.ln_modulate_gemm_bwd(g["dqkv"], sh[nm["qkv"] + ".weight|t"], w["x"][i], self.P(nm["n1"] + ".weight"),
+                                        self.P(nm["n1"] + ".bias"), mod[:, mo : mo + D], N, a["mean1"], a["rstd1"], dx, nx,
+                                        dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], w["dwb"][2 * i], **nxt))
+        if fold:
+            sw.fold(w["dwb"][2 * i], nm["n1"] + ".weight", self.geo[0])
+        return nx
 
     def _head_bwd(self, dpred: Tensor, dxm: Tensor | None, scratch: Tensor | None = None) -> None:
         """backward of the last linear: dpred patchified into ws["dO"], its weight gradient (through an f32 slab padded to 8 rows
@@ -1024,6 +1191,23 @@ class DiTEngine:
         if dxm is not None:
             ops.gemm_nt(w["dO"], self.sh["last_layer.linear.weight|t"], dxm, M=M, N=D, K=self._ko)
 
+    def _dfeat_rows(self, dfeats: dict[int, Tensor] | None) -> dict[int, Tensor]:
+        """the auxiliary-loss gradients {block index: d(loss)/d(feature(k))} as contiguous bf16 token rows [B*N, D]"""
+        return {k: g.reshape(-1, self.d.inner_dim).to(torch.bfloat16).contiguous() for k, g in (dfeats or {}).items()}
+
+    def _patch_wgrad(self, dx: Tensor, name: str, scratch: Tensor | None) -> None:
+        """weight gradient of the patch-embedding convolution `name` from the gradient dx of its tokens (through an f32 slab padded
+        to 8 columns when the patch features are ragged); scratch: the bit-reproducible form of the GEMM (ops.gemm_tn)"""
+        d, w = self.d, self.ws
+        D, Fi = d.inner_dim, d.input_channels * d.patch_size**2
+        gc = self.G(name).view(D, Fi)
+        if Fi % 8 == 0:
+            ops.gemm_tn(dx, w["tokP"], gc, M=D, N=Fi, scratch=scratch)
+        else:
+            w["scr_conv"].zero_()
+            ops.gemm_tn(dx, w["tokP"], w["scr_conv"], M=D, N=_rup(Fi, 8), scratch=scratch)
+            gc.add_(w["scr_conv"][:, :Fi])  # ragged edge (e.g. RGB p=2 -> 12 features): torch slice-add, not on the hot path
+
     def _end_block(self, sw: "SideWork", bi: int) -> None:
         """end of block bi's backward in a staged engine: its pending weight gradients are issued and, data parallel, its gradient
         range is handed to the reducer behind the side stream's work so far"""
@@ -1039,15 +1223,7 @@ class DiTEngine:
         D, E = d.inner_dim, d.embedding_dim
         dmod = w["dmod32"]
         det = w.get("det_scr")  # scratch of the bit-reproducible small GEMMs / column sums (None: the atomic forms)
-        # stem: conv_proj weight gradient (no gradient flows to the input latents)
-        Fi = d.input_channels * d.patch_size**2
-        gc = self.G(self._conv_name).view(D, Fi)
-        if Fi % 8 == 0:
-            ops.gemm_tn(dx, w["tokP"], gc, M=D, N=Fi, scratch=det)
-        else:
-            w["scr_conv"].zero_()
-            ops.gemm_tn(dx, w["tokP"], w["scr_conv"], M=D, N=_rup(Fi, 8), scratch=det)
-            gc.add_(w["scr_conv"][:, :Fi])  # ragged edge (e.g. RGB p=2 -> 12 features): torch slice-add, not on the hot path
+        self._patch_wgrad(dx, self._conv_name, det)  # (no gradient flows to the input latents)
 
         # conditioning path: every adaLN linear at once, then the time MLP and the label table
         R = self.layout.mod_rows
@@ -1087,21 +1263,36 @@ class DiTEngine:
             self.reducer.finish()
 
 
+class _StrictWgradGroups(ops.WgradGroups):
+    """WgradGroups for a backward that must stay free of atomics: a grouped launch that declines its problems raises"""
+
+    def _issue(self, key: int) -> None:
+        probs = self.pending.pop(key, [])
+        if probs:
+            self.launch(lambda: _must(ops.gemm_tn_group(probs, self.slab, max_wgs=self.max_wgs)))
+
+
 class SideWork:
-    """the side-stream half of a staged engine's backward (SPRINT, MMDiT, DDT and their joint forms).  The weight gradients and the
-    LayerNorm-affine folds are off the dependency chain, so they run on a side stream, each launch behind an event recorded on the main
-    stream when it is issued.  The linears of a block (per token stream) are collected and issued as ONE atomics-free
-    dl_gemm_tn_group launch where the workspace has a grouped-launch slab (ops.WgradGroups), else as one atomic launch each.
+    """the side-stream half of a bf16 transformer engine's backward.  The four weight-gradient GEMMs of a block and the
+    LayerNorm-affine folds are off the dependency chain (nothing downstream reads them), so they run on a SIDE HIP stream, each launch
+    behind an event recorded on the main stream when it is issued: they overlap the HBM-bound kernels of the main chain (gate / SwiGLU
+    / adaLN / QK-norm backward), which leave the matrix pipes idle.  Their inputs (dt2, du, dt1, dqkv) live in per-block buffers so
+    the main chain never overwrites something the side stream still reads.  The linears of a block (per token stream) are collected
+    and issued as ONE atomics-free dl_gemm_tn_group launch where the workspace has a grouped-launch slab (ops.WgradGroups), else as
+    one atomic launch each.  grouped_wgs: default workgroup cap with the slab; serial: the weight gradients (not the folds) run
+    inline on the main stream, uncapped; strict: see _StrictWgradGroups.
     Built where the backward begins to issue side work: the side stream waits for everything the main stream has issued so far."""
 
-    def __init__(self, eng: DiTEngine) -> None:
+    def __init__(self, eng: DiTEngine, grouped_wgs: int = 128, serial: bool = False, strict: bool = False) -> None:
         self.G, self.width = eng.G, 2 * eng.d.inner_dim
         self.main = torch.cuda.current_stream()
         self.side = eng._side_stream()
         self.side.wait_stream(self.main)
-        self.side_wgs = tuning.integer("DL_SIDE_WGS", 128)  # workgroup cap of the side-stream launches (of 256 CUs)
         slab = eng.ws.get("tn_slab")
-        self.groups = ops.WgradGroups(slab, self.run, max_wgs=self.side_wgs) if slab is not None else None
+        self.side_wgs = tuning.integer("DL_SIDE_WGS", grouped_wgs if slab is not None else 128)  # cap of the side-stream launches (of 256 CUs)
+        self.wgs, self.launch = (0, lambda fn: fn()) if serial else (self.side_wgs, self.run)
+        groups = _StrictWgradGroups if strict else ops.WgradGroups
+        self.groups = groups(slab, self.launch, max_wgs=self.wgs) if slab is not None else None
 
     def run(self, fn) -> None:
         """fn() on the side stream, behind everything the main stream has issued so far"""
@@ -1115,7 +1306,7 @@ class SideWork:
         if self.groups is not None:
             self.groups.add(dy, x, self.G(name))
         else:
-            self.run(lambda: ops.gemm_tn(dy, x, self.G(name), max_wgs=self.side_wgs))
+            self.launch(lambda: ops.gemm_tn(dy, x, self.G(name), max_wgs=self.wgs))
 
     def flush(self) -> None:
         """issue the grouped weight gradients still pending (at every block end)"""

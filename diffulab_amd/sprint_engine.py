@@ -18,7 +18,7 @@ import torch
 from torch import Tensor
 
 from . import ops, tuning
-from .engine import DiTDims, DiTEngine, ParamLayout, SideWork, _must, _rup, rope_grid_tables
+from .engine import DiTDims, DiTEngine, Modulation, ParamLayout, SideWork, _rup, rope_grid_tables
 
 
 @dataclass
@@ -114,118 +114,38 @@ class SprintEngine(DiTEngine):
     def _stage_fwd(self, blocks: range, xin: Tensor, nt: int, pos: Tensor | None, out: Tensor) -> None:
         """DiT blocks `blocks` (indices into the block list) over xin [B*nt, D]; the stage output (last gated residual
         materialised) is written to `out` (rows may be strided)"""
-        d, w, sh = self.d, self.ws, self.sh
-        B = self.geo[0]
-        D, Hh = d.inner_dim, d.num_heads
-        gh, gw = self.geo[3], self.geo[4]
-        cos, sin = self._rope[(gh, gw)]
-        rot = sum(d.rope_axes_dim)
-        mod = w["mod"]
+        w, D = self.ws, self.d.inner_dim
+        cos, sin = self._rope[(self.geo[3], self.geo[4])]
         pend = None
         for bi in blocks:
-            a, pre, mo = w["blk"][bi], self.prefixes[bi], bi * 6 * D
-            n1w, n1b = self.P(pre + "norm_1.weight"), self.P(pre + "norm_1.bias")
-            if pend is None:
-                xcur = xin
-                ops.ln_modulate_fwd(xcur, n1w, n1b, mod[:, mo : mo + D], mod[:, mo + D : mo + 2 * D], nt, 1e-5, a["xm1"], a["mean1"],
-                                    a["rstd1"])
-            else:
-                xcur = a["x0"]
-                ops.ln_modulate_fwd(pend[0], n1w, n1b, mod[:, mo : mo + D], mod[:, mo + D : mo + 2 * D], nt, 1e-5, a["xm1"],
-                                    a["mean1"], a["rstd1"], t=pend[1], gate=pend[2], x_out=xcur)
-            a["xin"] = xcur
-            ops.gemm_nt(a["xm1"], sh[pre + "attention.qkv.weight|f"], a["qkv"])
-            ops.qk_norm_rope_fwd(a["qkv"], self.P(pre + "attention.qk_norm.query_norm.scale"),
-                                 self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["q"], a["k"],
-                                 None if ops.v_in_place(nt) else a["v"], a["rrms"], B, nt,
-                                 Hh, 64, rot, pos=pos)
-            if ops.v_in_place(nt):  # V read in place from the qkv rows (engine.py)
-                ops.attn_fwd_qkv(a["q"], a["k"], a["qkv"], a["a"], a["lse"], B, Hh, nt, 64, 64**-0.5)
-            else:
-                ops.attn_fwd(a["q"], a["k"], a["v"], a["a"], a["lse"], B, Hh, nt, 64, 64**-0.5)
-            ops.gemm_nt(a["a"], sh[pre + "attention.proj_out.weight|f"], a["t1"])
-            ops.ln_modulate_fwd(xcur, self.P(pre + "norm_2.weight"), self.P(pre + "norm_2.bias"), mod[:, mo + 3 * D : mo + 4 * D],
-                                mod[:, mo + 4 * D : mo + 5 * D], nt, 1e-5, a["xm2"], a["mean2"], a["rstd2"], t=a["t1"],
-                                gate=mod[:, mo + 2 * D : mo + 3 * D], x_out=a["x1"])
-            if not ops.gemm_nt_swiglu(a["xm2"], sh[pre + "mlp_input.0.weight|g"], a["u"] if self._train else None, a["h"]):
-                ops.gemm_nt(a["xm2"], sh[pre + "mlp_input.0.weight|f"], a["u"])
-                ops.swiglu_fwd(a["u"], a["h"])
-            ops.gemm_nt(a["h"], sh[pre + "mlp_input.2.weight|f"], a["t2"])
-            pend = (a["x1"], a["t2"], mod[:, mo + 5 * D : mo + 6 * D])
-        ops.gated_residual_fwd(pend[0], pend[1], pend[2], nt, out)
+            a = w["blk"][bi]
+            a["xin"] = xin if pend is None else a["x0"]
+            pend = self._dit_block_fwd(a, self.prefixes[bi], a["xin"], pend, Modulation(w["mod"], None, bi * 6 * D, D, nt), nt, cos, sin,
+                                       pos)
+        ops.gated_residual_fwd(*pend, nt, out)
 
     def _stage_bwd(self, blocks: range, dx: Tensor, nt: int, pos: Tensor | None, dfe: dict[int, Tensor], sw: SideWork) -> Tensor:
         """backward of _stage_fwd: dx = gradient at the stage output, contiguous bf16 [B*nt, D] (overwritten); returns the
         gradient at the stage input.  dfe: {block index: auxiliary-loss gradient at that block's output}"""
-        d, w, sh = self.d, self.ws, self.sh
-        B = self.geo[0]
-        D, Hh = d.inner_dim, d.num_heads
-        gh, gw = self.geo[3], self.geo[4]
-        cos, sin = self._rope[(gh, gw)]
-        rot = sum(d.rope_axes_dim)
+        w, B, D = self.ws, self.geo[0], self.d.inner_dim
+        cos, sin = self._rope[(self.geo[3], self.geo[4])]
         mod, dmod = w["mod"], w["dmod32"]
-        s = w[f"s{nt}"]
         blocks = list(blocks)
         last = blocks[-1]
-        inplace_qk = ops.qk_inplace_ok(w, B, nt)
         if last in dfe:
             ops.add_bf16(dx, dfe[last], dx)
         ml = last * 6 * D
         ops.gate_bwd(dx, w["blk"][last]["t2"], mod[:, ml + 5 * D : ml + 6 * D], nt, w["blk"][last]["wg"]["dt2"],
                      dmod[:, ml + 5 * D : ml + 6 * D])
-
-        def other(cur: Tensor) -> Tensor:  # ping-pong target of the next LayerNorm backward (never the buffer it reads)
-            return s["dxb"] if cur.data_ptr() == s["dxa"].data_ptr() else s["dxa"]
-
         for j in reversed(range(len(blocks))):
             bi = blocks[j]
-            a, pre, mo = w["blk"][bi], self.prefixes[bi], bi * 6 * D
-            g = a["wg"]
-            sw.wgrad(g["dt2"], a["h"], pre + "mlp_input.2.weight")
-            ops.mlp_swiglu_bwd(g["dt2"], sh[pre + "mlp_input.2.weight|t"], a["xm2"], sh[pre + "mlp_input.0.weight|g"], a["u"], s["dh"], g["du"])
-            sw.wgrad(g["du"], a["xm2"], pre + "mlp_input.0.weight")
-            ops.gemm_nt(g["du"], sh[pre + "mlp_input.0.weight|t"], s["dxm"])
-            dx_alt = other(dx)
-            ops.ln_modulate_bwd(s["dxm"], a["x1"], self.P(pre + "norm_2.weight"), self.P(pre + "norm_2.bias"),
-                                mod[:, mo + 3 * D : mo + 4 * D], nt, a["mean2"], a["rstd2"], dx, dx_alt, dmod[:, mo + 3 * D : mo + 4 * D],
-                                dmod[:, mo + 4 * D : mo + 5 * D], a["dwb"][1], gate_t=a["t1"], gate=mod[:, mo + 2 * D : mo + 3 * D],
-                                dt=g["dt1"], dgate=dmod[:, mo + 2 * D : mo + 3 * D])
-            sw.fold(a["dwb"][1], pre + "norm_2.weight", B)
-            dx = dx_alt
-            sw.wgrad(g["dt1"], a["a"], pre + "attention.proj_out.weight")
-            ops.gemm_nt(g["dt1"], sh[pre + "attention.proj_out.weight|t"], s["da"])
-            if inplace_qk:  # dQ, dK, dV token-major into dqkv; the QK-norm backward transforms the q / k thirds in place
-                ops.attn_bwd_tok(a["q"], a["k"], a["qkv"], a["a"], s["da"], a["lse"], g["dqkv"], B, Hh, nt, 64, 64**-0.5)
-                _must(ops.qk_norm_rope_bwd_inplace(a["qkv"], self.P(pre + "attention.qk_norm.query_norm.scale"),
-                                                    self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], g["dqkv"],
-                                                    self.G(pre + "attention.qk_norm.query_norm.scale"), w["qk_part"], B, nt, Hh, 64, rot,
-                                                    pos=pos))
-            else:
-                if ops.v_in_place(nt):
-                    ops.attn_bwd_qkv(a["q"], a["k"], a["qkv"], a["a"], s["da"], a["lse"], s["dq"], s["dk"], g["dqkv"], B, Hh, nt, 64,
-                                     64**-0.5)
-                else:
-                    ops.attn_bwd(a["q"], a["k"], a["v"], a["a"], s["da"], a["lse"], s["dq"], s["dk"], s["dv"], B, Hh, nt, 64, 64**-0.5)
-                ops.qk_norm_rope_bwd(s["dq"], s["dk"], None if ops.v_in_place(nt) else s["dv"], a["qkv"],
-                                     self.P(pre + "attention.qk_norm.query_norm.scale"),
-                                     self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], g["dqkv"],
-                                     self.G(pre + "attention.qk_norm.query_norm.scale"), B, nt, Hh, 64, rot, pos=pos)
-            sw.wgrad(g["dqkv"], a["xm1"], pre + "attention.qkv.weight")
-            ops.gemm_nt(g["dqkv"], sh[pre + "attention.qkv.weight|t"], s["dxm"])
-            nxt = {}
+            a = w["blk"][bi]
+            prev = dres = None
             if j > 0:
                 bp = blocks[j - 1]
-                if bp in dfe:  # auxiliary-loss gradient on the previous block's output (= this block's input)
-                    ops.add_bf16(dx, dfe[bp], dx)
-                mp = bp * 6 * D
-                nxt = dict(gate_t=w["blk"][bp]["t2"], gate=mod[:, mp + 5 * D : mp + 6 * D], dt=w["blk"][bp]["wg"]["dt2"],
-                           dgate=dmod[:, mp + 5 * D : mp + 6 * D])
-            dx_alt = other(dx)
-            ops.ln_modulate_bwd(s["dxm"], a["xin"], self.P(pre + "norm_1.weight"), self.P(pre + "norm_1.bias"), mod[:, mo : mo + D],
-                                nt, a["mean1"], a["rstd1"], dx, dx_alt, dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D],
-                                a["dwb"][0], **nxt)
-            sw.fold(a["dwb"][0], pre + "norm_1.weight", B)
-            dx = dx_alt
+                prev, dres = (w["blk"][bp]["t2"], bp * 6 * D + 5 * D, w["blk"][bp]["wg"]["dt2"]), dfe.get(bp)
+            m = Modulation(mod, dmod, bi * 6 * D, D, nt, part=a["dwb"], groups=B)
+            dx = self._dit_block_bwd(a, a["wg"], self.prefixes[bi], a["xin"], dx, prev, dres, w[f"s{nt}"], m, nt, cos, sin, sw, pos)
             self._end_block(sw, bi)
         return dx
 
@@ -257,12 +177,7 @@ class SprintEngine(DiTEngine):
             ops.restore_tokens(w["xd_out"], route.inv, mask, cat[:, :D], B, N, k, D)
         ops.gemm_nt(cat, sh["fuse.weight|f"], w["xfuse"], M=M, N=D, K=2 * D)
         self._stage_fwd(range(ne + nd, L), w["xfuse"], N, None, w["xdec"])
-        mo = L * 6 * D
-        ops.ln_modulate_fwd(w["xdec"], None, None, mod[:, mo : mo + D], mod[:, mo + D : mo + 2 * D], N, 1e-6, w["xf"], w["meanf"],
-                            w["rstdf"])
-        ops.gemm_nt(w["xf"], sh["last_layer.linear.weight|f"], w["otok"], bias=self.P("last_layer.linear.bias"), M=M, N=Fo, K=D)
-        ops.unpatchify(w["otok"], w["pred"], d.patch_size)
-        return w["pred"]
+        return self._head_fwd(Modulation(mod, None, L * 6 * D, D, N), w["xdec"])
 
     route: Route | None = None
 
@@ -283,16 +198,14 @@ class SprintEngine(DiTEngine):
         ne, nd = d.encoder_depth, d.deep_layers_depth
         route = self._route
         k = route.k
-        dfe = {kb: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb, g in (dfeats or {}).items()}
+        dfe = self._dfeat_rows(dfeats)
         mod, dmod = w["mod"], w["dmod32"]
         dmod[:B].zero_()
         sN = w[f"s{N}"]
 
         # head
         self._head_bwd(dpred, sN["dxm"])
-        mo = L * 6 * D
-        ops.ln_modulate_bwd(sN["dxm"], w["xdec"], None, None, mod[:, mo : mo + D], N, w["meanf"], w["rstdf"], None, sN["dxa"],
-                            dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], None)
+        Modulation(mod, dmod, L * 6 * D, D, N).ln_bwd(sN["dxm"], w["xdec"], None, None, 0, w["meanf"], w["rstdf"], None, sN["dxa"], None)
         sw = SideWork(self)
         dxf = self._stage_bwd(range(ne + nd, L), sN["dxa"], N, None, {}, sw)
         # fuse: xfuse = [restored | enc] Wf^T

@@ -6,7 +6,7 @@ the model of configs/train_imagenet_repa_txt_to_img_sprint.yaml):
     one 3D-row modulation) -> restore the image canvas, fuse = Linear(2D -> D) on [restored ; encoder image output],
     fuse_context = Linear(2D -> D) on [deep context ; encoder context] -> joint decoder blocks -> last layer
 
-Every stage reuses the launch sequences of the DiT / joint engines over ONE flat arena: per-stream gated residuals are absorbed by
+Every joint stage is DiTEngine._jstage_fwd / _jstage_bwd (engine.py) over ONE flat arena: per-stream gated residuals are absorbed by
 the next LayerNorm-modulate kernel inside a stage and materialised at stage boundaries; the single-stream stage keeps the
 concatenated latents [B, Lc + k, D] resident across its blocks (the reference's split / re-concatenate between consecutive blocks
 is the identity); RoPE rows of the kept tokens come from a position index, the key-padding mask from an additive key bias.
@@ -20,7 +20,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .engine import ArenaLayout, DiTEngine, SideWork, _rup
+from .engine import ArenaLayout, DiTEngine, Modulation, SideWork, _other, _rup
 from .mmdit_engine import STREAMS, JointDims, joint_rope_tables
 from .sprint_engine import Route
 
@@ -193,137 +193,11 @@ class SprintJointEngine(DiTEngine):
         self._publish(w, key, (B, H, W, gh, gw, N, M, _rup(B, 64), p * p * d.output_channels), (Lc, gh, gw),
                       lambda: joint_rope_tables(Lc, gh, gw, d.rope_axes_dim, d.rope_base))
 
-    # ------------------------------------------------------------------ joint stage
-    def _jstage_fwd(self, blocks, x_in: Tensor, c_in: Tensor, nx: int, pos: Tensor | None, kb: Tensor, x_out: Tensor,
-                    c_out: Tensor | None) -> None:
-        """MMDiTBlocks `blocks` on (image stream x_in [B*nx, D], context stream c_in [B*Lc, D]); outputs materialised into x_out /
-        c_out (rows may be strided); c_out None: the context half of the last block feeds nothing and is skipped"""
-        d, w, sh = self.d, self.ws, self.sh
-        B = self.geo[0]
-        Lc = self._Lc
-        D, Hh = d.inner_dim, d.num_heads
-        cos, sin = self._tabs
-        rot = sum(d.rope_axes_dim)
-        mod = w["mod"]
-        Tp = kb.shape[1]
-        streams = (("input", nx, Lc, 0, pos), ("context", Lc, 0, 6 * D, None))
-        cur = {"input": x_in, "context": c_in}
-        pend: dict[str, tuple | None] = {"input": None, "context": None}
-        blocks = list(blocks)
-        for bi in blocks:
-            per, pre, base = w["blk"][bi], self.prefixes[bi], self.layout.mod_off[bi]
-            for st, nt, off, mc, ps in streams:
-                a, mo = per[st], base + mc
-                n1w, n1b = self.P(pre + f"{st}_norm_1.weight"), self.P(pre + f"{st}_norm_1.bias")
-                if pend[st] is None:
-                    xcur = cur[st]
-                    ops.ln_modulate_fwd(xcur, n1w, n1b, mod[:, mo : mo + D], mod[:, mo + D : mo + 2 * D], nt, 1e-5, a["xm1"],
-                                        a["mean1"], a["rstd1"])
-                else:
-                    xcur, pd = a["x0"], pend[st]
-                    ops.ln_modulate_fwd(pd[0], n1w, n1b, mod[:, mo : mo + D], mod[:, mo + D : mo + 2 * D], nt, 1e-5, a["xm1"],
-                                        a["mean1"], a["rstd1"], t=pd[1], gate=pd[2], x_out=xcur)
-                a["xin"] = xcur
-                ops.gemm_nt(a["xm1"], sh[pre + f"attention.qkv_{st}.weight|f"], a["qkv"])
-                ops.qk_norm_rope_fwd(a["qkv"], self.P(pre + f"attention.qk_norm_{st}.query_norm.scale"),
-                                     self.P(pre + f"attention.qk_norm_{st}.key_norm.scale"), cos[off:], sin[off:], per["q"], per["k"],
-                                     per["v"], a["rrms"], B, nt, Hh, 64, rot, pos=ps, n_off=off)
-            ops.attn_fwd_ex(per["q"], per["k"], per["v"], per["ao"], per["lse"], B, Hh, Tp, Tp, 64, 64**-0.5, kb)
-            for st, nt, off, mc, ps in streams:
-                if st == "context" and c_out is None and bi == blocks[-1]:
-                    continue
-                a, mo = per[st], base + mc
-                ops.copy_rows3d(per["ao"][off:], Tp * D, D, a["a"], nt * D, D, B, nt, D)
-                ops.gemm_nt(a["a"], sh[pre + f"attention.{st}_proj_out.weight|f"], a["t1"])
-                ops.ln_modulate_fwd(a["xin"], self.P(pre + f"{st}_norm_2.weight"), self.P(pre + f"{st}_norm_2.bias"),
-                                    mod[:, mo + 3 * D : mo + 4 * D], mod[:, mo + 4 * D : mo + 5 * D], nt, 1e-5, a["xm2"], a["mean2"],
-                                    a["rstd2"], t=a["t1"], gate=mod[:, mo + 2 * D : mo + 3 * D], x_out=a["x1"])
-                if not ops.gemm_nt_swiglu(a["xm2"], sh[pre + f"mlp_{st}.0.weight|g"], a["u"] if self._train else None, a["h"]):
-                    ops.gemm_nt(a["xm2"], sh[pre + f"mlp_{st}.0.weight|f"], a["u"])
-                    ops.swiglu_fwd(a["u"], a["h"])
-                ops.gemm_nt(a["h"], sh[pre + f"mlp_{st}.2.weight|f"], a["t2"])
-                pend[st] = (a["x1"], a["t2"], mod[:, mo + 5 * D : mo + 6 * D])
-        ops.gated_residual_fwd(pend["input"][0], pend["input"][1], pend["input"][2], nx, x_out)
-        if c_out is not None:
-            ops.gated_residual_fwd(pend["context"][0], pend["context"][1], pend["context"][2], Lc, c_out)
-
-    def _jstage_bwd(self, blocks, dx_x: Tensor, dx_c: Tensor | None, nx: int, pos: Tensor | None, kb: Tensor, tag: str, dfe,
-                    sw: SideWork):
-        """backward of _jstage_fwd.  dx_x / dx_c: gradients at the stage outputs (contiguous, overwritten; dx_c None: the context output
-        was not produced).  Returns the gradients at the stage inputs (image, context)."""
-        d, w, sh = self.d, self.ws, self.sh
-        B = self.geo[0]
-        Lc = self._Lc
-        D, Hh = d.inner_dim, d.num_heads
-        cos, sin = self._tabs
-        rot = sum(d.rope_axes_dim)
-        mod, dmod = w["mod"], w["dmod32"]
-        Tp = kb.shape[1]
-        streams = (("input", nx, Lc, 0, pos), ("context", Lc, 0, 6 * D, None))
-        scr = {"input": w[f"s_x{nx}"], "context": w["s_c"]}
-        dao, dq, dk, dv = w["dao_" + tag], w["dq_" + tag], w["dk_" + tag], w["dv_" + tag]
-        blocks = list(blocks)
-        last = blocks[-1]
-        dx: dict[str, Tensor | None] = {"input": dx_x, "context": dx_c}
-
-        def other(s, cur):
-            return s["dxb"] if (cur is not None and cur.data_ptr() == s["dxa"].data_ptr()) else s["dxa"]
-
-        if last in dfe:
-            ops.add_bf16(dx_x, dfe[last], dx_x)
-        for st, nt, off, mc, ps in streams:  # backward of the materialised last residual of each stream
-            if dx[st] is None:
-                continue
-            a, mo = w["blk"][last][st], self.layout.mod_off[last] + mc
-            ops.gate_bwd(dx[st], a["t2"], mod[:, mo + 5 * D : mo + 6 * D], nt, a["wg"]["dt2"], dmod[:, mo + 5 * D : mo + 6 * D])
-        skip_ctx_last = dx_c is None
-        for j in reversed(range(len(blocks))):
-            bi = blocks[j]
-            per, pre, base = w["blk"][bi], self.prefixes[bi], self.layout.mod_off[bi]
-            dao.zero_()
-            for st, nt, off, mc, ps in streams:
-                if st == "context" and skip_ctx_last and bi == last:
-                    continue
-                a, mo, s, g = per[st], base + mc, scr[st], per[st]["wg"]
-                sw.wgrad(g["dt2"], a["h"], pre + f"mlp_{st}.2.weight")
-                ops.mlp_swiglu_bwd(g["dt2"], sh[pre + f"mlp_{st}.2.weight|t"], a["xm2"], sh[pre + f"mlp_{st}.0.weight|g"], a["u"], s["dh"], g["du"])
-                sw.wgrad(g["du"], a["xm2"], pre + f"mlp_{st}.0.weight")
-                ops.gemm_nt(g["du"], sh[pre + f"mlp_{st}.0.weight|t"], s["dxm"])
-                nx_ = other(s, dx[st])
-                ops.ln_modulate_bwd(s["dxm"], a["x1"], self.P(pre + f"{st}_norm_2.weight"), self.P(pre + f"{st}_norm_2.bias"),
-                                    mod[:, mo + 3 * D : mo + 4 * D], nt, a["mean2"], a["rstd2"], dx[st], nx_,
-                                    dmod[:, mo + 3 * D : mo + 4 * D], dmod[:, mo + 4 * D : mo + 5 * D], a["dwb"][1], gate_t=a["t1"],
-                                    gate=mod[:, mo + 2 * D : mo + 3 * D], dt=g["dt1"], dgate=dmod[:, mo + 2 * D : mo + 3 * D])
-                sw.fold(a["dwb"][1], pre + f"{st}_norm_2.weight", B)
-                dx[st] = nx_
-                sw.wgrad(g["dt1"], a["a"], pre + f"attention.{st}_proj_out.weight")
-                ops.gemm_nt(g["dt1"], sh[pre + f"attention.{st}_proj_out.weight|t"], s["da"])
-                ops.copy_rows3d(s["da"], nt * D, D, dao[off:], Tp * D, D, B, nt, D)
-            ops.attn_bwd_ex(per["q"], per["k"], per["v"], per["ao"], dao, per["lse"], dq, dk, dv, B, Hh, Tp, Tp, 64, 64**-0.5, kb)
-            for st, nt, off, mc, ps in streams:
-                a, mo, s, g = per[st], base + mc, scr[st], per[st]["wg"]
-                ops.qk_norm_rope_bwd(dq, dk, dv, a["qkv"], self.P(pre + f"attention.qk_norm_{st}.query_norm.scale"),
-                                     self.P(pre + f"attention.qk_norm_{st}.key_norm.scale"), cos[off:], sin[off:], a["rrms"], g["dqkv"],
-                                     self.G(pre + f"attention.qk_norm_{st}.query_norm.scale"), B, nt, Hh, 64, rot, pos=ps, n_off=off)
-                sw.wgrad(g["dqkv"], a["xm1"], pre + f"attention.qkv_{st}.weight")
-                ops.gemm_nt(g["dqkv"], sh[pre + f"attention.qkv_{st}.weight|t"], s["dxm"])
-                nxt = {}
-                if j > 0:
-                    bp = blocks[j - 1]
-                    if st == "input" and bp in dfe and dx[st] is not None:
-                        ops.add_bf16(dx[st], dfe[bp], dx[st])
-                    mp = self.layout.mod_off[bp] + mc
-                    ap = w["blk"][bp][st]
-                    nxt = dict(gate_t=ap["t2"], gate=mod[:, mp + 5 * D : mp + 6 * D], dt=ap["wg"]["dt2"],
-                               dgate=dmod[:, mp + 5 * D : mp + 6 * D])
-                nx_ = other(s, dx[st])
-                ops.ln_modulate_bwd(s["dxm"], a["xin"], self.P(pre + f"{st}_norm_1.weight"), self.P(pre + f"{st}_norm_1.bias"),
-                                    mod[:, mo : mo + D], nt, a["mean1"], a["rstd1"], dx[st], nx_, dmod[:, mo : mo + D],
-                                    dmod[:, mo + D : mo + 2 * D], a["dwb"][0], **nxt)
-                sw.fold(a["dwb"][0], pre + f"{st}_norm_1.weight", B)
-                dx[st] = nx_
-            self._end_block(sw, bi)
-        return dx["input"], dx["context"]
+    def _jscratch(self, nx: int, tag: str) -> tuple[dict, tuple]:
+        """scratch of _jstage_bwd over nx image tokens per sample: the chain scratch of each stream and the attention scratch of the
+        full ("f") or the deep ("d") joint sequence"""
+        w = self.ws
+        return {"input": w[f"s_x{nx}"], "context": w["s_c"]}, (w["dao_" + tag], w["dq_" + tag], w["dk_" + tag], w["dv_" + tag])
 
     # ------------------------------------------------------------------ single-stream stage
     def _sstage_fwd(self, blocks, lat_in: Tensor, T: int, pos: Tensor, kb: Tensor, out: Tensor) -> None:
@@ -401,7 +275,7 @@ class SprintJointEngine(DiTEngine):
                 mp = self.layout.mod_off[bp]
                 nxt = dict(gate_t=w["blk"][bp]["t"], gate=mod[:, mp + 2 * D : mp + 3 * D], dt=w["blk"][bp]["wg"]["dt"],
                            dgate=dmod[:, mp + 2 * D : mp + 3 * D])
-            nx_ = s["dxb"] if dx.data_ptr() == s["dxa"].data_ptr() else s["dxa"]
+            nx_ = _other(s, dx)
             ops.ln_modulate_bwd(s["dxm2"], a["xin"], self.P(pre + "norm.weight"), self.P(pre + "norm.bias"), mod[:, mo : mo + D], T,
                                 a["mean"], a["rstd"], dx, nx_, dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], a["dwb"][0], **nxt)
             sw.fold(a["dwb"][0], pre + "norm.weight", B)
@@ -465,12 +339,7 @@ class SprintJointEngine(DiTEngine):
         ops.gemm_nt(cat, sh["fuse.weight|f"], w["xfuse"], M=M, N=D, K=2 * D)
         ops.gemm_nt(ccat, sh["fuse_context.weight|f"], w["cfuse"], M=B * Lc, N=D, K=2 * D)
         self._jstage_fwd(range(ne + nd, L), w["xfuse"], w["cfuse"], N, None, w["kb_f"], w["xdec"], None)
-        mo = self.layout.mod_rows - 2 * D
-        ops.ln_modulate_fwd(w["xdec"], None, None, mod[:, mo : mo + D], mod[:, mo + D : mo + 2 * D], N, 1e-6, w["xf"], w["meanf"],
-                            w["rstdf"])
-        ops.gemm_nt(w["xf"], sh["last_layer.linear.weight|f"], w["otok"], bias=self.P("last_layer.linear.bias"), M=M, N=Fo, K=D)
-        ops.unpatchify(w["otok"], w["pred"], d.patch_size)
-        return w["pred"]
+        return self._head_fwd(Modulation(mod, None, self.layout.mod_rows - 2 * D, D, N), w["xdec"])
 
     def feature(self, kblk: int) -> Tensor:
         """image-stream output of encoder block k (``layers[k]``) of the last train-mode forward"""
@@ -491,17 +360,16 @@ class SprintJointEngine(DiTEngine):
         route, Lc = self._route, self._Lc
         k = route.k
         Td = Lc + k
-        dfe = {kb_: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb_, g in (dfeats or {}).items()}
+        dfe = self._dfeat_rows(dfeats)
         mod, dmod = w["mod"], w["dmod32"]
         dmod[:B].zero_()
         sN = w[f"s_x{N}"]
 
         self._head_bwd(dpred, sN["dxm"])
-        mo = self.layout.mod_rows - 2 * D
-        ops.ln_modulate_bwd(sN["dxm"], w["xdec"], None, None, mod[:, mo : mo + D], N, w["meanf"], w["rstdf"], None, w["dxdec"],
-                            dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], None)
+        Modulation(mod, dmod, self.layout.mod_rows - 2 * D, D, N).ln_bwd(sN["dxm"], w["xdec"], None, None, 0, w["meanf"], w["rstdf"], None,
+                                                                         w["dxdec"], None)
         sw = SideWork(self)
-        dxf, dcf = self._jstage_bwd(range(ne + nd, L), w["dxdec"], None, N, None, w["kb_f"], "f", {}, sw)
+        dxf, dcf = self._jstage_bwd(range(ne + nd, L), w["dxdec"], None, N, None, w["kb_f"], *self._jscratch(N, "f"), {}, sw)
         # fuse / fuse_context (main stream: dxf / dcf are chain scratch that the next stages reuse)
         ops.gemm_tn(dxf, w["cat"], self.G("fuse.weight"))
         ops.gemm_tn(dcf, w["ccat"], self.G("fuse_context.weight"))
@@ -529,10 +397,10 @@ class SprintJointEngine(DiTEngine):
                 ops.copy_rows3d(dl, Td * D, D, w["dcj"], Lc * D, D, B, Lc, D)
                 gx, gc = w["dxj"], w["dcj"]
             if nj:
-                gx, gc = self._jstage_bwd(range(ne, ne + nj), gx, gc, k, pos_img, w["kb_d"], "d", {}, sw)
+                gx, gc = self._jstage_bwd(range(ne, ne + nj), gx, gc, k, pos_img, w["kb_d"], *self._jscratch(k, "d"), {}, sw)
             ops.scatter_tokens_add(gx, route.idx, w["dright"], B, N, k, D)
             ops.add_bf16(w["dcr"], gc, w["dcr"])
-        dx0, dc0 = self._jstage_bwd(range(0, ne), w["dright"], w["dcr"], N, None, w["kb_f"], "f", dfe, sw)
+        dx0, dc0 = self._jstage_bwd(range(0, ne), w["dright"], w["dcr"], N, None, w["kb_f"], *self._jscratch(N, "f"), dfe, sw)
         sw.join()
         ops.gemm_tn(dc0, w["ctxP"], self.G("context_embed.weight"), M=D, N=Cd)
         self._cond_bwd(dx0)
@@ -644,12 +512,7 @@ class JointStackEngine(SprintJointEngine):
         ops.copy_rows3d(xs, N * D, D, lat0[Lc:], T * D, D, B, N, D)
         self._sstage_fwd(range(nj, L), lat0, T, None, kb, w["lat_out"])
         ops.copy_rows3d(w["lat_out"][Lc:], T * D, D, w["xl"], N * D, D, B, N, D)
-        mo = self.layout.mod_rows - 2 * D
-        ops.ln_modulate_fwd(w["xl"], None, None, mod[:, mo : mo + D], mod[:, mo + D : mo + 2 * D], N, 1e-6, w["xf"], w["meanf"],
-                            w["rstdf"])
-        ops.gemm_nt(w["xf"], sh["last_layer.linear.weight|f"], w["otok"], bias=self.P("last_layer.linear.bias"), M=M, N=Fo, K=D)
-        ops.unpatchify(w["otok"], w["pred"], d.patch_size)
-        return w["pred"]
+        return self._head_fwd(Modulation(mod, None, self.layout.mod_rows - 2 * D, D, N), w["xl"])
 
     def feature(self, kblk: int) -> Tensor:
         nj = self.d.depth - self.d.n_single_stream_blocks
@@ -668,14 +531,13 @@ class JointStackEngine(SprintJointEngine):
         D, L, Cd, Lc = d.inner_dim, d.depth, d.context_dim, self._Lc
         nj = L - d.n_single_stream_blocks
         T = Lc + N
-        dfe = {kb_: g.reshape(-1, D).to(torch.bfloat16).contiguous() for kb_, g in (dfeats or {}).items()}
+        dfe = self._dfeat_rows(dfeats)
         mod, dmod = w["mod"], w["dmod32"]
         dmod[:B].zero_()
         sN = w[f"s_x{N}"]
         self._head_bwd(dpred, sN["dxm"])
-        mo = self.layout.mod_rows - 2 * D
-        ops.ln_modulate_bwd(sN["dxm"], w["xl"], None, None, mod[:, mo : mo + D], N, w["meanf"], w["rstdf"], None, w["dxl"],
-                            dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], None)
+        Modulation(mod, dmod, self.layout.mod_rows - 2 * D, D, N).ln_bwd(sN["dxm"], w["xl"], None, None, 0, w["meanf"], w["rstdf"], None,
+                                                                         w["dxl"], None)
         sw = SideWork(self)
         dlat = w["dlat"]
         dlat.zero_()  # the context rows of the last block's output feed nothing
@@ -685,7 +547,7 @@ class JointStackEngine(SprintJointEngine):
         ops.copy_rows3d(dl, T * D, D, w["dcj"], Lc * D, D, B, Lc, D)
         gx, gc = w["dxj"], w["dcj"]
         if nj:
-            gx, gc = self._jstage_bwd(range(0, nj), gx, gc, N, None, w["kb_f"], "f", dfe, sw)
+            gx, gc = self._jstage_bwd(range(0, nj), gx, gc, N, None, w["kb_f"], *self._jscratch(N, "f"), dfe, sw)
         sw.join()
         ops.gemm_tn(gc, w["ctxP"], self.G("context_embed.weight"), M=D, N=Cd)
         self._cond_bwd(gx)

@@ -20,6 +20,12 @@
 // Beyond 2048 tokens (up to 32768): `*_long_k` -- the forward double-buffers its K / V stream, the backward computes delta in a
 // pre-pass and splits dK / dV and dQ into two launches, so that no LDS array grows with N.
 #include "common.h"
+#include "attn_paths.h"
+
+// the path code of the last attention launch (attn_paths.h): one relaxed host-side store per call, read by the tests
+static std::atomic<int> g_last_attn_path{DL_ATTN_PATH_NONE};
+void dl_note_attn_path(int path) { g_last_attn_path.store(path, std::memory_order_relaxed); }
+extern "C" __attribute__((visibility("default"))) int dl_lab_last_attn_path() { return g_last_attn_path.load(std::memory_order_relaxed); }
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
@@ -492,6 +498,7 @@ extern "C" int dl_attn_fwd_ex(const void* q, const void* k, const void* v, void*
       (void)hipFuncSetAttribute((const void*)attn_fwd_long_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * LBUF);
       (void)hipFuncSetAttribute((const void*)attn_fwd_long_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * LBUF);
     });
+    dl_note_attn_path(key_bias ? ATTN_FWD_LONG_BIAS : ATTN_FWD_LONG_NOBIAS);
     if (key_bias)
       hipLaunchKernelGGL(attn_fwd_long_k<true>, (int)(B * H * (Nq / ACH)), 512, 2 * LBUF, (hipStream_t)stream, (const bf16_t*)q,
                          (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, lse, (int)H, (int)Nq, (int)Nk, scale, key_bias);
@@ -503,6 +510,7 @@ extern "C" int dl_attn_fwd_ex(const void* q, const void* k, const void* v, void*
   }
   const int ldt = 2 * ACH * ROWB + ACH * (int)sizeof(float);
   (void)hipFuncSetAttribute((const void*)attn_fwd_tiled_k, hipFuncAttributeMaxDynamicSharedMemorySize, ldt);
+  dl_note_attn_path(ATTN_FWD_TILED);
   hipLaunchKernelGGL(attn_fwd_tiled_k, (int)(B * H * (Nq / ACH)), 512, ldt, (hipStream_t)stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, lse, (int)H, (int)Nq, (int)Nk, scale, key_bias);
   DL_LAUNCH_CHECK();
@@ -528,6 +536,7 @@ extern "C" int dl_attn_fwd_sv(const void* q, const void* k, const void* v, int64
                "dl_attn_fwd_sv: V rows must be 16-byte aligned");
   const int lds = (int)(2 * N * ROWB);
   (void)hipFuncSetAttribute((const void*)attn_fwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  dl_note_attn_path(ATTN_FWD_RESIDENT);
   hipLaunchKernelGGL(attn_fwd_k, (int)(B * H), (int)(N / 32) * 64, lds, (hipStream_t)stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, lse, (int)H, (int)N, scale,
                      HeadLayout{v_batch_stride, v_head_stride, (int)v_pitch});
@@ -957,11 +966,13 @@ extern "C" int dl_attn_fwd_qkn(const void* qkv, const float* ssq, const float* s
     (void)dev_cus(once2, [] { (void)hipFuncSetAttribute((const void*)attn_fwd_qkn_pipe_k, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * PIPE_N * ROWB + 8 * 2048); });
     const int items = (int)(B * H);
     const int per = (items + cus - 1) / cus, grid = (items + per - 1) / per;
+    dl_note_attn_path(ATTN_FWD_QKN_PIPE);
     hipLaunchKernelGGL(attn_fwd_qkn_pipe_k, grid, 512, 4 * PIPE_N * ROWB + 8 * (int)D, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, (int)H,
                        items, scale, qn);
     DL_LAUNCH_CHECK();
     return DL_OK;
   }
+  dl_note_attn_path(ATTN_FWD_QKN_CHAIN);
   hipLaunchKernelGGL(attn_fwd_qkn_k, (int)(B * H), (int)(N / 32) * 64, lds, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, (int)H,
                      (int)N, scale, qn);
   DL_LAUNCH_CHECK();
@@ -1506,6 +1517,7 @@ extern "C" int dl_attn_bwd_ex(const void* q, const void* k, const void* v, const
       (void)hipFuncSetAttribute((const void*)attn_bwd_dq_long_k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 2 * ACH * ROWB + ACH * (int)sizeof(float));
     });
+    dl_note_attn_path(ATTN_BWD_LONG);
     hipLaunchKernelGGL(attn_bwd_delta_k, (int)(B * Nq * H / 128), 256, 0, (hipStream_t)stream, (const bf16_t*)out, (const bf16_t*)dout,
                        (bf16_t*)dq, (int)H, (int)Nq);
     DL_LAUNCH_CHECK();
@@ -1522,6 +1534,7 @@ extern "C" int dl_attn_bwd_ex(const void* q, const void* k, const void* v, const
   const int ldt = (int)(2 * ACH * ROWB + (2 * Nq + ACH) * sizeof(float));
   const int64_t nmax = (Nq > Nk ? Nq : Nk) / ACH;
   (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_k, hipFuncAttributeMaxDynamicSharedMemorySize, ldt);
+  dl_note_attn_path(ATTN_BWD_TILED);
   hipLaunchKernelGGL(attn_bwd_tiled_k, (int)(B * H * nmax), 256, ldt, (hipStream_t)stream, (const bf16_t*)q, (const bf16_t*)k,
                      (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv,
                      (int)H, (int)Nq, (int)Nk, scale, key_bias);
@@ -1544,6 +1557,7 @@ static int attn_bwd_launch(const void* q, const void* k, const void* v, HeadLayo
                            int64_t N, float scale, dl_stream_t stream) {
   const int lds = (int)(2 * N * ROWB + 2 * N * sizeof(float));
   (void)hipFuncSetAttribute((const void*)attn_bwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  dl_note_attn_path(ATTN_BWD_RESIDENT);
   hipLaunchKernelGGL(attn_bwd_k, (int)(B * H), (int)(N / 64) * 64, lds, (hipStream_t)stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dq,
                      (bf16_t*)dk, (bf16_t*)dv, (int)H, (int)N, scale, vl, dvl, dql);
@@ -1794,6 +1808,7 @@ bool launch_attn_small_mfma_fwd(const void* q, const void* k, const void* v, int
   (void)dev_cus(once, [] {
     (void)hipFuncSetAttribute((const void*)attn_small_mfma_fwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * ASM_PITCH * 4 + 512 * 128);
   });
+  dl_note_attn_path(ATTN_SMALL_FWD_MFMA);
   hipLaunchKernelGGL(attn_small_mfma_fwd_k, (int)(B * H), 256, lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq,
                      ldkv, (bf16_t*)out, ldo, probs, (int)n, (int)H, (int)dh, scale);
   return true;
@@ -1807,6 +1822,7 @@ bool launch_attn_small_mfma_bwd(const void* q, const void* k, const void* v, int
   (void)dev_cus(once, [] {
     (void)hipFuncSetAttribute((const void*)attn_small_mfma_bwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * ASM_PITCH * 4 + 512 * 128);
   });
+  dl_note_attn_path(ATTN_SMALL_BWD_MFMA);
   hipLaunchKernelGGL(attn_small_mfma_bwd_k, (int)(B * H), 256, lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq,
                      ldkv, (const bf16_t*)dout, ldo, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, (int)n, (int)H, (int)dh, scale);
   return true;
@@ -2022,6 +2038,7 @@ bool launch_attn_cross_mfma_fwd(const void* q, const void* k, const void* v, int
   (void)dev_cus(once, [] {
     (void)hipFuncSetAttribute((const void*)attn_cross_mfma_fwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * ASM_PITCH * 4 + 512 * 128);
   });
+  dl_note_attn_path(ATTN_CROSS_FWD_MFMA);
   hipLaunchKernelGGL(attn_cross_mfma_fwd_k, (int)(B * H), 256, lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq,
                      ldkv, kbias, (bf16_t*)out, ldo, probs, (int)Nq, (int)L, (int)H, (int)dh, scale);
   return true;
@@ -2035,6 +2052,7 @@ bool launch_attn_cross_mfma_bwd(const void* q, const void* k, const void* v, int
   (void)dev_cus(once, [] {
     (void)hipFuncSetAttribute((const void*)attn_cross_mfma_bwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * ASM_PITCH * 4 + 512 * 128);
   });
+  dl_note_attn_path(ATTN_CROSS_BWD_MFMA);
   hipLaunchKernelGGL(attn_cross_mfma_bwd_k, (int)(B * H), 256, lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq,
                      ldkv, (const bf16_t*)dout, ldo, probs, ds, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, (int)Nq, (int)L, (int)H, (int)dh,
                      scale);

@@ -6,6 +6,7 @@
 // K = 9*C contiguous per tap); the reference's NCHW f32 tensors are converted at the model boundary.
 // Reference: networks/utils/nn.py:11-88, networks/denoisers/unet.py:215-237,296-355.
 #include "common.h"
+#include "attn_paths.h"
 
 static inline int grid_for(int64_t n, int threads = 256, int cap = 4096) {
   int64_t g = (n + threads - 1) / threads;
@@ -1434,6 +1435,7 @@ extern "C" int dl_attn_small_fwd(const void* q, const void* k, const void* v, in
     DL_LAUNCH_CHECK();
     return DL_OK;
   }
+  dl_note_attn_path(ATTN_SMALL_FWD_VALU);
   hipLaunchKernelGGL(attn_small_fwd_k, (int)(B * H), 256, 0, (hipStream_t)stream, (const bf16_t*)q, (const bf16_t*)k,
                      (const bf16_t*)v, ldq, ldkv, (bf16_t*)out, ldo, probs, (int)n, (int)H, (int)dh, scale);
   DL_LAUNCH_CHECK();
@@ -1449,6 +1451,7 @@ extern "C" int dl_attn_small_bwd(const void* q, const void* k, const void* v, in
     DL_LAUNCH_CHECK();
     return DL_OK;
   }
+  dl_note_attn_path(ATTN_SMALL_BWD_VALU);
   hipLaunchKernelGGL(attn_small_bwd_k, (int)(B * H), 256, 0, (hipStream_t)stream, (const bf16_t*)q, (const bf16_t*)k,
                      (const bf16_t*)v, ldq, ldkv, (const bf16_t*)dout, ldo, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, (int)n,
                      (int)H, (int)dh, scale);
@@ -1688,6 +1691,7 @@ extern "C" int dl_attn_cross_fwd(const void* q, const void* k, const void* v, in
     DL_LAUNCH_CHECK();
     return DL_OK;
   }
+  dl_note_attn_path(ATTN_CROSS_FWD_VALU);
   hipLaunchKernelGGL(attn_cross_fwd_k, dim3((unsigned)(B * H), (unsigned)((Nq + AX_QT - 1) / AX_QT)), 256, 0, (hipStream_t)stream,
                      (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldkv, key_bias, (bf16_t*)out, ldo, probs, (int)Nq,
                      (int)L, (int)H, (int)dh, scale);
@@ -1710,6 +1714,7 @@ extern "C" int dl_attn_cross_bwd(const void* q, const void* k, const void* v, in
     DL_LAUNCH_CHECK();
     return DL_OK;
   }
+  dl_note_attn_path(ATTN_CROSS_BWD_VALU);
   hipLaunchKernelGGL(attn_cross_bwd_q_k, dim3((unsigned)(B * H), (unsigned)((Nq + AX_QB - 1) / AX_QB)), 256, 0, (hipStream_t)stream,
                      (const bf16_t*)k, (const bf16_t*)v, ldkv, (const bf16_t*)dout, ldo, probs, ds, (bf16_t*)dq, ldq, (int)Nq, (int)L,
                      (int)H, (int)dh, scale);

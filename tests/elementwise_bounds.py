@@ -11,6 +11,9 @@ Fp32 accumulation of K terms in any order -- split-K partials, atomics and folds
 gamma_K ~ K * 2^-24.  The factor 2 is margin for the MFMA unit's internal accumulation order and rounding.
 Every epilogue step then adds its own term (see the functions below), and the final store adds half an ulp of |ref| + err:
 2^(e - 9) for bf16 and 2^(e - 25) for f32, where 2^(e - 1) <= |ref| + err < 2^e.
+
+The bounds of the softmax-attention kernels (forward, backward, the UNet's saved-probability forms, the fused QK-norm forward) live
+in tests/attention_bounds.py, which builds on the constants, store terms and poisoned buffers of this module.
 """
 
 from __future__ import annotations

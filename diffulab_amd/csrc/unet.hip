@@ -7,6 +7,8 @@
 // Reference: networks/utils/nn.py:11-88, networks/denoisers/unet.py:215-237,296-355.
 #include "common.h"
 #include "attn_paths.h"
+#include "gn_paths.h"
+#include <atomic>
 
 static inline int grid_for(int64_t n, int threads = 256, int cap = 4096) {
   int64_t g = (n + threads - 1) / threads;
@@ -57,79 +59,98 @@ static int g_gn_fused = 1;  // 3 (tests): as 1, also where a launch would not fi
                              // small maps only (round 4); 0: the separate launches (forward: statistics + apply; backward: reduce + group sums + apply)
 extern "C" __attribute__((visibility("default"))) void dl_lab_set_gn_fused(int mode) { g_gn_fused = mode; }  // LAB A/B switch (not in the header)
 static int gn_bwd_fused() { return g_gn_fused; }  // (the three-launch form stays for the shapes the fused kernel does not take)
+// the path code of the last GroupNorm launch (gn_paths.h): one relaxed host-side store per call, read by the tests
+static std::atomic<int> g_last_gn_path{DL_GN_PATH_NONE};
+static void gn_note_path(int path) { g_last_gn_path.store(path, std::memory_order_relaxed); }
+extern "C" __attribute__((visibility("default"))) int dl_lab_last_gn_path() { return g_last_gn_path.load(std::memory_order_relaxed); }
 
-// statistics: one workgroup per sample; thread (pixel lane, chunk) accumulates sum / sum of squares of its 8 channels over its pixels
-// and leaves them in an LDS row of its own; thread g then adds group g's channels over the pixel lanes in a fixed order -- no atomics:
-// the statistics (and with them the inference forward) are bit-reproducible.  C <= 2048 (256 chunks); wider rows: LDS float atomics.
+// statistics: one workgroup per sample, two passes over its pixels (the second one re-reads the sample through L2).  Pass 1: thread
+// (pixel lane, chunk) sums its 8 channels over its pixels and leaves the sums in an LDS row of its own; thread g then adds group g's
+// channels over the pixel lanes in a fixed order and publishes the mean.  Pass 2: the same walk over (x - mean)^2.  The variance is the
+// CENTRED second moment: E[x^2] - mean^2 from f32 sums loses (mean / std)^2 of the precision (1.7e-3 of rstd at a ratio of 128).
+// No atomics up to C = 2048 (256 chunks): the statistics (and with them the inference forward) are bit-reproducible; wider rows: LDS
+// float atomics.
 __global__ __launch_bounds__(256) void gn_stats_k(const bf16_t* __restrict__ x, float* __restrict__ st, int HW, int C, int G,
                                                   float eps) {
-  __shared__ float part[2][2048];  // [sum | sum of squares][pixel lane * C + channel]  (npl * C <= 2048)
+  __shared__ float part[2048];  // [pixel lane * C + channel]  (npl * C <= 2048)
   __shared__ float rs[GN_MAXG][2];
   const int b = blockIdx.x, cg = C / G, C8 = C >> 3;
+  const float n = (float)HW * cg;
   if (C8 <= 256) {
     const int npl = 256 / C8;
     const int chunk = (int)threadIdx.x % C8, pl = (int)threadIdx.x / C8;
-    if (pl < npl) {
-      float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int p = pl; p < HW; p += npl) {
-        float v[8];
-        unpack8(*(const u32x4_t*)(x + ((int64_t)b * HW + p) * C + chunk * 8), v);
+    float mu[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+      if (pl < npl) {
+        float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int p = pl; p < HW; p += npl) {
+          float v[8];
+          unpack8(*(const u32x4_t*)(x + ((int64_t)b * HW + p) * C + chunk * 8), v);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          s[e] += v[e];
-          q[e] += v[e] * v[e];
+          for (int e = 0; e < 8; ++e) {
+            const float d = v[e] - mu[e];
+            s[e] += pass ? d * d : d;
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) part[pl * C + chunk * 8 + e] = s[e];
+      }
+      __syncthreads();
+      if ((int)threadIdx.x < G) {
+        float S = 0.f;
+        for (int r = 0; r < npl; ++r)
+          for (int j = 0; j < cg; ++j) S += part[r * C + threadIdx.x * cg + j];
+        if (pass == 0) {
+          rs[threadIdx.x][0] = S / n;
+          st[((int64_t)b * G + threadIdx.x) * 2] = S / n;
+        } else {
+          st[((int64_t)b * G + threadIdx.x) * 2 + 1] = rsqrtf(S / n + eps);
         }
       }
+      __syncthreads();
+      if (pass == 0 && pl < npl) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        part[0][pl * C + chunk * 8 + e] = s[e];
-        part[1][pl * C + chunk * 8 + e] = q[e];
+        for (int e = 0; e < 8; ++e) mu[e] = rs[(chunk * 8 + e) / cg][0];
       }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < G) {
-      float S = 0.f, Q = 0.f;
-      for (int r = 0; r < npl; ++r)
-        for (int j = 0; j < cg; ++j) {
-          S += part[0][r * C + threadIdx.x * cg + j];
-          Q += part[1][r * C + threadIdx.x * cg + j];
-        }
-      const float n = (float)HW * cg;
-      const float mu = S / n;
-      st[((int64_t)b * G + threadIdx.x) * 2] = mu;
-      st[((int64_t)b * G + threadIdx.x) * 2 + 1] = rsqrtf(fmaxf(Q / n - mu * mu, 0.f) + eps);
     }
     return;
   }
   if (threadIdx.x < 2 * GN_MAXG) (&rs[0][0])[threadIdx.x] = 0.f;
   __syncthreads();
-  for (int ch0 = 0; ch0 < C8; ch0 += 256) {
-    const int chunk = ch0 + (int)threadIdx.x;
-    if (chunk < C8) {
-      float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int p = 0; p < HW; ++p) {
-        float v[8];
-        unpack8(*(const u32x4_t*)(x + ((int64_t)b * HW + p) * C + chunk * 8), v);
+#pragma unroll 1
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int ch0 = 0; ch0 < C8; ch0 += 256) {
+      const int chunk = ch0 + (int)threadIdx.x;
+      if (chunk < C8) {
+        float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mu[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          s[e] += v[e];
-          q[e] += v[e] * v[e];
+        for (int e = 0; e < 8; ++e) mu[e] = pass ? rs[(chunk * 8 + e) / cg][0] : 0.f;
+        for (int p = 0; p < HW; ++p) {
+          float v[8];
+          unpack8(*(const u32x4_t*)(x + ((int64_t)b * HW + p) * C + chunk * 8), v);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float d = v[e] - mu[e];
+            s[e] += pass ? d * d : d;
+          }
         }
-      }
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {  // (a chunk of 8 channels may straddle two groups: booked per element)
-        atomicAdd(&rs[(chunk * 8 + e) / cg][0], s[e]);
-        atomicAdd(&rs[(chunk * 8 + e) / cg][1], q[e]);
+        for (int e = 0; e < 8; ++e)  // (a chunk of 8 channels may straddle two groups: booked per element)
+          atomicAdd(&rs[(chunk * 8 + e) / cg][pass], s[e]);
       }
     }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < G) {
-    const float n = (float)HW * cg;
-    const float mu = rs[threadIdx.x][0] / n;
-    const float var = fmaxf(rs[threadIdx.x][1] / n - mu * mu, 0.f);
-    st[((int64_t)b * G + threadIdx.x) * 2] = mu;
-    st[((int64_t)b * G + threadIdx.x) * 2 + 1] = rsqrtf(var + eps);
+    __syncthreads();
+    if ((int)threadIdx.x < G) {
+      if (pass == 0) {
+        const float m = rs[threadIdx.x][0] / n;
+        rs[threadIdx.x][0] = m;
+        st[((int64_t)b * G + threadIdx.x) * 2] = m;
+      } else {
+        st[((int64_t)b * G + threadIdx.x) * 2 + 1] = rsqrtf(rs[threadIdx.x][1] / n + eps);
+      }
+    }
+    __syncthreads();
   }
 }
 extern "C" int dl_gn_stats(const void* x, float* stats, int64_t B, int64_t HW, int64_t C, int64_t G, float eps,
@@ -137,6 +158,7 @@ extern "C" int dl_gn_stats(const void* x, float* stats, int64_t B, int64_t HW, i
   DL_CHECK_ARG(x && stats && B > 0 && HW > 0 && C > 0 && G > 0 && G <= GN_MAXG && C % G == 0 && C % 8 == 0 &&
                    ((uintptr_t)x & 15) == 0,
                "dl_gn_stats: bad args (C %% 8, C %% G, G <= 64, 16-byte alignment)");
+  gn_note_path(C <= 2048 ? GN_STATS : GN_STATS_ATOMIC);
   hipLaunchKernelGGL(gn_stats_k, (int)B, 256, 0, (hipStream_t)stream, (const bf16_t*)x, stats, (int)HW, (int)C, (int)G, eps);
   DL_LAUNCH_CHECK();
   return DL_OK;
@@ -200,6 +222,7 @@ extern "C" int dl_gn_apply_fwd(const void* x, const float* stats, const float* w
                    ld_film % 8 == 0,
                "dl_gn_apply_fwd: 16-byte alignment");
   DL_CHECK_ARG(B < 65536 && HW * C / 8 < (1ll << 31), "dl_gn_apply_fwd: B < 65536, HW*C/8 < 2^31");
+  gn_note_path(GN_APPLY_FWD);
   hipLaunchKernelGGL(gn_apply_fwd_k, gn_grid(B, HW * C / 8), 256, 0, (hipStream_t)stream, (const bf16_t*)x, stats, w, b,
                      (const bf16_t*)film_scale, (const bf16_t*)film_shift, ld_film, act_silu, (bf16_t*)out, (int)HW, (int)C,
                      (int)G);
@@ -209,8 +232,8 @@ extern "C" int dl_gn_apply_fwd(const void* x, const float* stats, const float* w
 
 // statistics + apply in ONE launch (the training shapes): a workgroup owns a slab of NCH * 8 channels (a whole number of groups) of one
 // sample; every x row of a lane is loaded once and stays in registers (KEEP rows per lane: feature maps of <= KEEP * 256 / NCH pixels)
-// between the statistics pass and the normalise / FiLM / SiLU pass.  Same arithmetic as gn_stats_k + gn_apply_fwd_k (f32 sum and sum of
-// squares per group); statistics are written for the backward.
+// between the statistics passes and the normalise / FiLM / SiLU pass.  Same arithmetic as gn_stats_k + gn_apply_fwd_k: the group mean
+// from f32 sums, then the CENTRED second moment from the rows in registers (no second read); statistics are written for the backward.
 template <int NCH, int KEEP>
 __global__ __launch_bounds__(256) void gn_fwd_fused_k(const bf16_t* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bb,
                                                       const bf16_t* __restrict__ fs, const bf16_t* __restrict__ fh, int64_t ldf, int silu,
@@ -218,7 +241,7 @@ __global__ __launch_bounds__(256) void gn_fwd_fused_k(const bf16_t* __restrict__
   constexpr int SLAB = NCH * 8, PL = 256 / NCH;
   constexpr bool POW2 = (NCH & (NCH - 1)) == 0;  // (NCH = 12: 96-channel slabs, 21 pixel lanes + 4 idle threads -- see gn_bwd_fused_k)
   constexpr int NP = POW2 ? 4 : PL;
-  __shared__ __attribute__((aligned(16))) float part[NP][2][SLAB];  // [wave or pixel lane][sum | sum of squares][channel of the slab]
+  __shared__ __attribute__((aligned(16))) float part[NP][SLAB];  // [wave or pixel lane][channel of the slab]
   __shared__ float gst[32][2];
   const int slabs = C / SLAB;
   const int b = blockIdx.x / slabs, cbase = (blockIdx.x % slabs) * SLAB;
@@ -240,71 +263,79 @@ __global__ __launch_bounds__(256) void gn_fwd_fused_k(const bf16_t* __restrict__
     sc[e] = fs ? bf2f(fs[(int64_t)b * ldf + c0 + e]) : 0.f;
     sh[e] = fs ? bf2f(fh[(int64_t)b * ldf + c0 + e]) : 0.f;
   }
-  float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int i = 0; i < KEEP; ++i) {
-    if (pl + i * PL < HW && live) {
-      float v[8];
-      unpack8(xk[i], v);
+  // per-channel sums of this thread -> sum over the group, on all 8 threads of the group (8 threads per group, <= 32 groups per slab):
+  // the pixel lanes of a wave meet in shuffles, the waves (or the 21 pixel lanes) leave partial rows in LDS (plain stores, no LDS
+  // atomics), the group's threads add them up and meet in three shuffles.  Called twice; the barrier before the partials are read
+  // and the one the caller places before the next call keep the two uses of `part` apart.
+  const int g = threadIdx.x >> 3, k = threadIdx.x & 7;
+  auto group_sum = [&](float(&a)[8]) -> float {
+    if constexpr (POW2) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        s[e] += v[e];
-        q[e] += v[e] * v[e];
+#pragma unroll
+        for (int m = NCH; m < 64; m <<= 1) a[e] += __shfl_xor(a[e], m);
       }
     }
-  }
-  if constexpr (POW2) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-#pragma unroll
-      for (int m = NCH; m < 64; m <<= 1) {
-        s[e] += __shfl_xor(s[e], m);
-        q[e] += __shfl_xor(q[e], m);
-      }
+    if (POW2 ? (int)(threadIdx.x & 63) < NCH : live) {
+      const int row = POW2 ? wave : pl;
+      *(f32x4_t*)&part[row][chunk * 8] = f32x4_t{a[0], a[1], a[2], a[3]};
+      *(f32x4_t*)&part[row][chunk * 8 + 4] = f32x4_t{a[4], a[5], a[6], a[7]};
     }
-  }
-  if (POW2 ? (int)(threadIdx.x & 63) < NCH : live) {  // (partial sums in LDS rows of their own: plain stores, no LDS atomics)
-    const int row = POW2 ? wave : pl;
-    *(f32x4_t*)&part[row][0][chunk * 8] = f32x4_t{s[0], s[1], s[2], s[3]};
-    *(f32x4_t*)&part[row][0][chunk * 8 + 4] = f32x4_t{s[4], s[5], s[6], s[7]};
-    *(f32x4_t*)&part[row][1][chunk * 8] = f32x4_t{q[0], q[1], q[2], q[3]};
-    *(f32x4_t*)&part[row][1][chunk * 8 + 4] = f32x4_t{q[4], q[5], q[6], q[7]};
-  }
-  __syncthreads();
-  {
-    const int g = threadIdx.x >> 3, k = threadIdx.x & 7;  // 8 threads per group (<= 32 groups per slab), three shuffles
-    float S = 0.f, Q = 0.f;
+    __syncthreads();
+    float S = 0.f;
     if (g < SLAB / cg)
       for (int j = k; j < cg; j += 8) {
-        const int i = g * cg + j;
 #pragma unroll
-        for (int r = 0; r < NP; ++r) {
-          S += part[r][0][i];
-          Q += part[r][1][i];
-        }
+        for (int r = 0; r < NP; ++r) S += part[r][g * cg + j];
       }
 #pragma unroll
-    for (int m = 1; m < 8; m <<= 1) {
-      S += __shfl_xor(S, m);
-      Q += __shfl_xor(Q, m);
+    for (int m = 1; m < 8; m <<= 1) S += __shfl_xor(S, m);
+    return S;
+  };
+  const float n = (float)HW * cg;
+  float mu[8], rs[8];
+  {  // pass 1: the mean
+    float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < KEEP; ++i) {
+      if (pl + i * PL < HW && live) {
+        float v[8];
+        unpack8(xk[i], v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] += v[e];
+      }
     }
+    const float S = group_sum(s);
+    if (k == 0 && g < SLAB / cg) gst[g][0] = S / n;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mu[e] = gst[(chunk * 8 + e) / cg][0];
+  }
+  {  // pass 2: the centred second moment, from the rows in registers
+    float q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < KEEP; ++i) {
+      if (pl + i * PL < HW && live) {
+        float v[8];
+        unpack8(xk[i], v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = v[e] - mu[e];
+          q[e] += d * d;
+        }
+      }
+    }
+    const float Q = group_sum(q);
     if (k == 0 && g < SLAB / cg) {
-      const float n = (float)HW * cg;
-      const float mu = S / n;
-      const float r = rsqrtf(fmaxf(Q / n - mu * mu, 0.f) + eps);
-      gst[g][0] = mu;
+      const float r = rsqrtf(Q / n + eps);
       gst[g][1] = r;
       float* sg = st + ((int64_t)b * G + cbase / cg + g) * 2;
-      sg[0] = mu;
+      sg[0] = gst[g][0];
       sg[1] = r;
     }
-  }
-  __syncthreads();
-  float mu[8], rs[8];
+    __syncthreads();
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    mu[e] = gst[(chunk * 8 + e) / cg][0];
-    rs[e] = gst[(chunk * 8 + e) / cg][1];
+    for (int e = 0; e < 8; ++e) rs[e] = gst[(chunk * 8 + e) / cg][1];
   }
 #pragma unroll
   for (int i = 0; i < KEEP; ++i) {
@@ -336,6 +367,7 @@ extern "C" int dl_gn_fwd(const void* x, const float* w, const float* b, const vo
   DL_CHECK_ARG(B < 65536 && HW * C / 8 < (1ll << 31), "dl_gn_fwd: B < 65536, HW*C/8 < 2^31");
   const int64_t cg = C / G;
 #define GN_FWD_LAUNCH(NCH_, KEEP_)                                                                                                    \
+  gn_note_path(GN_FWD_FUSED_##NCH_##_##KEEP_);                                                                                        \
   hipLaunchKernelGGL((gn_fwd_fused_k<NCH_, KEEP_>), dim3((unsigned)(B * (C / (NCH_ * 8)))), 256, 0, (hipStream_t)stream,              \
                      (const bf16_t*)x, w, b, (const bf16_t*)film_scale, (const bf16_t*)film_shift, ld_film, act_silu, (bf16_t*)out,   \
                      stats, (int)HW, (int)C, (int)G, eps)
@@ -348,15 +380,22 @@ extern "C" int dl_gn_fwd(const void* x, const float* w, const float* b, const vo
       return DL_OK;
     }
     if (C % 96 == 0 && 96 % cg == 0 && 128 % cg != 0 && HW <= 21 * 12) {  // 12 / 24 / 48 channels per group: 96-channel slabs, 21 pixel lanes
-      if (HW <= 84) GN_FWD_LAUNCH(12, 4);
-      else GN_FWD_LAUNCH(12, 12);
+      if (HW <= 84) {
+        GN_FWD_LAUNCH(12, 4);
+      } else {
+        GN_FWD_LAUNCH(12, 12);
+      }
       DL_LAUNCH_CHECK();
       return DL_OK;
     }
     if (C % 64 == 0 && 64 % cg == 0 && 64 / cg <= 32 && HW <= 1024) {
-      if (HW <= 128) GN_FWD_LAUNCH(8, 4);
-      else if (HW <= 256) GN_FWD_LAUNCH(8, 8);
-      else GN_FWD_LAUNCH(8, 32);
+      if (HW <= 128) {
+        GN_FWD_LAUNCH(8, 4);
+      } else if (HW <= 256) {
+        GN_FWD_LAUNCH(8, 8);
+      } else {
+        GN_FWD_LAUNCH(8, 32);
+      }
       DL_LAUNCH_CHECK();
       return DL_OK;
     }
@@ -808,6 +847,7 @@ extern "C" int dl_gn_bwd(const void* dout, const void* x, const float* stats, co
     // 128-channel slabs (whole groups), 16 pixel lanes: four times the workgroups of the 512-channel form below -- at B = 128 that
     // one launches 128-384 workgroups of 4-16 serial pixel iterations on a 256-CU chip (54 us for 40 MB of traffic)
     const GnFused fz{dw, db, (bf16_t*)dfilm_scale, (bf16_t*)dfilm_shift, ld_dfilm, (const bf16_t*)dres, (bf16_t*)dx};
+    gn_note_path(GN_BWD_FUSED_16_4);
     hipLaunchKernelGGL((gn_bwd_fused_k<16, 4>), dim3((unsigned)(B * (C / 128)), 1u), 256, 0, (hipStream_t)stream,
                        (const bf16_t*)dout, (const bf16_t*)x, stats, w, b, (const bf16_t*)film_scale, (const bf16_t*)film_shift,
                        ld_film, act_silu, (int)B, (int)HW, (int)C, (int)G, fz);
@@ -819,6 +859,7 @@ extern "C" int dl_gn_bwd(const void* dout, const void* x, const float* stats, co
     // reduce (pixel ranges) + group sums + apply; the second pass re-reads the slab's x / dout (up to 2 x 128 KB) through L2 / MALL
     const GnFused fz{dw, db, (bf16_t*)dfilm_scale, (bf16_t*)dfilm_shift, ld_dfilm, (const bf16_t*)dres, (bf16_t*)dx};
     // (rows kept in registers -- KEEP = 8 at 16 x 16 -- cost the second wave per SIMD: 42 vs 25 us; both passes stream)
+    gn_note_path(GN_BWD_FUSED_8_0);
     hipLaunchKernelGGL((gn_bwd_fused_k<8, 0>), dim3((unsigned)(B * (C / 64)), 1u), 256, 0, (hipStream_t)stream,
                        (const bf16_t*)dout, (const bf16_t*)x, stats, w, b, (const bf16_t*)film_scale, (const bf16_t*)film_shift,
                        ld_film, act_silu, (int)B, (int)HW, (int)C, (int)G, fz);
@@ -829,6 +870,7 @@ extern "C" int dl_gn_bwd(const void* dout, const void* x, const float* stats, co
       (gn_bwd_fused() & 1)) {
     // 12 / 24 / 48 channels per group (C = 384 / 768 / 1536, the concatenated inputs of the output blocks): 96-channel slabs
     const GnFused fz{dw, db, (bf16_t*)dfilm_scale, (bf16_t*)dfilm_shift, ld_dfilm, (const bf16_t*)dres, (bf16_t*)dx};
+    gn_note_path(HW <= 84 ? GN_BWD_FUSED_12_4 : GN_BWD_FUSED_12_0);
     if (HW <= 84)
       hipLaunchKernelGGL((gn_bwd_fused_k<12, 4>), dim3((unsigned)(B * (C / 96)), 1u), 256, 0, (hipStream_t)stream,
                          (const bf16_t*)dout, (const bf16_t*)x, stats, w, b, (const bf16_t*)film_scale, (const bf16_t*)film_shift,
@@ -842,6 +884,7 @@ extern "C" int dl_gn_bwd(const void* dout, const void* x, const float* stats, co
   }
   if (HW <= 64 && C >= 512 && 512 % (C / G) == 0 && 512 / (C / G) <= 32 && gn_bwd_fused()) {
     const GnFused fz{dw, db, (bf16_t*)dfilm_scale, (bf16_t*)dfilm_shift, ld_dfilm, (const bf16_t*)dres, (bf16_t*)dx};
+    gn_note_path(GN_BWD_FUSED_64_0);
     hipLaunchKernelGGL((gn_bwd_fused_k<64, 0>), dim3((unsigned)(B * ((C + 511) / 512)), 1u), 256, 0, (hipStream_t)stream,
                        (const bf16_t*)dout, (const bf16_t*)x, stats, w, b, (const bf16_t*)film_scale, (const bf16_t*)film_shift,
                        ld_film, act_silu, (int)B, (int)HW, (int)C, (int)G, fz);
@@ -849,11 +892,13 @@ extern "C" int dl_gn_bwd(const void* dout, const void* x, const float* stats, co
     return DL_OK;
   }
   if (HW <= 64 && C >= 512) {
+    gn_note_path(GN_BWD_REDUCE_64);
     hipLaunchKernelGGL((gn_bwd_reduce_k<64>), dim3((unsigned)(B * ((C + 511) / 512)), 1u), 256, 0, (hipStream_t)stream,
                        (const bf16_t*)dout, (const bf16_t*)x, stats, w, b, (const bf16_t*)film_scale, (const bf16_t*)film_shift,
                        ld_film, act_silu, Sp, (int)B, (int)HW, (int)C, (int)G);
   } else {
     ns = gn_bwd_ranges(B, HW, C);
+    gn_note_path(GN_BWD_REDUCE_8);
     hipLaunchKernelGGL((gn_bwd_reduce_k<8>), dim3((unsigned)(B * ((C + 63) / 64)), (unsigned)ns), 256, 0, (hipStream_t)stream,
                        (const bf16_t*)dout, (const bf16_t*)x, stats, w, b, (const bf16_t*)film_scale, (const bf16_t*)film_shift,
                        ld_film, act_silu, Sp, (int)B, (int)HW, (int)C, (int)G);

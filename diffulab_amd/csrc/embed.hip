@@ -150,6 +150,57 @@ extern "C" int dl_cond_combine_bwd(const float* dact, const float* emb, const in
   return DL_OK;
 }
 
+// ---------------------------------------------------------------- emb = e + pe (dense addend); act = silu(emb)
+// the pooled-context form of the combine (mmdit.py:800-806): pe = mlp_pooled_context(pooled) is an f32 [B, E] matrix, not a table
+// row.  Contiguous [B, E] operands, four elements per thread (E % 4 == 0).
+__global__ void cond_combine_dense_fwd_k(const float* __restrict__ e, const float* __restrict__ pe, float* __restrict__ emb,
+                                         bf16_t* __restrict__ act, int64_t n4) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 a = ((const float4*)e)[i], p = ((const float4*)pe)[i];
+    const float4 v = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
+    ((float4*)emb)[i] = v;
+    ((uint2*)act)[i] = make_uint2((uint32_t)f2bf(silu_f(v.x)) | ((uint32_t)f2bf(silu_f(v.y)) << 16),
+                                  (uint32_t)f2bf(silu_f(v.z)) | ((uint32_t)f2bf(silu_f(v.w)) << 16));
+  }
+}
+extern "C" int dl_cond_combine_dense_fwd(const float* e, const float* pe, float* emb, void* act, int64_t B, int64_t E,
+                                         dl_stream_t stream) {
+  DL_CHECK_ARG(e && pe && emb && act && B > 0 && E > 0 && E % 4 == 0 && ((uintptr_t)e | (uintptr_t)pe | (uintptr_t)emb) % 16 == 0 &&
+                   (uintptr_t)act % 8 == 0,
+               "dl_cond_combine_dense_fwd: contiguous [B, E] operands, E a multiple of 4 (E=%lld), f32 operands 16-byte, act 8-byte aligned",
+               (long long)E);
+  const int64_t n4 = B * E / 4;
+  int64_t g = (n4 + 255) / 256;
+  if (g > 1024) g = 1024;
+  hipLaunchKernelGGL(cond_combine_dense_fwd_k, (int)g, 256, 0, (hipStream_t)stream, e, pe, emb, (bf16_t*)act, n4);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+// demb = dact * silu'(emb), once: the f32 copy feeds the bias column sums of both MLPs (time, pooled context), the bf16 copy
+// is the operand of their weight- and data-gradient GEMMs
+__global__ void cond_combine_dense_bwd_k(const float* __restrict__ dact, const float* __restrict__ emb, float* __restrict__ demb,
+                                         bf16_t* __restrict__ demb16, int64_t n4) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 d = ((const float4*)dact)[i], v = ((const float4*)emb)[i];
+    const float4 g = make_float4(d.x * dsilu_f(v.x), d.y * dsilu_f(v.y), d.z * dsilu_f(v.z), d.w * dsilu_f(v.w));
+    ((float4*)demb)[i] = g;
+    ((uint2*)demb16)[i] = make_uint2((uint32_t)f2bf(g.x) | ((uint32_t)f2bf(g.y) << 16), (uint32_t)f2bf(g.z) | ((uint32_t)f2bf(g.w) << 16));
+  }
+}
+extern "C" int dl_cond_combine_dense_bwd(const float* dact, const float* emb, float* demb, void* demb_bf16, int64_t B, int64_t E,
+                                         dl_stream_t stream) {
+  DL_CHECK_ARG(dact && emb && demb && demb_bf16 && B > 0 && E > 0 && E % 4 == 0 &&
+                   ((uintptr_t)dact | (uintptr_t)emb | (uintptr_t)demb) % 16 == 0 && (uintptr_t)demb_bf16 % 8 == 0,
+               "dl_cond_combine_dense_bwd: contiguous [B, E] operands, E a multiple of 4 (E=%lld), f32 operands 16-byte, bf16 8-byte aligned",
+               (long long)E);
+  const int64_t n4 = B * E / 4;
+  int64_t g = (n4 + 255) / 256;
+  if (g > 1024) g = 1024;
+  hipLaunchKernelGGL(cond_combine_dense_bwd_k, (int)g, 256, 0, (hipStream_t)stream, dact, emb, demb, (bf16_t*)demb_bf16, n4);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
 __global__ void silu_bwd_k(const float* __restrict__ dy, const bf16_t* __restrict__ pre, bf16_t* __restrict__ dx,
                            int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

@@ -234,14 +234,21 @@ from .sprint_joint_engine import SprintJointEngine  # noqa: E402
 class DDTJointDims(JointDims):
     encoder_depth: int = 8
     decoder_depth: int = 4
+    n_single_stream_blocks: int = 0  # the last encoder blocks that are MMDiTSingleStreamBlocks (ddt.py:169-199)
 
     def __post_init__(self) -> None:
         self.embedding_dim = self.inner_dim
         super().__post_init__()
         self.depth = self.encoder_depth + self.decoder_depth
 
+    def validate(self) -> None:
+        assert self.n_single_stream_blocks < self.encoder_depth, "n_single_stream_blocks must be less than encoder_depth"
+        super().validate()
+
     def kinds(self) -> list[tuple[str, str]]:
-        return ([(f"layers.{i}.", "J") for i in range(self.encoder_depth)]
+        """(state_dict prefix, 'J' joint | 'S' single-stream | 'D' per-token decoder block) of every block in execution order"""
+        nj = self.encoder_depth - self.n_single_stream_blocks
+        return ([(f"layers.{i}.", "J" if i < nj else "S") for i in range(self.encoder_depth)]
                 + [(f"decoder_layers.{i}.", "D") for i in range(self.decoder_depth)])
 
 
@@ -251,26 +258,21 @@ class DDTJointLayout(ArenaLayout):
         E, F = D, d.mlp_ratio * D
         kinds = d.kinds()
         self.prefixes = [pre for pre, _ in kinds]
-        enc = [pre for pre, k in kinds if k == "J"]
         dec = [pre for pre, k in kinds if k == "D"]
-        for suffix, shp in (("weight", lambda r: (r, E)), ("bias", lambda r: (r,))):
-            first = True
-            for pre in enc:  # per-sample adaLN of the joint encoder blocks: [input 6D | context 6D] each
-                for st in STREAMS:
-                    add(pre + f"modulation_{st}.lin." + suffix, shp(6 * D), align=64 if first else 1)
-                    first = False
+        # per-sample adaLN of the encoder blocks: [input 6D | context 6D] per joint block, 3D per single-stream block
+        self.add_stacked_adaln([(pre, k) for pre, k in kinds if k != "D"], D, E, last_layer=False)
         for suffix, shp in (("weight", lambda r: (r, E)), ("bias", lambda r: (r,))):
             for i, pre in enumerate(dec):  # per-token adaLN of the decoder blocks + last layer
                 add(pre + "modulation.lin." + suffix, shp(6 * D), align=1 if i else 64)
             add("last_layer.adaLN_modulation.1." + suffix, shp(2 * D), align=1)
-        self.mod_off = [i * 12 * D for i in range(len(enc))] + [0] * len(dec)
-        self.mod_rows, self.tmod_rows = len(enc) * 12 * D, len(dec) * 6 * D + 2 * D
-        self.mod_w0, self.mod_b0 = enc[0] + "modulation_input.lin.weight", enc[0] + "modulation_input.lin.bias"
+        self.mod_off += [0] * len(dec)
+        self.tmod_rows = len(dec) * 6 * D + 2 * D
         self.tmod_w0, self.tmod_b0 = dec[0] + "modulation.lin.weight", dec[0] + "modulation.lin.bias"
         add("time_embed.0.weight", (E, d.frequency_embedding))
         add("time_embed.0.bias", (E,))
         add("time_embed.2.weight", (E, E))
         add("time_embed.2.bias", (E,))
+        self.add_pooled_mlp(d.pooled_dim, E)
         add("conv_proj_encoder.weight", (D, d.input_channels, p, p))
         add("conv_proj_decoder.weight", (D, d.input_channels, p, p))
         add("context_embed.weight", (D, d.context_dim))
@@ -281,6 +283,9 @@ class DDTJointLayout(ArenaLayout):
             if kind == "J":
                 self.block_first.append(pre + "input_norm_1.weight")
                 self.add_joint_block(pre, D, F)
+            elif kind == "S":
+                self.block_first.append(pre + "norm.weight")
+                self.add_single_block(pre, D, F)
             else:
                 self.block_first.append(pre + "norm_1.weight")
                 self.add_dit_block(pre, D, F)
@@ -304,7 +309,7 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
         reg("@tmod", self.layout.tmod_rows, d.inner_dim)
 
     def _block_shadows(self, reg, pre: str) -> None:
-        if dict(self.kinds)[pre] == "J":
+        if dict(self.kinds)[pre] != "D":
             SprintJointEngine._block_shadows(self, reg, pre)
         else:
             super(SprintJointEngine, self)._block_shadows(reg, pre)  # DiT block names
@@ -347,6 +352,9 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
                 per = self._joint_attn_buffers(B, Tpf)
                 for st, nt in (("input", N), ("context", Lc)):
                     per[st] = self._joint_stream_buffers(B, nt, train)
+            elif kind == "S":
+                per = self._joint_attn_buffers(B, Tpf)
+                per.update(self._single_stream_buffers(B, Tf, train))
             else:
                 per = self._dit_block_buffers(B, N, train, nq=Nd)
                 if pad:
@@ -361,7 +369,15 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
         w["xdec_in"], w["enc_out"], w["sz"] = z(M, D), z(M, D), z(M, D)
         w["tmod"] = z(M, R)
         w["xl"] = z(M, D)
+        ns = d.n_single_stream_blocks
+        if ns:  # outputs of the joint sub-stage, the concatenated [context ; image] latents into / out of the single-stream stage
+            w["xj"], w["cj"] = z(M, D), zr(B * Lc, D)
+            w["lat0"], w["lat_out"] = zr(B * Tf, D), zr(B * Tf, D)
         if train:
+            if ns:
+                w["s_l"] = {"dxa": zr(B * Tf, D), "dxb": zr(B * Tf, D), "dxm": zr(B * Tf, D), "dxm2": zr(B * Tf, D), "da": zr(B * Tf, D),
+                            "dh": zr(B * Tf, F)}
+                w["dlat"], w["dxj"], w["dcj"] = zr(B * Tf, D), z(M, D), zr(B * Lc, D)
             w[f"s_x{N}"] = {"dxa": z(M, D), "dxb": z(M, D), "dxm": z(M, D), "dxm2": z(M, D), "da": z(M, D), "dh": z(M, F),
                             "dq": z(B, Hh, Nd, 64), "dk": z(B, Hh, Nd, 64), "dv": z(B, Hh, Nd, 64)}
             if pad:
@@ -402,28 +418,53 @@ class DDTJointEngine(SprintJointEngine, PerTokenDecoder):
             kb[:, :Lc].zero_()
         else:
             kb[:, :Lc].zero_().masked_fill_(~keep.to(device=kb.device, dtype=torch.bool), float("-inf"))
-        self._jstage_fwd(range(0, ne), w["x"][0], w["c0"], N, None, kb, w["enc_out"], None)
+        nj = ne - d.n_single_stream_blocks
+        if nj == ne:
+            self._jstage_fwd(range(0, ne), w["x"][0], w["c0"], N, None, kb, w["enc_out"], None)
+        else:  # encode_mmddt (ddt.py:352-406): joint blocks, then single-stream blocks on [context ; image]; the decoder is
+            T = Lc + N  # conditioned on the image rows of the concatenated latents
+            self._jstage_fwd(range(0, nj), w["x"][0], w["c0"], N, None, kb, w["xj"], w["cj"])
+            lat0 = w["lat0"]
+            ops.copy_rows3d(w["cj"], Lc * D, D, lat0, T * D, D, B, Lc, D)
+            ops.copy_rows3d(w["xj"], N * D, D, lat0[Lc:], T * D, D, B, N, D)
+            self._sstage_fwd(range(nj, ne), lat0, T, None, kb, w["lat_out"])
+            ops.copy_rows3d(w["lat_out"][Lc:], T * D, D, w["enc_out"], N * D, D, B, N, D)
         cos, sin = self._tabs
         return self._decoder_fwd(ne, d.decoder_depth, cos[Lc:], sin[Lc:])
 
     def feature(self, kblk: int) -> Tensor:
         assert self._train and 0 <= kblk < self.d.encoder_depth
         B, N, D = self.geo[0], self.geo[5], self.d.inner_dim
-        if kblk + 1 < self.d.encoder_depth:
+        ne, nj = self.d.encoder_depth, self.d.encoder_depth - self.d.n_single_stream_blocks
+        if kblk + 1 < nj:
             return self.ws["blk"][kblk + 1]["input"]["x0"].view(B, N, D)
-        return self.ws["enc_out"].view(B, N, D)
+        if kblk + 1 == nj:
+            return (self.ws["enc_out"] if nj == ne else self.ws["xj"]).view(B, N, D)
+        raise NotImplementedError("forward hooks on single-stream blocks (the image rows live inside the concatenated latents)")
 
     def backward(self, dpred: Tensor, dfeats: dict[int, Tensor] | None = None) -> None:
         assert self._train and self.grads is not None
         d, w = self.d, self.ws
         B, H, W, gh, gw, N, M, Bp, Fo = self.geo
         D, Cd, ne, Lc = d.inner_dim, d.context_dim, d.encoder_depth, self._Lc
+        nj = ne - d.n_single_stream_blocks
         dfe = self._dfeat_rows(dfeats)
         cos, sin = self._tabs
         w["dmod32"][:B].zero_()
         sw = SideWork(self)
         denc = self._decoder_bwd(dpred, ne, d.decoder_depth, cos[Lc:], sin[Lc:], w[f"s_x{N}"], sw)
-        dx0, dc0 = self._jstage_bwd(range(0, ne), denc, None, N, None, w["kb_f"], *self._jscratch(N, "f"), dfe, sw)
+        scr, attn = self._jscratch(N, "f")
+        gx, gc = denc, None
+        if nj < ne:  # the gradient of the image rows flows back into the concatenated latents; their context rows feed nothing
+            T = Lc + N
+            dlat = w["dlat"]
+            dlat.zero_()
+            ops.copy_rows3d(denc, N * D, D, dlat[Lc:], T * D, D, B, N, D)
+            dl = self._sstage_bwd(range(nj, ne), dlat, T, None, w["kb_f"], sw, attn=attn)
+            ops.copy_rows3d(dl[Lc:], T * D, D, w["dxj"], N * D, D, B, N, D)
+            ops.copy_rows3d(dl, T * D, D, w["dcj"], Lc * D, D, B, Lc, D)
+            gx, gc = w["dxj"], w["dcj"]
+        dx0, dc0 = self._jstage_bwd(range(0, nj), gx, gc, N, None, w["kb_f"], scr, attn, dfe, sw)
         sw.join()
         ops.gemm_tn(dc0, w["ctxP"], self.G("context_embed.weight"), M=D, N=Cd)
         self._cond_bwd(dx0, extra_demb=w["dtemb"])

@@ -208,6 +208,55 @@ class ArenaLayout:
             self.add(pre + f"mlp_{st}.0.weight", (2 * F, D))
             self.add(pre + f"mlp_{st}.2.weight", (D, F))
 
+    def add_single_block(self, pre: str, D: int, F: int) -> None:
+        """the parameters of an MMDiTSingleStreamBlock except its adaLN linear"""
+        self.add(pre + "norm.weight", (D,))
+        self.add(pre + "norm.bias", (D,), align=1)
+        self.add(pre + "attention.qk_norm.query_norm.scale", (D,))
+        self.add(pre + "attention.qk_norm.key_norm.scale", (D,), align=1)
+        self.add(pre + "attention.qkv.weight", (3 * D, D))
+        self.add(pre + "attention.proj_out.weight", (D, D))
+        self.add(pre + "mlp.0.weight", (2 * F, D))
+        self.add(pre + "mlp.2.weight", (D, F))
+
+    def add_stacked_adaln(self, kinds: list[tuple[str, str]], D: int, E: int, last_layer: bool) -> None:
+        """the per-sample adaLN linears of the blocks `kinds` ((prefix, 'J' joint | 'S' single-stream)) back to back as ONE
+        [mod_rows, E] matrix, then their biases: [input 6D | context 6D] per joint block, 3D per single-stream block, then
+        (last_layer) the last layer's 2D rows.  Sets mod_off (first modulation column of every block), mod_rows, mod_w0 / mod_b0"""
+        def mods(suffix: str, width) -> list:
+            names = []
+            for pre, kind in kinds:
+                if kind == "J":
+                    names += [(pre + f"modulation_{st}.lin.{suffix}", width(6)) for st in STREAMS]
+                else:
+                    names.append((pre + f"modulation.1.{suffix}", width(3)))
+            return names
+
+        self.mod_off, off = [], 0
+        for _, kind in kinds:
+            self.mod_off.append(off)
+            off += (12 if kind == "J" else 3) * D
+        self.mod_rows = off + (2 * D if last_layer else 0)
+        for suffix, width in (("weight", lambda r: (r * D, E)), ("bias", lambda r: (r * D,))):
+            names = mods(suffix, width)
+            for i, (n, shp) in enumerate(names):
+                self.add(n, shp, align=1 if i else 64)
+            if suffix == "weight":
+                self.mod_w0 = names[0][0]
+            else:
+                self.mod_b0 = names[0][0]
+            if last_layer:
+                self.add("last_layer.adaLN_modulation.1." + suffix, width(2), align=1)
+
+    def add_pooled_mlp(self, P: int, E: int) -> None:
+        """mlp_pooled_context = Linear(P, 2E) -> SiLU -> Linear(2E, E) of a joint form behind a two-output context embedder
+        (mmdit.py:650-657); P = 0: the embedder has no pooled output and nothing is placed"""
+        if P:
+            self.add("mlp_pooled_context.0.weight", (2 * E, P))
+            self.add("mlp_pooled_context.0.bias", (2 * E,))
+            self.add("mlp_pooled_context.2.weight", (E, 2 * E))
+            self.add("mlp_pooled_context.2.bias", (E,))
+
     def view(self, flat: Tensor, name: str) -> Tensor:
         off, shape = self.entries[name]
         return flat[off : off + math.prod(shape)].view(shape)
@@ -250,6 +299,7 @@ class ParamLayout(ArenaLayout):
 
 class DiTEngine:
     _conv_name = "conv_proj.weight"  # patch-embedding convolution of the (encoder) token stream
+    pooled: Tensor | None = None  # pooled context embedding [B, pooled_dim] of this step (joint forms with dims.pooled_dim > 0)
 
     def __init__(self, dims: DiTDims, device: torch.device | str = "cuda") -> None:
         dims.validate()
@@ -257,6 +307,7 @@ class DiTEngine:
         self.dev = torch.device(device)
         self._ki = _rup(dims.input_channels * dims.patch_size**2, 64)   # K of the patch-embedding GEMM (zero-padded)
         self._ko = _rup(dims.output_channels * dims.patch_size**2, 64)  # K of the last linear's data gradient
+        self._pooled_dim = getattr(dims, "pooled_dim", 0)  # width of the pooled context embedding (joint forms; 0: none)
         self.layout = self._make_layout(dims)
         self.prefixes = self.layout.prefixes
         self.params: Tensor | None = None
@@ -320,6 +371,9 @@ class DiTEngine:
         reg("@mod", self.layout.mod_rows, E)
         reg("time_embed.0.weight", E, d.frequency_embedding, dgrad=False)
         reg("time_embed.2.weight", E, E)
+        if self._pooled_dim:
+            reg("mlp_pooled_context.0.weight", 2 * E, self._pooled_dim, dgrad=False)
+            reg("mlp_pooled_context.2.weight", E, 2 * E)
         reg(self._conv_name, D, d.input_channels * d.patch_size**2, dgrad=False)
         reg("last_layer.linear.weight", d.patch_size**2 * d.output_channels, D)
         self._extra_shadows(reg)
@@ -414,6 +468,10 @@ class DiTEngine:
         w["temb"], w["pre1"], w["h1"] = z(Bp, d.frequency_embedding), z(Bp, E), z(Bp, E)
         w["e"], w["emb"], w["se"] = z(Bp, E, dtype=f32), z(Bp, E, dtype=f32), z(Bp, E)
         w["mod"] = z(Bp, R)
+        if self._pooled_dim:  # mlp_pooled_context: zero-padded input, hidden pre-activation / activation, f32 output
+            w["poolP"], w["ppre1"], w["ph1"], w["pe"] = z(Bp, _rup(self._pooled_dim, 64)), z(Bp, 2 * E), z(Bp, 2 * E), z(Bp, E, dtype=f32)
+            if train:
+                w["dph1"], w["dppre1"] = z(Bp, 2 * E, dtype=f32), z(Bp, 2 * E)
         w["meanf"], w["rstdf"], w["xf"] = z(M, dtype=f32), z(M, dtype=f32), z(M, D)
         w["otok"] = z(M, _rup(Fo, 8), dtype=f32)
         w["pred"] = z(B, d.output_channels, H, W, dtype=f32)
@@ -571,11 +629,39 @@ class DiTEngine:
         ops.gemm_nt(w["temb"], sh["time_embed.0.weight|f"], w["h1"], bias=self.P("time_embed.0.bias"), act=ops.ACT_SILU,
                     pre_out=w["pre1"], M=B, N=E, K=d.frequency_embedding)
         ops.gemm_nt(w["h1"], sh["time_embed.2.weight|f"], w["e"], bias=self.P("time_embed.2.bias"), M=B, N=E, K=E)
-        table = self.P("label_embed.embedding.weight") if d.n_classes is not None else None
-        ops.cond_combine_fwd(w["e"][:B], table, y_eff if table is not None else None, w["emb"][:B], w["se"][:B])
+        if self._pooled_dim:
+            self._pooled_fwd(B)
+        else:
+            table = self.P("label_embed.embedding.weight") if d.n_classes is not None else None
+            ops.cond_combine_fwd(w["e"][:B], table, y_eff if table is not None else None, w["emb"][:B], w["se"][:B])
         mod_bias = self.params[self.layout.entries[self.layout.mod_b0][0] :][: self.layout.mod_rows]
         ops.gemm_nt(w["se"], sh["@mod|f"], w["mod"], bias=mod_bias, M=B, N=self.layout.mod_rows, K=E)
         return w["mod"]
+
+    def _pooled_fwd(self, B: int) -> None:
+        """emb = mlp_pooled_context(pooled) + time embedding (mmdit.py:800-806) and its SiLU: the two linears as small-M GEMMs like
+        the time MLP's, the add and the SiLU in the dense combine kernel"""
+        d, w, sh = self.d, self.ws, self.sh
+        E, P = d.embedding_dim, self._pooled_dim
+        pooled = self.pooled
+        assert pooled is not None and tuple(pooled.shape) == (B, P), "pooled context embedding [B, pooled_dim] not set for this step"
+        w["poolP"][:B, :P].copy_(pooled)
+        ops.gemm_nt(w["poolP"], sh["mlp_pooled_context.0.weight|f"], w["ph1"], bias=self.P("mlp_pooled_context.0.bias"), act=ops.ACT_SILU,
+                    pre_out=w["ppre1"], M=B, N=2 * E, K=w["poolP"].shape[1])
+        ops.gemm_nt(w["ph1"], sh["mlp_pooled_context.2.weight|f"], w["pe"], bias=self.P("mlp_pooled_context.2.bias"), M=B, N=E, K=2 * E)
+        ops.cond_combine_dense_fwd(w["e"][:B], w["pe"][:B], w["emb"][:B], w["se"][:B])
+
+    def _pooled_bwd(self, B: int, det: Tensor | None) -> None:
+        """backward of mlp_pooled_context from ws["demb"] / ws["demb16"] (the gradient of the combined embedding), gradients into
+        the arena through the same small GEMMs / column sums as the time MLP's"""
+        d, w, sh = self.d, self.ws, self.sh
+        E, P = d.embedding_dim, self._pooled_dim
+        ops.colsum(w["demb"], self.G("mlp_pooled_context.2.bias"), B, E, scratch=det)
+        ops.gemm_tn(w["demb16"], w["ph1"], self.G("mlp_pooled_context.2.weight"), scratch=det)
+        ops.gemm_nt(w["demb16"], sh["mlp_pooled_context.2.weight|t"], w["dph1"], M=B, N=2 * E, K=E)
+        ops.silu_bwd(w["dph1"][:B], w["ppre1"][:B], w["dppre1"][:B])
+        ops.gemm_tn(w["dppre1"], w["poolP"], self.G("mlp_pooled_context.0.weight"), M=2 * E, N=P, scratch=det)
+        ops.colsum(w["dppre1"], self.G("mlp_pooled_context.0.bias"), B, 2 * E, scratch=det)
 
     def _main_wgs(self) -> int:
         """workgroup budget of the persistent main-chain kernels (0 = one per CU).  DL_DP_RESERVE_CUS = r > 0: with a gradient reducer
@@ -1242,8 +1328,12 @@ class DiTEngine:
             ops.colsum(dmod, g_modb, B, R, scratch=det)
         ops.gemm_nt(dmod, sh["@mod|t"], w["dse"], M=B, N=E, K=R, scratch=det)
         table = d.n_classes is not None
-        ops.cond_combine_bwd(w["dse"][:B], w["emb"][:B], self._yeff if table else None, w["demb"][:B], w["demb16"][:B],
-                             self.G("label_embed.embedding.weight") if table else None)
+        if self._pooled_dim:  # demb reaches both MLPs; extra_demb (DDT's decoder) is a gradient of the time embedding alone
+            ops.cond_combine_dense_bwd(w["dse"][:B], w["emb"][:B], w["demb"][:B], w["demb16"][:B])
+            self._pooled_bwd(B, det)
+        else:
+            ops.cond_combine_bwd(w["dse"][:B], w["emb"][:B], self._yeff if table else None, w["demb"][:B], w["demb16"][:B],
+                                 self.G("label_embed.embedding.weight") if table else None)
         if extra_demb is not None:
             w["demb"][:B].add_(extra_demb[:B])
             ops.cast_f32_to_bf16(w["demb"][:B], w["demb16"][:B])

@@ -25,6 +25,7 @@ from .engine import ROW_MAX_DIM, STREAMS, ArenaLayout, DiTDims, DiTEngine, Modul
 @dataclass
 class JointDims(DiTDims):
     context_dim: int = 768
+    pooled_dim: int = 0  # width of the pooled context embedding (two-output embedder -> mlp_pooled_context); 0: none
 
     def __post_init__(self) -> None:
         if not self.rope_axes_dim:
@@ -43,6 +44,8 @@ class JointDims(DiTDims):
                                       f"a multiple of 8 and <= head_dim (got {self.rope_axes_dim})")
         if self.context_dim % 8:
             raise NotImplementedError("context embedding width must be a multiple of 8")
+        if self.pooled_dim % 8:
+            raise NotImplementedError(f"pooled context embedding width must be a multiple of 8 (got pooled_dim {self.pooled_dim})")
         if self.n_classes is not None:
             raise NotImplementedError("joint blocks are conditioned on a context embedder, not on class labels")
 
@@ -89,6 +92,7 @@ class JointLayout(ArenaLayout):
         add("time_embed.0.bias", (E,))
         add("time_embed.2.weight", (E, E))
         add("time_embed.2.bias", (E,))
+        self.add_pooled_mlp(d.pooled_dim, E)
         add("conv_proj.weight", (D, d.input_channels, p, p))
         add("context_embed.weight", (D, d.context_dim))
         add("last_layer.linear.weight", (p * p * d.output_channels, D))

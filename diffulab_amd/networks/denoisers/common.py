@@ -249,6 +249,54 @@ class FlatArenaDenoiser(Denoiser):
             self.flatten_parameters()
         return self._engine
 
+    # ---- joint text-image forms (MMDiT / SprintDiT simple_dit=False, DDT simple_ddt=False): the context embedder's side
+    def _build_context_embed(self, inner_dim: int, embedding_dim: int) -> tuple[int, int]:
+        """``context_embed`` and, behind a two-output embedder (token embeddings + one pooled vector per sample, SD3 style),
+        ``mlp_pooled_context``, registered as the reference registers them (mmdit.py:649-660, sprint.py:120-131, ddt.py:113-124):
+        ``output_size[0]`` is then the POOLED width and ``output_size[1]`` the token width.  Returns (context width, pooled width | 0)"""
+        ce = self.context_embedder
+        if any(True for _ in ce.parameters()):
+            raise NotImplementedError(f"diffulab_amd.{type(self).__name__}: the context embedder must be parameter-free (precomputed embeddings)")
+        self.pooled_embedding = False
+        self.mlp_pooled_context = None
+        if ce.n_output == 2:
+            self.pooled_embedding = True
+            self.mlp_pooled_context = nn.Sequential(nn.Linear(ce.output_size[0], embedding_dim * 2), nn.SiLU(),
+                                                    nn.Linear(embedding_dim * 2, embedding_dim))
+            self.context_embed = nn.Linear(ce.output_size[1], inner_dim, bias=False)
+            return ce.output_size[1], ce.output_size[0]
+        assert ce.n_output == 1
+        self.context_embed = nn.Linear(ce.output_size[0], inner_dim, bias=False)
+        return ce.output_size[0], 0
+
+    def _context_output(self, initial_context: Any, p: float) -> dict:
+        """the embedder's output for this call (its context drop for classifier-free guidance stays host-side torch), with the
+        reference's checks of the pooled form (mmdit.py:800-805)"""
+        assert self.context_embedder is not None, "for MMDiT context embedder must be provided"
+        out = self.context_embedder(initial_context, p)
+        if self.pooled_embedding:
+            assert self.mlp_pooled_context is not None, "for MMDiT with pooled context, mlp_pooled_context must be defined"
+            assert "pooled_embeddings" in out, "pooled embeddings must be in context_output"
+        return out
+
+    def _set_context(self, eng, out: dict) -> None:
+        """hand the per-call context tensors to the engine"""
+        dev = eng.dev
+        keep = out.get("attn_mask", None)
+        eng.context = (out["embeddings"].to(device=dev), keep.to(device=dev) if keep is not None else None)
+        if self.pooled_embedding:
+            eng.pooled = out["pooled_embeddings"].to(device=dev)
+
+    # (the context tensors -- and the pooled vector -- are per-call inputs of the joint launch sequence: a captured graph reads
+    # static copies of them)
+    def _joint_graph_inputs(self, eng) -> tuple:
+        return (*eng.context, eng.pooled) if self.pooled_embedding else tuple(eng.context)
+
+    def _joint_graph_set_inputs(self, eng, tensors: tuple) -> None:
+        eng.context = tuple(tensors[:2])
+        if self.pooled_embedding:
+            eng.pooled = tensors[2]
+
     # ---- classifier-free guidance: the conditional and the label-dropped forward of a sampler step as ONE forward
     cfg_pair_capable = False  # True where `p` reaches nothing but the label drop (class-conditional MMDiT / DDT / UNetModel)
 

@@ -1,6 +1,7 @@
 """``DDT`` denoiser, MI355X build -- drop-in for ``diffulab.networks.denoisers.ddt.DDT``: ``simple_ddt=True`` (the shipped
-``configs/model/ddt.yaml``) and the joint text-image encoder form (``simple_ddt=False`` behind a one-output context embedder,
-``n_single_stream_blocks == 0``; ``configs/train_imagenet_repa_txt_to_img.yaml``).  Same constructor kwargs (ddt.py:66-86), ``forward`` kwargs (ddt.py:466-475), ``state_dict`` keys
+``configs/model/ddt.yaml``) and the joint text-image encoder form (``simple_ddt=False`` behind a parameter-free context embedder,
+with or without a pooled vector per sample; MMDiTBlock encoder layers followed by ``n_single_stream_blocks``
+MMDiTSingleStreamBlocks; ``configs/train_imagenet_repa_txt_to_img.yaml``).  Same constructor kwargs (ddt.py:66-86), ``forward`` kwargs (ddt.py:466-475), ``state_dict`` keys
 (``conv_proj_encoder`` / ``conv_proj_decoder``, ``layers`` / ``decoder_layers``) and initialisation (ddt.py:222-230).  The module
 owns the parameters; the arithmetic is ``diffulab_amd.ddt_engine.DDTEngine`` / ``DDTJointEngine``.
 """
@@ -17,7 +18,7 @@ from torch import Tensor
 from ...ddt_engine import DDTDims, DDTEngine, DDTJointDims, DDTJointEngine
 from .common import FlatArenaDenoiser, ModelOutput
 from ...diffuse.utils import to_device
-from .mmdit import DiTBlock, MMDiT, MMDiTBlock, _LabelEmbed, _LastLayer
+from .mmdit import DiTBlock, MMDiT, MMDiTBlock, MMDiTSingleStreamBlock, _LabelEmbed, _LastLayer
 
 
 class DDT(FlatArenaDenoiser):
@@ -49,9 +50,7 @@ class DDT(FlatArenaDenoiser):
         assert n_single_stream_blocks < encoder_depth, "n_single_stream_blocks must be less than encoder_depth"
         if simple_ddt and context_embedder is not None:
             raise NotImplementedError("diffulab_amd.DDT: simple_ddt=True takes class labels, not a context embedder")
-        if n_single_stream_blocks > 0:
-            if not simple_ddt:
-                raise NotImplementedError("diffulab_amd.DDT: MMDiTSingleStreamBlock encoder layers are not built (n_single_stream_blocks=0)")
+        if n_single_stream_blocks > 0 and simple_ddt:
             logging.warning("n_single_stream_blocks is ignored when simple_ddt=True. All blocks are single-stream DiT blocks.")
         if encoder_depth < 1 or decoder_depth < 1:
             raise NotImplementedError("diffulab_amd.DDT: encoder and decoder need at least one block each")
@@ -67,7 +66,8 @@ class DDT(FlatArenaDenoiser):
         self.use_checkpoint = use_checkpoint
         heads_dim = inner_dim // num_heads
         if not simple_ddt:
-            self._init_joint(inner_dim, num_heads, mlp_ratio, encoder_depth, decoder_depth, rope_axes_dim, partial_rotary_factor, heads_dim)
+            self._init_joint(inner_dim, num_heads, mlp_ratio, encoder_depth, n_single_stream_blocks, decoder_depth, rope_axes_dim,
+                             partial_rotary_factor, heads_dim)
             return
         if rope_axes_dim is None:
             rope_axes_dim = [int((partial_rotary_factor * heads_dim) // 2)] * 2
@@ -87,20 +87,14 @@ class DDT(FlatArenaDenoiser):
         self.decoder_layers = nn.ModuleList([DiTBlock(inner_dim, inner_dim, mlp_ratio) for _ in range(decoder_depth)])
         self.apply(MMDiT._init_weights)
 
-    def _init_joint(self, inner_dim: int, num_heads: int, mlp_ratio: int, encoder_depth: int, decoder_depth: int,
+    def _init_joint(self, inner_dim: int, num_heads: int, mlp_ratio: int, encoder_depth: int, n_single: int, decoder_depth: int,
                     rope_axes_dim: list[int] | None, partial_rotary_factor: float, heads_dim: int) -> None:
-        """ddt.py:105-131,150-220 with a one-output context embedder"""
+        """ddt.py:105-131,150-220"""
         ce = self.context_embedder
         assert ce is not None, "for ddt with text context embedder must be provided"
         assert isinstance(ce.output_size, tuple) and all(isinstance(i, int) for i in ce.output_size), (
             "context_embedder.output_size must be a tuple of integers")
-        if ce.n_output != 1:
-            raise NotImplementedError("diffulab_amd.DDT: context embedders with a pooled embedding are not built")
-        if any(True for _ in ce.parameters()):
-            raise NotImplementedError("diffulab_amd.DDT: the context embedder must be parameter-free (precomputed embeddings)")
-        self.pooled_embedding = False
-        self.mlp_pooled_context = None
-        self.context_embed = nn.Linear(ce.output_size[0], inner_dim, bias=False)
+        context_dim, pooled_dim = self._build_context_embed(inner_dim, inner_dim)
         if rope_axes_dim is None:
             rope_axes_dim = [int((partial_rotary_factor * heads_dim) // 3)] * 3
         self.rope_axes_dim = list(rope_axes_dim)
@@ -108,14 +102,16 @@ class DDT(FlatArenaDenoiser):
                                  embedding_dim=inner_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, patch_size=self.patch_size,
                                  rope_base=float(self.rope_base), frequency_embedding=self.frequency_embedding, n_classes=None,
                                  classifier_free=self.classifier_free, rope_axes_dim=self.rope_axes_dim,
-                                 context_dim=ce.output_size[0], encoder_depth=encoder_depth, decoder_depth=decoder_depth)
+                                 context_dim=context_dim, pooled_dim=pooled_dim, encoder_depth=encoder_depth,
+                                 n_single_stream_blocks=n_single, decoder_depth=decoder_depth)
         self.dims.validate()
         self.label_embed = None
         self.last_layer = _LastLayer(inner_dim, inner_dim, self.patch_size, self.output_channels)
         self.time_embed = nn.Sequential(nn.Linear(self.frequency_embedding, inner_dim), nn.SiLU(), nn.Linear(inner_dim, inner_dim))
         mk = lambda: nn.Conv2d(self.input_channels, inner_dim, kernel_size=self.patch_size, stride=self.patch_size, bias=False)  # noqa: E731
         self.conv_proj_encoder, self.conv_proj_decoder = mk(), mk()
-        self.layers = nn.ModuleList([MMDiTBlock(inner_dim, inner_dim, mlp_ratio) for _ in range(encoder_depth)])
+        self.layers = nn.ModuleList([MMDiTBlock(inner_dim, inner_dim, mlp_ratio) for _ in range(encoder_depth - n_single)]
+                                    + [MMDiTSingleStreamBlock(inner_dim, inner_dim, mlp_ratio) for _ in range(n_single)])
         self.decoder_layers = nn.ModuleList([DiTBlock(inner_dim, inner_dim, mlp_ratio) for _ in range(decoder_depth)])
         self.apply(MMDiT._init_weights)
 
@@ -131,11 +127,11 @@ class DDT(FlatArenaDenoiser):
         return DDTEngine(self.dims, device) if self.simple_ddt else DDTJointEngine(self.dims, device)
 
     def _graph_inputs(self, eng) -> tuple:  # (the context tensors are per-call inputs of the joint launch sequence)
-        return () if self.simple_ddt else tuple(eng.context)
+        return () if self.simple_ddt else self._joint_graph_inputs(eng)
 
     def _graph_set_inputs(self, eng, tensors: tuple) -> None:
         if not self.simple_ddt:
-            eng.context = tuple(tensors)
+            self._joint_graph_set_inputs(eng, tensors)
 
     def forward(
         self,
@@ -160,16 +156,14 @@ class DDT(FlatArenaDenoiser):
                     "probability of dropping for classifier free guidance is only available if a number of classes is set")
         if x_context is not None:
             x = torch.cat([x, x_context], dim=1)
+        out = None if self.simple_ddt else self._context_output(initial_context, p)
         eng = self.engine
         dev = eng.dev
         x = x.to(device=dev, dtype=torch.float32).contiguous()
         t = to_device(timesteps, dev, torch.float32)
         y_eff = None
         if not self.simple_ddt:
-            assert self.context_embedder is not None, "for MMDiT context embedder must be provided"
-            out = self.context_embedder(initial_context, p)
-            keep = out.get("attn_mask", None)
-            eng.context = (out["embeddings"].to(device=dev), keep.to(device=dev) if keep is not None else None)
+            self._set_context(eng, out)
         elif self.label_embed is not None:
             assert y is not None, "class-conditional DDT needs labels `y`"
             y_eff = self._effective_labels(y.to(device=dev, dtype=torch.int64), p).contiguous()  # (drop_labels nn.py:149)

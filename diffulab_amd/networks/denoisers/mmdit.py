@@ -1,6 +1,7 @@
 """``MMDiT`` denoiser, MI355X build -- drop-in for ``diffulab.networks.denoisers.mmdit.MMDiT``: the class-conditional
-``simple_dit`` form and the joint text-image form (``simple_dit=False`` with a context embedder that returns one embedding and an
-attention mask, e.g. ``PrecomputedEmbedder``; ``MMDiTBlock`` layers, ``n_single_stream_blocks == 0``).
+``simple_dit`` form and the joint text-image form (``simple_dit=False`` with a parameter-free context embedder that returns token
+embeddings and an attention mask, e.g. ``PrecomputedEmbedder``, optionally with one pooled vector per sample (``n_output == 2``:
+``mlp_pooled_context``); ``MMDiTBlock`` layers followed by ``n_single_stream_blocks`` ``MMDiTSingleStreamBlock``s).
 
 Same constructor kwargs (mmdit.py:604-625 of the reference), same ``forward`` kwargs (mmdit.py:903-912), same
 ``state_dict`` key names / shapes and the same initialisation scheme (mmdit.py:735-745), so Hydra ``_target_``
@@ -199,19 +200,12 @@ class MMDiT(FlatArenaDenoiser):
 
     def _init_joint(self, inner_dim: int, embedding_dim: int, num_heads: int, mlp_ratio: int, depth: int,
                     rope_axes_dim: list[int] | None, partial_rotary_factor: float, heads_dim: int) -> None:
-        """mmdit.py:641-664,678-734 with MMDiTBlock layers"""
+        """mmdit.py:641-664,678-734"""
         ce = self.context_embedder
         assert ce is not None, "for MMDiT context embedder must be provided"
         assert isinstance(ce.output_size, tuple) and all(isinstance(i, int) for i in ce.output_size), (
             "context_embedder.output_size must be a tuple of integers")
-        if ce.n_output != 1:
-            raise NotImplementedError("diffulab_amd.MMDiT: context embedders with a pooled embedding (n_output == 2, "
-                                      "mmdit.py:646-654) are not built")
-        if any(True for _ in ce.parameters()):
-            raise NotImplementedError("diffulab_amd.MMDiT: the context embedder must be parameter-free (precomputed embeddings)")
-        self.pooled_embedding = False
-        self.mlp_pooled_context = None
-        self.context_embed = nn.Linear(ce.output_size[0], inner_dim, bias=False)
+        context_dim, pooled_dim = self._build_context_embed(inner_dim, embedding_dim)
         if rope_axes_dim is None:
             rope_axes_dim = [int((partial_rotary_factor * heads_dim) // 3)] * 3
         self.rope_axes_dim = list(rope_axes_dim)
@@ -219,7 +213,8 @@ class MMDiT(FlatArenaDenoiser):
         common = dict(input_channels=self.input_channels, output_channels=self.output_channels, inner_dim=inner_dim,
                       embedding_dim=embedding_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, patch_size=self.patch_size, depth=depth,
                       rope_base=float(self.rope_base), frequency_embedding=self.frequency_embedding, n_classes=None,
-                      classifier_free=self.classifier_free, rope_axes_dim=self.rope_axes_dim, context_dim=ce.output_size[0])
+                      classifier_free=self.classifier_free, rope_axes_dim=self.rope_axes_dim, context_dim=context_dim,
+                      pooled_dim=pooled_dim)
         self.dims = JointStackDims(n_single_stream_blocks=ns, **common) if ns else JointDims(**common)
         self.dims.validate()
         self.last_layer = _LastLayer(embedding_dim, inner_dim, self.patch_size, self.output_channels)
@@ -263,21 +258,18 @@ class MMDiT(FlatArenaDenoiser):
 
     # the context tensors are per-call inputs of the joint launch sequence: a captured graph reads static copies of them
     def _graph_inputs(self, eng) -> tuple:
-        return () if self.simple_dit else tuple(eng.context)
+        return () if self.simple_dit else self._joint_graph_inputs(eng)
 
     def _graph_set_inputs(self, eng, tensors: tuple) -> None:
         if not self.simple_dit:
-            eng.context = tuple(tensors)
+            self._joint_graph_set_inputs(eng, tensors)
 
     def _forward_joint(self, x: Tensor, timesteps: Tensor, initial_context: Any, p: float) -> ModelOutput:
         """mmdit.py:789-851: the embedder (context drop for classifier-free guidance) stays host-side torch"""
-        assert self.context_embedder is not None, "for MMDiT context embedder must be provided"
-        out = self.context_embedder(initial_context, p)
+        out = self._context_output(initial_context, p)
         eng = self.engine
         dev = eng.dev
-        emb = out["embeddings"].to(device=dev)
-        keep = out.get("attn_mask", None)
-        eng.context = (emb, keep.to(device=dev) if keep is not None else None)
+        self._set_context(eng, out)
         x = x.to(device=dev, dtype=torch.float32).contiguous()
         t = to_device(timesteps, dev, torch.float32)
         taps = tuple(i for i, layer in enumerate(self.layers) if layer._forward_hooks)

@@ -1,6 +1,6 @@
 """``SprintDiT`` denoiser, MI355X build -- drop-in for ``diffulab.networks.denoisers.sprint.SprintDiT``: the class-conditional
 ``simple_dit=True`` form (the shipped ``configs/model/sprint.yaml``) and the joint text-image form (``simple_dit=False`` behind a
-one-output context embedder such as ``PrecomputedEmbedder``: MMDiTBlock encoder / decoder, MMDiTBlock + MMDiTSingleStreamBlock deep
+parameter-free context embedder such as ``PrecomputedEmbedder``, with or without a pooled vector per sample: MMDiTBlock encoder / decoder, MMDiTBlock + MMDiTSingleStreamBlock deep
 stage, ``fuse_context``; ``configs/train_imagenet_repa_txt_to_img_sprint.yaml``).  Same constructor kwargs (sprint.py:68-91), ``forward`` kwargs (sprint.py:575-584),
 ``state_dict`` keys (``mask_token``, ``fuse``, ``layers`` / ``deep_layers`` / ``decoder_layers``) and initialisation.
 
@@ -103,18 +103,12 @@ class SprintDiT(FlatArenaDenoiser):
     def _init_joint(self, inner_dim: int, embedding_dim: int, num_heads: int, mlp_ratio: int, encoder_depth: int,
                     deep_layers_depth: int, n_single: int, decoder_depth: int, rope_axes_dim: list[int] | None,
                     partial_rotary_factor: float, heads_dim: int) -> None:
-        """sprint.py:109-131,160-262 with a one-output context embedder"""
+        """sprint.py:109-131,160-262"""
         ce = self.context_embedder
         assert ce is not None, "for dit with text context embedder must be provided"
         assert isinstance(ce.output_size, tuple) and all(isinstance(i, int) for i in ce.output_size), (
             "context_embedder.output_size must be a tuple of integers")
-        if ce.n_output != 1:
-            raise NotImplementedError("diffulab_amd.SprintDiT: context embedders with a pooled embedding are not built")
-        if any(True for _ in ce.parameters()):
-            raise NotImplementedError("diffulab_amd.SprintDiT: the context embedder must be parameter-free (precomputed embeddings)")
-        self.pooled_embedding = False
-        self.mlp_pooled_context = None
-        self.context_embed = nn.Linear(ce.output_size[0], inner_dim, bias=False)
+        context_dim, pooled_dim = self._build_context_embed(inner_dim, embedding_dim)
         if rope_axes_dim is None:
             rope_axes_dim = [int((partial_rotary_factor * heads_dim) // 3)] * 3
         self.rope_axes_dim = list(rope_axes_dim)
@@ -122,7 +116,7 @@ class SprintDiT(FlatArenaDenoiser):
                                     embedding_dim=embedding_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, patch_size=self.patch_size,
                                     rope_base=float(self.rope_base), frequency_embedding=self.frequency_embedding, n_classes=None,
                                     classifier_free=self.classifier_free, rope_axes_dim=self.rope_axes_dim,
-                                    context_dim=ce.output_size[0], encoder_depth=encoder_depth, deep_layers_depth=deep_layers_depth,
+                                    context_dim=context_dim, pooled_dim=pooled_dim, encoder_depth=encoder_depth, deep_layers_depth=deep_layers_depth,
                                     n_single_stream_blocks=n_single, decoder_depth=decoder_depth, drop_rate=self.drop_rate)
         self.dims.validate()
         self.mask_token = nn.Parameter(torch.zeros(1, 1, inner_dim))
@@ -200,11 +194,11 @@ class SprintDiT(FlatArenaDenoiser):
         return (id(r), r.skip_deep) if any(r is c for c in self._eval_routes.values()) else None
 
     def _graph_inputs(self, eng) -> tuple:
-        return () if self.simple_dit else tuple(eng.context)
+        return () if self.simple_dit else self._joint_graph_inputs(eng)
 
     def _graph_set_inputs(self, eng, tensors: tuple) -> None:
         if not self.simple_dit:
-            eng.context = tuple(tensors)
+            self._joint_graph_set_inputs(eng, tensors)
 
     # ------------------------------------------------------------------ forward (sprint.py:575-624)
     def forward(
@@ -230,16 +224,14 @@ class SprintDiT(FlatArenaDenoiser):
                     "probability of dropping for classifier free guidance is only available if a number of classes is set")
         if x_context is not None:
             x = torch.cat([x, x_context], dim=1)
-        eng = self.engine
+        out = None if self.simple_dit else self._context_output(initial_context, p)  # sprint.py:411-424: the embedder (context drop)
+        eng = self.engine                                                            # first, then the routing draws
         dev = eng.dev
         x = x.to(device=dev, dtype=torch.float32).contiguous()
         t = to_device(timesteps, dev, torch.float32)
         y_eff = None
-        if not self.simple_dit:  # sprint.py:411-424: the embedder (context drop) first, then the routing draws
-            assert self.context_embedder is not None, "for MMDiT context embedder must be provided"
-            out = self.context_embedder(initial_context, p)
-            keep = out.get("attn_mask", None)
-            eng.context = (out["embeddings"].to(device=dev), keep.to(device=dev) if keep is not None else None)
+        if not self.simple_dit:
+            self._set_context(eng, out)
             B, _, H, W = x.shape
             S = (H // self.patch_size) * (W // self.patch_size)
             eng.route = self._route(B, S, float(p), dev, n_ctx=out["embeddings"].shape[1])

@@ -689,6 +689,15 @@ def cond_combine_bwd(dact, emb, idx, demb, demb16, dtable):
           _s())
 
 
+def cond_combine_dense_fwd(e, pe, emb, act):
+    """emb = e + pe (f32 [B, E], contiguous), act = silu(emb) bf16"""
+    _call("dl_cond_combine_dense_fwd", _p(e), _p(pe), _p(emb), _p(act), e.shape[0], e.shape[1], _s())
+
+
+def cond_combine_dense_bwd(dact, emb, demb, demb16):
+    _call("dl_cond_combine_dense_bwd", _p(dact), _p(emb), _p(demb), _p(demb16), emb.shape[0], emb.shape[1], _s())
+
+
 def silu_bwd(dy, pre, dx):
     _call("dl_silu_bwd", _p(dy), _p(pre), _p(dx), dy.numel(), _s())
 

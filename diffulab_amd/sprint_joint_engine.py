@@ -55,35 +55,13 @@ class SprintJointLayout(ArenaLayout):
         kinds = d.kinds()
         self.prefixes = [pre for pre, _ in kinds]
 
-        def mods(suffix: str, width) -> list[str]:
-            names = []
-            for pre, kind in kinds:
-                if kind == "J":
-                    names += [(pre + f"modulation_{st}.lin.{suffix}", width(6)) for st in STREAMS]
-                else:
-                    names.append((pre + f"modulation.1.{suffix}", width(3)))
-            return names
-
         # stacked adaLN matrix: [input 6D | context 6D] per joint block, 3D per single-stream block, then the last layer's 2D
-        self.mod_off, off = [], 0
-        for _, kind in kinds:
-            self.mod_off.append(off)
-            off += (12 if kind == "J" else 3) * D
-        self.mod_rows = off + 2 * D
-        for i, (n, shp) in enumerate(mods("weight", lambda r: (r * D, E))):
-            add(n, shp, align=1 if i else 64)
-            if i == 0:
-                self.mod_w0 = n
-        add("last_layer.adaLN_modulation.1.weight", (2 * D, E), align=1)
-        for i, (n, shp) in enumerate(mods("bias", lambda r: (r * D,))):
-            add(n, shp, align=1 if i else 64)
-            if i == 0:
-                self.mod_b0 = n
-        add("last_layer.adaLN_modulation.1.bias", (2 * D,), align=1)
+        self.add_stacked_adaln(kinds, D, E, last_layer=True)
         add("time_embed.0.weight", (E, d.frequency_embedding))
         add("time_embed.0.bias", (E,))
         add("time_embed.2.weight", (E, E))
         add("time_embed.2.bias", (E,))
+        self.add_pooled_mlp(d.pooled_dim, E)
         add("conv_proj.weight", (D, d.input_channels, p, p))
         add("context_embed.weight", (D, d.context_dim))
         add("last_layer.linear.weight", (p * p * d.output_channels, D))
@@ -99,14 +77,7 @@ class SprintJointLayout(ArenaLayout):
                 self.add_joint_block(pre, D, F)
             else:
                 self.block_first.append(pre + "norm.weight")
-                add(pre + "norm.weight", (D,))
-                add(pre + "norm.bias", (D,), align=1)
-                add(pre + "attention.qk_norm.query_norm.scale", (D,))
-                add(pre + "attention.qk_norm.key_norm.scale", (D,), align=1)
-                add(pre + "attention.qkv.weight", (3 * D, D))
-                add(pre + "attention.proj_out.weight", (D, D))
-                add(pre + "mlp.0.weight", (2 * F, D))
-                add(pre + "mlp.2.weight", (D, F))
+                self.add_single_block(pre, D, F)
 
 
 class SprintJointEngine(DiTEngine):
@@ -235,7 +206,8 @@ class SprintJointEngine(DiTEngine):
             pend = (xcur, a["t"], mod[:, mo + 2 * D : mo + 3 * D])
         ops.gated_residual_fwd(pend[0], pend[1], pend[2], T, out)
 
-    def _sstage_bwd(self, blocks, dlat: Tensor, T: int, pos: Tensor, kb: Tensor, sw: SideWork) -> Tensor:
+    def _sstage_bwd(self, blocks, dlat: Tensor, T: int, pos: Tensor, kb: Tensor, sw: SideWork, attn: tuple | None = None) -> Tensor:
+        """backward of _sstage_fwd; attn: the attention scratch (dao, dq, dk, dv) over kb.shape[1] rows, default the deep stage's"""
         d, w, sh = self.d, self.ws, self.sh
         B = self.geo[0]
         D, Hh = d.inner_dim, d.num_heads
@@ -244,7 +216,7 @@ class SprintJointEngine(DiTEngine):
         mod, dmod = w["mod"], w["dmod32"]
         Tp = kb.shape[1]
         s = w["s_l"]
-        dao, dq, dk, dv = w["dao_d"], w["dq_d"], w["dk_d"], w["dv_d"]
+        dao, dq, dk, dv = attn if attn is not None else (w["dao_d"], w["dq_d"], w["dk_d"], w["dv_d"])
         blocks = list(blocks)
         last = blocks[-1]
         ml = self.layout.mod_off[last]

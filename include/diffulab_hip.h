@@ -382,6 +382,15 @@ DL_API int dl_cond_combine_fwd(const float* e, const float* table, const int64_t
 /* demb = dact * silu'(emb) (f32 + bf16 copies); dtable[idx[b],:] += demb[b,:] (atomic; dtable may be NULL) */
 DL_API int dl_cond_combine_bwd(const float* dact, const float* emb, const int64_t* idx, float* demb,
                                void* demb_bf16, float* dtable, int64_t B, int64_t E, dl_stream_t stream);
+/* the combine with a DENSE addend: emb = e + pe with pe = mlp_pooled_context(pooled) f32 [B, E] (SD3-style pooled context
+ * embedding; mmdit.py:800-806, sprint.py:412-418, ddt.py:296-302), act = silu(emb) as bf16, in one pass.  Contiguous [B, E]
+ * operands, E % 4 == 0, f32 operands 16-byte and act 8-byte aligned */
+DL_API int dl_cond_combine_dense_fwd(const float* e, const float* pe, float* emb, void* act, int64_t B, int64_t E,
+                                     dl_stream_t stream);
+/* its backward: demb = dact * silu'(emb), written once as f32 (bias gradients of the time MLP and of mlp_pooled_context) and as
+ * the bf16 operand of their weight- / data-gradient GEMMs; same layout rules */
+DL_API int dl_cond_combine_dense_bwd(const float* dact, const float* emb, float* demb, void* demb_bf16, int64_t B, int64_t E,
+                                     dl_stream_t stream);
 /* dx = dy * silu'(pre) ; pre bf16 (saved pre-activation), dy f32, dx bf16 */
 DL_API int dl_silu_bwd(const float* dy, const void* pre, void* dx, int64_t n, dl_stream_t stream);
 /* dx = dy * gelu'(pre)  (exact erf GELU; FeedForward of the Perceiver resampler, perceiver_resampler.py:77-80) */

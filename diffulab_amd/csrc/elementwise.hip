@@ -403,9 +403,13 @@ extern "C" int dl_ddim_step(const float* pred, const float* pred_uncond, float g
 }
 
 // ---------------------------------------------------------------- optimizer / casts
+// CLIP: the gradient scale is grad_scale * *coef, the clipping coefficient dl_clip_coef left in device memory (clip.hip); formed once
+// per thread, so with *coef == 1 the update is bit-identical to the plain one
+template <bool CLIP>
 __global__ void adamw_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                         float* __restrict__ v, int64_t n4, int64_t n, float lr, float b1, float b2, float eps,
-                        float wd, float inv_bc1_lr, float inv_sqrt_bc2, float gs) {
+                        float wd, float inv_bc1_lr, float inv_sqrt_bc2, float grad_scale, const float* __restrict__ coef) {
+  const float gs = CLIP ? grad_scale * *coef : grad_scale;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 pp = ((float4*)p)[i], gg = ((const float4*)g)[i], mm = ((float4*)m)[i], vv = ((float4*)v)[i];
@@ -451,8 +455,20 @@ extern "C" int dl_adamw_step(float* p, const float* g, float* m, float* v, int64
   DL_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "dl_adamw_step: 16B alignment");
   const float inv_bc1_lr = (float)((double)lr / (double)bias_corr1);
   const float inv_sqrt_bc2 = (float)(1.0 / sqrt((double)bias_corr2));
-  hipLaunchKernelGGL(adamw_k, ew_grid(n / 4 + 1), 256, 0, (hipStream_t)stream, p, g, m, v, n / 4, n, lr, beta1, beta2,
-                     eps, weight_decay, inv_bc1_lr, inv_sqrt_bc2, grad_scale);
+  hipLaunchKernelGGL(adamw_k<false>, ew_grid(n / 4 + 1), 256, 0, (hipStream_t)stream, p, g, m, v, n / 4, n, lr, beta1, beta2,
+                     eps, weight_decay, inv_bc1_lr, inv_sqrt_bc2, grad_scale, (const float*)nullptr);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
+                                  float grad_scale, const float* coef, dl_stream_t stream) {
+  DL_CHECK_ARG(p && g && m && v && coef && n > 0, "dl_adamw_step_clip: bad args");
+  DL_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "dl_adamw_step_clip: 16B alignment");
+  const float inv_bc1_lr = (float)((double)lr / (double)bias_corr1);
+  const float inv_sqrt_bc2 = (float)(1.0 / sqrt((double)bias_corr2));
+  hipLaunchKernelGGL(adamw_k<true>, ew_grid(n / 4 + 1), 256, 0, (hipStream_t)stream, p, g, m, v, n / 4, n, lr, beta1, beta2,
+                     eps, weight_decay, inv_bc1_lr, inv_sqrt_bc2, grad_scale, coef);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
@@ -460,25 +476,36 @@ extern "C" int dl_adamw_step(float* p, const float* g, float* m, float* v, int64
 // same update with the scalars read from device memory (hyper = {lr, beta1, beta2, eps, weight_decay, lr / bias_corr1,
 // 1 / sqrt(bias_corr2), grad_scale}): the launch carries no per-step value, so a captured hipGraph of the training step can be
 // replayed while the host refreshes the 32 bytes before each replay (training/graph_step.py)
+// The roundings are written out (contraction off, each fused multiply-add explicit) in the form the plain kernel has always compiled
+// to: left to the compiler, the CLIP instantiation fused v's update differently and came out an ulp apart at *coef == 1.
+template <bool CLIP>
 __global__ void adamw_dev_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            int64_t n, const float* __restrict__ hyper) {
+                            int64_t n, const float* __restrict__ hyper, const float* __restrict__ coef) {
+#pragma clang fp contract(off)
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], inv_bc1_lr = hyper[5],
-              inv_sqrt_bc2 = hyper[6], gs = hyper[7];
+              inv_sqrt_bc2 = hyper[6], gs = CLIP ? hyper[7] * *coef : hyper[7];
+  const float decay = __builtin_fmaf(-lr, wd, 1.0f), omb1 = 1.0f - b1, omb2 = 1.0f - b2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const float gr = g[i] * gs;
-    float pj = p[i] * (1.0f - lr * wd);
-    const float mj = b1 * m[i] + (1.0f - b1) * gr;
-    const float vj = b2 * v[i] + (1.0f - b2) * gr * gr;
-    pj -= inv_bc1_lr * (mj / (sqrtf(vj) * inv_sqrt_bc2 + eps));
-    p[i] = pj;
+    const float mj = __builtin_fmaf(b1, m[i], omb1 * gr);
+    const float vj = __builtin_fmaf(gr, omb2 * gr, b2 * v[i]);
+    const float denom = __builtin_fmaf(sqrtf(vj), inv_sqrt_bc2, eps);
+    p[i] = decay * p[i] - inv_bc1_lr * (mj / denom);
     m[i] = mj;
     v[i] = vj;
   }
 }
 extern "C" int dl_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, dl_stream_t stream) {
   DL_CHECK_ARG(p && g && m && v && hyper && n > 0, "dl_adamw_step_dev: bad args");
-  hipLaunchKernelGGL(adamw_dev_k, ew_grid(n), 256, 0, (hipStream_t)stream, p, g, m, v, n, hyper);
+  hipLaunchKernelGGL(adamw_dev_k<false>, ew_grid(n), 256, 0, (hipStream_t)stream, p, g, m, v, n, hyper, (const float*)nullptr);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_adamw_step_dev_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef,
+                                      dl_stream_t stream) {
+  DL_CHECK_ARG(p && g && m && v && hyper && coef && n > 0, "dl_adamw_step_dev_clip: bad args");
+  hipLaunchKernelGGL(adamw_dev_k<true>, ew_grid(n), 256, 0, (hipStream_t)stream, p, g, m, v, n, hyper, coef);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }

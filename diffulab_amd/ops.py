@@ -771,6 +771,65 @@ def adamw_step_dev(p, g, m, v, hyper):
     _call("dl_adamw_step_dev", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _s())
 
 
+def grad_sumsq_chain(n: int) -> int:
+    """terms on the longest serial f32 addition chain of `grad_sumsq` over n elements (host arithmetic): the sum's relative error is
+    at most (chain + 2) * 2**-24"""
+    return int(lib().call("dl_grad_sumsq_chain", int(n)))
+
+
+def grad_sumsq_slots(n: int) -> int:
+    """slots `grad_sumsq` writes for a buffer of n elements (host arithmetic: size the partials buffer from it)"""
+    return int(lib().call("dl_grad_sumsq_slots", int(n)))
+
+
+def grad_sumsq(x, partials, slot=0) -> int:
+    """fixed-order sum of squares of the f32 buffer `x` into partials[slot : slot + k]; returns k, the slots written"""
+    if x.dtype != torch.float32 or not x.is_contiguous() or partials.dtype != torch.float32 or not partials.is_contiguous():
+        raise RuntimeError("grad_sumsq needs contiguous f32 tensors")
+    global _LIB
+    if _LIB is None:
+        _LIB = lib()
+    args = (_p(x), x.numel(), _p(partials), int(slot), partials.numel(), _s())
+    k = _LIB.call("dl_grad_sumsq", *args)
+    if k <= 0:
+        raise RuntimeError(f"dl_grad_sumsq failed ({k}): {_LIB.cdll.dl_last_error().decode()}")
+    if _REC is not None:
+        _REC.calls.append((_negative_is_failure(_LIB._fns["dl_grad_sumsq"][0]), args))
+    return k
+
+
+def _negative_is_failure(fn):
+    """a value-returning entry point as a launch-plan call (LaunchPlan.replay treats a non-zero return as a failure)"""
+    return lambda *a: fn(*a) < 0
+
+
+def clip_coef(partials, n_slots, max_norm, out, grad_scale=1.0, hyper=None):
+    """out f32[2] = {grad_scale * sqrt(sum of partials[:n_slots]), min(1, max_norm / (norm + 1e-6))}; with `hyper` (the device
+    scalars of `adamw_step_dev`) grad_scale is read from hyper[7]"""
+    if n_slots > partials.numel() or out.numel() < 2 or out.dtype != torch.float32 or partials.dtype != torch.float32:
+        raise RuntimeError("clip_coef: n_slots exceeds the partials buffer, or out is not f32[2]")
+    _call("dl_clip_coef", _p(partials), int(n_slots), float(grad_scale), _p(hyper), float(max_norm), _p(out), _s())
+    return out
+
+
+def adamw_step_clip(p, g, m, v, lr, beta1, beta2, eps, wd, step, coef, grad_scale=1.0):
+    """`adamw_step` with the gradient scaled by grad_scale * coef[0], `coef` a device f32 scalar (`clip_coef`'s out[1:2])"""
+    _call("dl_adamw_step_clip", _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
+          float(wd), float(1.0 - beta1**step), float(1.0 - beta2**step), float(grad_scale), _p(coef), _s())
+
+
+def adamw_step_dev_clip(p, g, m, v, hyper, coef):
+    _call("dl_adamw_step_dev_clip", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(coef), _s())
+
+
+def scale_inplace(g, coef):
+    """g *= coef[0] in place (f32, contiguous), `coef` a device f32 scalar"""
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        raise RuntimeError("scale_inplace needs a contiguous f32 tensor")
+    _call("dl_scale_inplace", _p(g), g.numel(), _p(coef), _s())
+    return g
+
+
 def cast_weight(src, dst, dst_t):
     R, C = src.shape
     _call("dl_cast_weight", _p(src), R, C, _p(dst), dst.stride(0) if dst is not None else 0, _p(dst_t),

@@ -1,4 +1,5 @@
-"""Fused AdamW over the flat parameter arena: ONE `dl_adamw_step` launch per optimizer step.
+"""Fused AdamW over the flat parameter arena: ONE `dl_adamw_step` launch per optimizer step (with ``max_grad_norm``: one sum of
+squares over the gradient arena and a one-workgroup fold in front of it, then `dl_adamw_step_clip`).
 
 Drop-in `torch.optim.Optimizer` (same hyper-parameters / update rule as `torch.optim.AdamW`, which
 `configs/optimizer/adamw.yaml` of the reference instantiates).  When the parameters are views of one flat f32
@@ -35,10 +36,23 @@ def _arena_of(params: list[Tensor], use_grad: bool) -> Tensor | None:
 
 
 class FusedAdamW(torch.optim.Optimizer):
+    """``max_grad_norm``: clip by the global 2-norm of all gradients of all parameter groups (``torch.nn.utils.clip_grad_norm_``'s
+    rule: every gradient times ``min(1, max_grad_norm / (norm + 1e-6))``, the norm being that of ``grad_scale * grad``) INSIDE the
+    update: ``step()`` reads the gradients once more for the sum of squares, leaves ``{norm, coef}`` in device memory and hands the
+    update kernels the coefficient's address.  ``p.grad`` is left UNSCALED -- the fused path never rewrites the gradient arena --
+    and nothing synchronises with the host; ``last_grad_norm`` is the norm of the latest step as a 0-d device tensor (a view of the
+    optimizer's own scalar: clone it to keep a value across steps).  ``None`` (the default): exactly the launches of the plain
+    update."""
+
     def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2) -> None:
+                 weight_decay: float = 1e-2, max_grad_norm: float | None = None) -> None:
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = 1.0  # data parallel: 1/world (gradients are SUM-reduced), folded into the update kernel
+        self.max_grad_norm = max_grad_norm
+        self.last_grad_norm: Tensor | None = None
+        # sum-of-squares slots and the {norm, coef} pair: allocated ONCE (captured graphs hold their addresses, like _graph_buffers)
+        self._clip_partials: Tensor | None = None
+        self._clip_out: Tensor | None = None
         self._legacy_arena_states: list[dict] = []
         self._graph_hyper: list[tuple[Tensor, Tensor]] | None = None  # per group: (device f32[8], pinned host mirror)
         self._graph_buffers: list[tuple[Tensor, Tensor]] | None = None
@@ -190,11 +204,55 @@ class FusedAdamW(torch.optim.Optimizer):
                     else:
                         p.grad.zero_()
 
+    def _clip_pass(self) -> Tensor:
+        """sum of squares over every group's gradient arena and loose gradients (ONE global norm, as torch's function takes it over a
+        parameter list), then the fold: -> the device coefficient the update launches of this step take"""
+        bufs: list[Tensor] = []
+        for group in self.param_groups:
+            flat = self._flat(group)
+            rest = group["params"]
+            if flat is not None:
+                bufs.append(flat[1])
+                rest = flat[2]
+            bufs.extend(p.grad for p in rest if p.grad is not None)
+        if not bufs:
+            raise RuntimeError("max_grad_norm is set but no parameter has a gradient")
+        need = sum(ops.grad_sumsq_slots(b.numel()) for b in bufs)
+        if self._clip_partials is None or need > self._clip_partials.numel():
+            if self._clip_partials is not None and self._graph_buffers is not None:
+                raise RuntimeError("the gradient buffers grew after a graph was captured: captured graphs hold the partials' address")
+            self._clip_partials = torch.zeros(max(need, 1024), device=bufs[0].device)
+        if self._clip_out is None:
+            self._clip_out = torch.zeros(2, device=bufs[0].device)
+            self.last_grad_norm = self._clip_out[0]
+        slot = 0
+        for b in bufs:
+            slot += ops.grad_sumsq(b, self._clip_partials, slot)
+        hyper = self._graph_hyper[0][0] if self._graph_hyper is not None else None  # (grad_scale is one value for every group)
+        ops.clip_coef(self._clip_partials, slot, self.max_grad_norm, self._clip_out, self.grad_scale, hyper)
+        return self._clip_out[1:2]
+
+    def _update(self, p: Tensor, g: Tensor, st: dict, group: dict, coef: Tensor | None) -> None:
+        b1, b2 = group["betas"]
+        if coef is None:
+            ops.adamw_step(p, g, st["m"], st["v"], group["lr"], b1, b2, group["eps"], group["weight_decay"], st["step"],
+                           self.grad_scale)
+        else:
+            ops.adamw_step_clip(p, g, st["m"], st["v"], group["lr"], b1, b2, group["eps"], group["weight_decay"], st["step"],
+                                coef, self.grad_scale)
+
+    @staticmethod
+    def _update_dev(p: Tensor, g: Tensor, st: dict, hyper: Tensor, coef: Tensor | None) -> None:
+        if coef is None:
+            ops.adamw_step_dev(p, g, st["m"], st["v"], hyper)
+        else:
+            ops.adamw_step_dev_clip(p, g, st["m"], st["v"], hyper, coef)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        coef = self._clip_pass() if self.max_grad_norm is not None else None
         for gi, group in enumerate(self.param_groups):
-            b1, b2 = group["betas"]
             if self._graph_hyper is not None:  # captured step: scalars come from the device buffer, state must already exist
                 hyper = self._graph_hyper[gi][0]
                 flat = self._flat(group)
@@ -204,12 +262,12 @@ class FusedAdamW(torch.optim.Optimizer):
                     st = self.state[self._arena_key(group, rest)]
                     if "m" not in st:
                         raise RuntimeError("graph mode needs the arena moments: run one eager step() after loading a checkpoint")
-                    ops.adamw_step_dev(pb, gb, st["m"], st["v"], hyper)
+                    self._update_dev(pb, gb, st, hyper, coef)
                 for p in rest:
                     if p.grad is not None:
                         st = self.state[p]
                         self._adopt_reference_param_state(st, p)
-                        ops.adamw_step_dev(p.data, p.grad, st["m"], st["v"], hyper)
+                        self._update_dev(p.data, p.grad, st, hyper, coef)
                 continue
             flat = self._flat(group)
             rest = group["params"]
@@ -233,8 +291,7 @@ class FusedAdamW(torch.optim.Optimizer):
                     assert st["m"].numel() == pb.numel(), "optimizer state does not match the parameter arena"
                     st["m"], st["v"] = st["m"].to(pb.device), st["v"].to(pb.device)
                 st["step"] = int(st["step"]) + 1
-                ops.adamw_step(pb, gb, st["m"], st["v"], group["lr"], b1, b2, group["eps"], group["weight_decay"], st["step"],
-                               self.grad_scale)
+                self._update(pb, gb, st, group, coef)
                 bump_param_epoch()  # raw-pointer writes bump no torch version counter: tell the engines
             if rest:
                 for p in rest:
@@ -247,7 +304,6 @@ class FusedAdamW(torch.optim.Optimizer):
                     if st["m"].device != p.device:
                         st["m"], st["v"] = st["m"].to(p.device), st["v"].to(p.device)
                     st["step"] = int(st["step"]) + 1
-                    ops.adamw_step(p.data, p.grad, st["m"], st["v"], group["lr"], b1, b2, group["eps"],
-                                   group["weight_decay"], st["step"], self.grad_scale)
+                    self._update(p.data, p.grad, st, group, coef)
             bump_param_epoch()
         return loss

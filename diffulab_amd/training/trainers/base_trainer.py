@@ -1,7 +1,8 @@
 """``BaseTrainer``: the training loop of the reference (training/trainers/base_trainer.py:104-399) on the MI355X runtime.
 
 ``training_step`` keeps the reference's order of operations (base_trainer.py:138-153): zero_grad -> draw timesteps (CPU generator)
--> compute_loss -> every loss into the tracker (the reference's ``.item()``; here a device scalar the meter reads back lazily) -> backward -> optimizer.step -> scheduler -> EMA update.
+-> compute_loss -> every loss into the tracker (the reference's ``.item()``; here a device scalar the meter reads back lazily) -> backward -> [clip by
+global gradient norm when ``max_grad_norm`` is set: fused into the AdamW update, ``train/grad_norm`` into the tracker] -> optimizer.step -> scheduler -> EMA update.
 What Accelerate did implicitly is spelled out (see trainers/common.py): loss / gradient_accumulation_step before backward,
 ``zero_grad`` / ``step`` / scheduler gated on the synchronising micro-step (so with k > 1 the default reproduces the reference's
 "(1/k) * gradient of the last micro-batch" update), EMA on every micro-step, gradient all-reduce overlapped
@@ -60,7 +61,10 @@ class BaseTrainer(Trainer):
         (loss / self.gradient_accumulation_step).backward()
         if self.sync_gradients:
             self.reduce_extra_grads(diffuser)
+            norm = self.clip_gradients(optimizer) if self.max_grad_norm is not None else None
             optimizer.step()
+            if self.max_grad_norm is not None:  # once per accumulation window, on the accumulated gradient; read back with the losses
+                tracker.update((optimizer.last_grad_norm if norm is None else norm).clone(), key="train/grad_norm")
             if scheduler is not None and per_batch_scheduler:
                 scheduler.step()
         if ema_denoiser is not None:

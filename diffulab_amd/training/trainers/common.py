@@ -66,6 +66,7 @@ class Trainer(ABC):
         ema_update_every: int = 10,
         compile: bool = False,
         dynamo_plugin_kwargs: dict[str, Any] = {},
+        max_grad_norm: float | None = None,
     ) -> None:
         if precision_type not in ("no", "bf16"):
             raise NotImplementedError(
@@ -80,6 +81,8 @@ class Trainer(ABC):
         self.ema_update_after_step = ema_update_after_step * self.gradient_accumulation_step
         self.ema_update_every = ema_update_every * self.gradient_accumulation_step
         self.compile = compile
+        # clip by global gradient norm on the synchronising micro-step (where accelerator.clip_grad_norm_ acts); None = no clipping
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
 
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
         self.rank = int(os.environ.get("RANK", "0"))
@@ -260,6 +263,19 @@ class Trainer(ABC):
                 for g in grads:
                     g.copy_(flat[off : off + g.numel()].view_as(g))
                     off += g.numel()
+
+    def clip_gradients(self, optimizer: Optimizer):
+        """before ``optimizer.step()`` of the synchronising micro-step, the reducer done: ``FusedAdamW`` takes the bound and clips
+        inside its update (None is returned: the norm exists after the step, ``optimizer.last_grad_norm``); any other optimizer has
+        its gradients scaled in place here, and the total-norm device scalar is returned"""
+        from ..optim import FusedAdamW
+        from ..utils import clip_grad_norm_
+
+        if isinstance(optimizer, FusedAdamW):
+            optimizer.max_grad_norm = self.max_grad_norm
+            return None
+        params = [p for group in optimizer.param_groups for p in group["params"]]
+        return clip_grad_norm_(params, self.max_grad_norm, self._reducer.grad_scale if self._reducer is not None else 1.0)
 
     def gather_mean(self, value: float) -> float:
         if self.world == 1:

@@ -469,6 +469,35 @@ DL_API int dl_adamw_step(float* p, const float* g, float* m, float* v, int64_t n
  * 1 / sqrt(bias_corr2), grad_scale}.  No per-step value travels in the launch, so a captured hipGraph of the whole training step
  * (base_trainer.py:138-151: zero_grad -> loss -> backward -> optimizer.step) replays with the host refreshing 32 bytes */
 DL_API int dl_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, dl_stream_t stream);
+/* Gradient clipping by global 2-norm (torch.nn.utils.clip_grad_norm_ with norm_type=2, error_if_nonfinite=False; accelerate's
+ * Accelerator.clip_grad_norm_ is the site it stands in for), without a host synchronisation and without rewriting the gradients.
+ *
+ * dl_grad_sumsq: fixed-order sum of squares of an f32 buffer (4-byte aligned, any n; no atomics, bit-reproducible).  Writes
+ * dl_grad_sumsq_slots(n) workgroup sums to partials[slot ...] (`capacity` = floats in `partials`; a range that does not fit is refused)
+ * and RETURNS the number of slots written (> 0), or a negative status.  Several buffers -- the arena and every loose tensor outside
+ * it -- write disjoint slot ranges of one partials buffer.  dl_grad_sumsq_chain(n): terms on the longest serial f32 addition chain
+ * (per-thread accumulator plus the in-workgroup tree), <= 4096 for n <= 2^31: the relative error of the sum is bounded by
+ * (chain + 2) * 2^-24.  Both are host arithmetic. */
+DL_API int64_t dl_grad_sumsq_slots(int64_t n);
+DL_API int64_t dl_grad_sumsq_chain(int64_t n);
+DL_API int dl_grad_sumsq(const float* x, int64_t n, float* partials, int64_t slot, int64_t capacity, dl_stream_t stream);
+/* one workgroup folds partials[0 .. n_slots) in f64, in slot order, and writes out = {total_norm, coef} (device f32[2]):
+ *   total_norm = grad_scale * sqrt(sum) ; coef = min(1, max_norm / (total_norm + 1e-6))
+ * which is clip_grad_norm_'s rule: an infinite norm gives coef = 0, a NaN norm coef = NaN.  With `hyper` non-NULL grad_scale is
+ * read from hyper[7] (the device scalars of dl_adamw_step_dev) and the by-value one is ignored. */
+DL_API int dl_clip_coef(const float* partials, int64_t n_slots, float grad_scale, const float* hyper, float max_norm, float* out,
+                        dl_stream_t stream);
+/* dl_adamw_step / dl_adamw_step_dev with the gradient scaled by grad_scale * *coef (`coef` = &out[1] of dl_clip_coef, a DEVICE
+ * pointer): the clipped update of clip_grad_norm_ followed by optimizer.step(), the gradient buffer left as it is.  *coef == 1
+ * gives bit for bit the plain update. */
+DL_API int dl_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                              float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
+                              const float* coef, dl_stream_t stream);
+DL_API int dl_adamw_step_dev_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef,
+                                  dl_stream_t stream);
+/* g *= *coef in place (4-byte aligned, any n): clip_grad_norm_'s own write-back, for optimizers other than the fused AdamW
+ * (configs/optimizer/sgd.yaml).  *coef == 1 leaves the buffer untouched. */
+DL_API int dl_scale_inplace(float* g, int64_t n, const float* coef, dl_stream_t stream);
 /* bf16 shadow of an f32 [R,C] weight: dst [R, ld_dst] (cols >= C zeroed up to ld_dst) and/or the transpose
  * dstT [C, ld_t] (cols >= R zeroed up to ld_t).  Either destination may be NULL. */
 DL_API int dl_cast_weight(const float* src, int64_t R, int64_t C, void* dst, int64_t ld_dst, void* dstT,

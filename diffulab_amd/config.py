@@ -19,6 +19,7 @@ _ALIASES = {
     "diffulab.networks.denoisers.UNetModel": "diffulab_amd.networks.denoisers.UNetModel",
     "diffulab.networks.UNetModel": "diffulab_amd.networks.denoisers.UNetModel",
     "torch.optim.AdamW": "diffulab_amd.training.FusedAdamW",  # same update rule, one launch over the flat arena
+    "torch.optim.SGD": "diffulab_amd.training.FusedSGD",  # likewise
 }
 
 

@@ -510,6 +510,96 @@ extern "C" int dl_adamw_step_dev_clip(float* p, const float* g, float* m, float*
   return DL_OK;
 }
 
+// torch.optim.SGD's single-tensor rule for one element.  ONE body for every caller (vector lanes, scalar head / tail, the odd-phase
+// loop; scalars from the launch or from device memory; with or without the clipping coefficient), with contraction off and each
+// fused multiply-add explicit, as in adamw_dev_k and for its reason: all of them round identically, which the tests hold bit for bit.
+struct SgdScalars {
+  float neg_lr, mom, omd, wd, gs;  // -lr, momentum, 1 - dampening, weight_decay, grad_scale [* *coef]
+  int flags;
+  bool has_buf;
+};
+__device__ __forceinline__ void sgd_elem(float& p, const float g, float& b, const SgdScalars& s) {
+#pragma clang fp contract(off)
+  float gr = g * s.gs;
+  if (s.flags & DL_SGD_MAXIMIZE) gr = -gr;
+  if (s.wd != 0.0f) gr = __builtin_fmaf(s.wd, p, gr);
+  if (s.has_buf) {
+    b = (s.flags & DL_SGD_FIRST) ? gr : __builtin_fmaf(s.mom, b, s.omd * gr);
+    gr = (s.flags & DL_SGD_NESTEROV) ? __builtin_fmaf(s.mom, b, gr) : b;
+  }
+  p = __builtin_fmaf(s.neg_lr, gr, p);
+}
+// Elements [head, head + 4 * n4) go as float4 (the host picks `head` so that p + head, g + head and buf + head are 16-byte aligned);
+// [0, head) and [head + 4 * n4, n) go one by one.  Buffers whose 16-byte phases differ: head = n, n4 = 0, a scalar grid-stride loop.
+// buf == NULL: no momentum, the buffer is neither read nor written.  DL_SGD_FIRST writes buf without reading it.
+__global__ void sgd_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n, int64_t head,
+                      int64_t n4, float lr, float mom, float damp, float wd, float grad_scale, const float* __restrict__ hyper,
+                      const float* __restrict__ coef, int flags) {
+#pragma clang fp contract(off)
+  if (hyper) lr = hyper[0], mom = hyper[1], damp = hyper[2], wd = hyper[3], grad_scale = hyper[4];
+  SgdScalars s;
+  s.neg_lr = -lr, s.mom = mom, s.omd = 1.0f - damp, s.wd = wd, s.gs = coef ? grad_scale * *coef : grad_scale;
+  s.flags = flags, s.has_buf = buf != nullptr;
+  const bool read_buf = s.has_buf && !(flags & DL_SGD_FIRST);
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  float4* p4 = (float4*)(p + head);
+  const float4* g4 = (const float4*)(g + head);
+  float4* b4 = s.has_buf ? (float4*)(buf + head) : nullptr;
+  for (int64_t i = tid; i < n4; i += stride) {
+    float4 pp = p4[i], bb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 gg = g4[i];
+    if (read_buf) bb = b4[i];
+    sgd_elem(pp.x, gg.x, bb.x, s);
+    sgd_elem(pp.y, gg.y, bb.y, s);
+    sgd_elem(pp.z, gg.z, bb.z, s);
+    sgd_elem(pp.w, gg.w, bb.w, s);
+    p4[i] = pp;
+    if (s.has_buf) b4[i] = bb;
+  }
+  const int64_t tail0 = head + 4 * n4, n_scalar = head + (n - tail0);
+  for (int64_t j = tid; j < n_scalar; j += stride) {
+    const int64_t i = j < head ? j : tail0 + (j - head);
+    float pj = p[i], bj = read_buf ? buf[i] : 0.0f;
+    sgd_elem(pj, g[i], bj, s);
+    p[i] = pj;
+    if (s.has_buf) buf[i] = bj;
+  }
+}
+static int sgd_launch(const char* who, float* p, const float* g, float* buf, int64_t n, float lr, float mom, float damp, float wd,
+                      float grad_scale, const float* hyper, const float* coef, int flags, dl_stream_t stream) {
+  DL_CHECK_ARG(p && g && n > 0, "%s: bad args (p, g non-null, n > 0)", who);
+  DL_CHECK_ARG(((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf | (uintptr_t)coef | (uintptr_t)hyper)) & 3) == 0, "%s: 4B alignment", who);
+  DL_CHECK_ARG((flags & ~(DL_SGD_NESTEROV | DL_SGD_FIRST | DL_SGD_MAXIMIZE)) == 0, "%s: unknown flag bits 0x%x", who, flags);
+  const int ph = (int)(((uintptr_t)p >> 2) & 3);
+  const bool same = ph == (int)(((uintptr_t)g >> 2) & 3) && (!buf || ph == (int)(((uintptr_t)buf >> 2) & 3));
+  int64_t head = n, n4 = 0;
+  if (same) {
+    head = (4 - ph) & 3;
+    if (head > n) head = n;
+    n4 = (n - head) / 4;
+  }
+  const int64_t n_scalar = n - 4 * n4;
+  hipLaunchKernelGGL(sgd_k, ew_grid(n4 > n_scalar ? n4 : n_scalar), 256, 0, (hipStream_t)stream, p, g, buf, n, head, n4, lr, mom,
+                     damp, wd, grad_scale, hyper, coef, flags);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float dampening,
+                           float weight_decay, float grad_scale, const float* coef, int flags, dl_stream_t stream) {
+  DL_CHECK_ARG(momentum == 0.0f || buf, "dl_sgd_step: momentum != 0 needs a momentum buffer");
+  DL_CHECK_ARG(!(flags & DL_SGD_NESTEROV) || (momentum != 0.0f && dampening == 0.0f),
+               "dl_sgd_step: Nesterov momentum needs momentum != 0 and dampening == 0");
+  return sgd_launch("dl_sgd_step", p, g, momentum != 0.0f ? buf : nullptr, n, lr, momentum, dampening, weight_decay, grad_scale,
+                    nullptr, coef, flags, stream);
+}
+extern "C" int dl_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const float* hyper, const float* coef, int flags,
+                               dl_stream_t stream) {
+  DL_CHECK_ARG(hyper, "dl_sgd_step_dev: bad args (hyper is null)");
+  DL_CHECK_ARG(!(flags & DL_SGD_FIRST), "dl_sgd_step_dev: DL_SGD_FIRST is refused, the momentum buffer must already exist");
+  DL_CHECK_ARG(!(flags & DL_SGD_NESTEROV) || buf, "dl_sgd_step_dev: Nesterov momentum needs a momentum buffer");
+  return sgd_launch("dl_sgd_step_dev", p, g, buf, n, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, hyper, coef, flags, stream);
+}
+
 __global__ void ema_k(float* __restrict__ ema, const float* __restrict__ p, float w, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {

@@ -822,6 +822,34 @@ def adamw_step_dev_clip(p, g, m, v, hyper, coef):
     _call("dl_adamw_step_dev_clip", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(coef), _s())
 
 
+SGD_NESTEROV, SGD_FIRST, SGD_MAXIMIZE = 1, 2, 4  # DL_SGD_* of include/diffulab_hip.h
+
+
+def _sgd_check(p, g, buf):
+    for t in (p, g, buf):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel()):
+            raise RuntimeError("sgd_step needs contiguous f32 tensors of one size")
+
+
+def sgd_step(p, g, buf, lr, momentum=0.0, dampening=0.0, wd=0.0, grad_scale=1.0, coef=None, nesterov=False, first=False,
+             maximize=False):
+    """torch.optim.SGD's update of the f32 buffer `p` in one launch; `buf` the momentum buffer (None with momentum == 0; `first`:
+    it is written with the gradient, not read), `coef` an optional device f32 scalar the gradient scale is multiplied by
+    (`clip_coef`'s out[1:2])"""
+    _sgd_check(p, g, buf)
+    flags = (SGD_NESTEROV if nesterov else 0) | (SGD_FIRST if first else 0) | (SGD_MAXIMIZE if maximize else 0)
+    _call("dl_sgd_step", _p(p), _p(g), _p(buf), p.numel(), float(lr), float(momentum), float(dampening), float(wd),
+          float(grad_scale), _p(coef), flags, _s())
+
+
+def sgd_step_dev(p, g, buf, hyper, coef=None, nesterov=False, maximize=False):
+    """SGD with the scalars read from the device buffer `hyper` f32 [8] = {lr, momentum, dampening, weight_decay, grad_scale, 0, 0,
+    0} (graph-replayable launch); `buf` None = no momentum"""
+    _sgd_check(p, g, buf)
+    _call("dl_sgd_step_dev", _p(p), _p(g), _p(buf), p.numel(), _p(hyper), _p(coef),
+          (SGD_NESTEROV if nesterov else 0) | (SGD_MAXIMIZE if maximize else 0), _s())
+
+
 def scale_inplace(g, coef):
     """g *= coef[0] in place (f32, contiguous), `coef` a device f32 scalar"""
     if g.dtype != torch.float32 or not g.is_contiguous():

@@ -5,6 +5,10 @@ Drop-in `torch.optim.Optimizer` (same hyper-parameters / update rule as `torch.o
 `configs/optimizer/adamw.yaml` of the reference instantiates).  When the parameters are views of one flat f32
 arena (what `MMDiT.flatten_parameters` sets up) the whole model is updated by a single kernel; otherwise it
 launches the same HIP kernel once per tensor.
+
+`FusedSGD` is the same for `torch.optim.SGD` (`configs/optimizer/sgd.yaml`): ONE `dl_sgd_step` launch.  Both derive from
+`FusedArenaOptimizer`, which owns what is not the update rule: finding the arena, `zero_grad` as one memset, the clipping pass,
+`grad_scale` and the device scalars of a captured step.
 """
 
 from __future__ import annotations
@@ -35,8 +39,10 @@ def _arena_of(params: list[Tensor], use_grad: bool) -> Tensor | None:
     return torch.empty(0, dtype=torch.float32, device=t0.device).set_(store, 0, (store.nbytes() // 4,))
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    """``max_grad_norm``: clip by the global 2-norm of all gradients of all parameter groups (``torch.nn.utils.clip_grad_norm_``'s
+class FusedArenaOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers share; a subclass adds the update rule (``step``), its state and ``_graph_scalars``.
+
+    ``max_grad_norm``: clip by the global 2-norm of all gradients of all parameter groups (``torch.nn.utils.clip_grad_norm_``'s
     rule: every gradient times ``min(1, max_grad_norm / (norm + 1e-6))``, the norm being that of ``grad_scale * grad``) INSIDE the
     update: ``step()`` reads the gradients once more for the sum of squares, leaves ``{norm, coef}`` in device memory and hands the
     update kernels the coefficient's address.  ``p.grad`` is left UNSCALED -- the fused path never rewrites the gradient arena --
@@ -44,23 +50,21 @@ class FusedAdamW(torch.optim.Optimizer):
     optimizer's own scalar: clone it to keep a value across steps).  ``None`` (the default): exactly the launches of the plain
     update."""
 
-    def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, max_grad_norm: float | None = None) -> None:
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, params, defaults: dict, max_grad_norm: float | None = None) -> None:
+        super().__init__(params, defaults)
         self.grad_scale = 1.0  # data parallel: 1/world (gradients are SUM-reduced), folded into the update kernel
         self.max_grad_norm = max_grad_norm
         self.last_grad_norm: Tensor | None = None
         # sum-of-squares slots and the {norm, coef} pair: allocated ONCE (captured graphs hold their addresses, like _graph_buffers)
         self._clip_partials: Tensor | None = None
         self._clip_out: Tensor | None = None
-        self._legacy_arena_states: list[dict] = []
         self._graph_hyper: list[tuple[Tensor, Tensor]] | None = None  # per group: (device f32[8], pinned host mirror)
         self._graph_buffers: list[tuple[Tensor, Tensor]] | None = None
 
-    # ---- hipGraph support (dl_adamw_step_dev; the captured-step experiment lives in scripts/lab/graph_step.py): inside a captured
-    #      step the update kernels read their scalars from a device buffer; the host advances the step count and refreshes that
-    #      buffer BEFORE each replay.  The buffers are allocated ONCE: graphs captured earlier hold their addresses, so a second
-    #      begin_graph_mode (another input shape being captured) must not replace them.
+    # ---- hipGraph support (dl_adamw_step_dev / dl_sgd_step_dev; the captured-step experiment lives in scripts/lab/graph_step.py):
+    #      inside a captured step the update kernels read their scalars from a device buffer; the host advances the step count and
+    #      refreshes that buffer BEFORE each replay.  The buffers are allocated ONCE: graphs captured earlier hold their addresses,
+    #      so a second begin_graph_mode (another input shape being captured) must not replace them.
     def begin_graph_mode(self) -> None:
         if self._graph_hyper is None:
             if self._graph_buffers is None:
@@ -83,62 +87,18 @@ class FusedAdamW(torch.optim.Optimizer):
             if "step" in st:
                 st["step"] = self._graph_step
         for group, (dev, host) in zip(self.param_groups, self._graph_hyper):
-            b1, b2 = group["betas"]
-            bc1, bc2 = 1.0 - b1**self._graph_step, 1.0 - b2**self._graph_step
-            host.copy_(torch.tensor([group["lr"], b1, b2, group["eps"], group["weight_decay"], group["lr"] / bc1, bc2**-0.5,
-                                     self.grad_scale], dtype=torch.float32))
+            host.copy_(torch.tensor(self._graph_scalars(group, self._graph_step), dtype=torch.float32))
             dev.copy_(host, non_blocking=True)
         bump_param_epoch()
+
+    def _graph_scalars(self, group: dict, step: int) -> list[float]:
+        """the eight f32 the update kernel of a captured step reads from device memory; [7] is grad_scale (dl_clip_coef reads it)"""
+        raise NotImplementedError
 
     @staticmethod
     def _arena_key(group, rest: list) -> Tensor:
         skip = {id(p) for p in rest}
         return next(p for p in group["params"] if id(p) not in skip and p.requires_grad)
-
-    def load_state_dict(self, state_dict) -> None:
-        """accepts three optimizer.pt layouts: this class's own (arena-sized ``m`` / ``v`` / ``step`` under the first arena
-        parameter of a group, per-parameter ``m`` / ``v`` / ``step`` for tensors outside the arena), the reference's
-        ``torch.optim.AdamW`` checkpoint (per-parameter ``exp_avg`` / ``exp_avg_sq`` / ``step``: packed into the arena moments at
-        the first step, see _adopt_reference_state) and the address-keyed ``arena*`` entries round 1 wrote (matched by size)"""
-        super().load_state_dict(state_dict)
-        for k in [k for k in self.state if isinstance(k, str) and k.startswith("arena")]:
-            self._legacy_arena_states.append(self.state.pop(k))
-
-    def _adopt_reference_state(self, pb: Tensor, inside: list, key: Tensor) -> None:
-        """torch.optim.AdamW state (the reference's optimizer.pt, base_trainer.py:246-251) -> arena moments: every arena
-        parameter's exp_avg / exp_avg_sq is copied to its offset, the step count is the parameters' common one"""
-        m, v = torch.zeros_like(pb), torch.zeros_like(pb)
-        steps = set()
-        base = pb.storage_offset()
-        for p in inside:
-            st = self.state.get(p)
-            if not st:
-                continue
-            if "exp_avg" not in st or "exp_avg_sq" not in st:
-                raise RuntimeError(f"optimizer state of an arena parameter has keys {sorted(st)}: expected FusedAdamW's "
-                                   "('m', 'v', 'step') or torch.optim.AdamW's ('exp_avg', 'exp_avg_sq', 'step')")
-            o = p.data.storage_offset() - base
-            m[o : o + p.numel()].copy_(st["exp_avg"].reshape(-1).to(pb.device, torch.float32))
-            v[o : o + p.numel()].copy_(st["exp_avg_sq"].reshape(-1).to(pb.device, torch.float32))
-            steps.add(int(st["step"]))
-            if p is not key:
-                del self.state[p]
-        if len(steps) > 1:
-            raise RuntimeError(f"torch.optim.AdamW checkpoint with different step counts per parameter ({sorted(steps)}): the arena "
-                               "update has one")
-        st = self.state[key]
-        st.clear()
-        st["step"], st["m"], st["v"] = (steps.pop() if steps else 0), m, v
-
-    @staticmethod
-    def _adopt_reference_param_state(st: dict, p: Tensor) -> None:
-        """a parameter OUTSIDE the arena (REPA projector / resampler tensors that share the denoiser's param group,
-        examples/train_repa.py) resumed from a torch.optim.AdamW checkpoint: rename exp_avg / exp_avg_sq to this class's m / v"""
-        if "m" not in st and "exp_avg" in st and "exp_avg_sq" in st:
-            st["m"] = st.pop("exp_avg").to(device=p.device, dtype=torch.float32).contiguous()
-            st["v"] = st.pop("exp_avg_sq").to(device=p.device, dtype=torch.float32).contiguous()
-            st.pop("max_exp_avg_sq", None)
-            st["step"] = int(st.get("step", 0))
 
     def _flat(self, group) -> tuple[Tensor, Tensor, list] | None:
         """`_flat_scan(group)`, remembered per group: a hit is re-validated by pointer compares only (every arena parameter's data and
@@ -232,6 +192,65 @@ class FusedAdamW(torch.optim.Optimizer):
         ops.clip_coef(self._clip_partials, slot, self.max_grad_norm, self._clip_out, self.grad_scale, hyper)
         return self._clip_out[1:2]
 
+
+class FusedAdamW(FusedArenaOptimizer):
+    """``torch.optim.AdamW``'s update in one launch per arena; ``max_grad_norm`` as in `FusedArenaOptimizer`."""
+
+    def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, max_grad_norm: float | None = None) -> None:
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm)
+        self._legacy_arena_states: list[dict] = []
+
+    def _graph_scalars(self, group: dict, step: int) -> list[float]:
+        b1, b2 = group["betas"]
+        bc1, bc2 = 1.0 - b1**step, 1.0 - b2**step
+        return [group["lr"], b1, b2, group["eps"], group["weight_decay"], group["lr"] / bc1, bc2**-0.5, self.grad_scale]
+
+    def load_state_dict(self, state_dict) -> None:
+        """accepts three optimizer.pt layouts: this class's own (arena-sized ``m`` / ``v`` / ``step`` under the first arena
+        parameter of a group, per-parameter ``m`` / ``v`` / ``step`` for tensors outside the arena), the reference's
+        ``torch.optim.AdamW`` checkpoint (per-parameter ``exp_avg`` / ``exp_avg_sq`` / ``step``: packed into the arena moments at
+        the first step, see _adopt_reference_state) and the address-keyed ``arena*`` entries round 1 wrote (matched by size)"""
+        super().load_state_dict(state_dict)
+        for k in [k for k in self.state if isinstance(k, str) and k.startswith("arena")]:
+            self._legacy_arena_states.append(self.state.pop(k))
+
+    def _adopt_reference_state(self, pb: Tensor, inside: list, key: Tensor) -> None:
+        """torch.optim.AdamW state (the reference's optimizer.pt, base_trainer.py:246-251) -> arena moments: every arena
+        parameter's exp_avg / exp_avg_sq is copied to its offset, the step count is the parameters' common one"""
+        m, v = torch.zeros_like(pb), torch.zeros_like(pb)
+        steps = set()
+        base = pb.storage_offset()
+        for p in inside:
+            st = self.state.get(p)
+            if not st:
+                continue
+            if "exp_avg" not in st or "exp_avg_sq" not in st:
+                raise RuntimeError(f"optimizer state of an arena parameter has keys {sorted(st)}: expected FusedAdamW's "
+                                   "('m', 'v', 'step') or torch.optim.AdamW's ('exp_avg', 'exp_avg_sq', 'step')")
+            o = p.data.storage_offset() - base
+            m[o : o + p.numel()].copy_(st["exp_avg"].reshape(-1).to(pb.device, torch.float32))
+            v[o : o + p.numel()].copy_(st["exp_avg_sq"].reshape(-1).to(pb.device, torch.float32))
+            steps.add(int(st["step"]))
+            if p is not key:
+                del self.state[p]
+        if len(steps) > 1:
+            raise RuntimeError(f"torch.optim.AdamW checkpoint with different step counts per parameter ({sorted(steps)}): the arena "
+                               "update has one")
+        st = self.state[key]
+        st.clear()
+        st["step"], st["m"], st["v"] = (steps.pop() if steps else 0), m, v
+
+    @staticmethod
+    def _adopt_reference_param_state(st: dict, p: Tensor) -> None:
+        """a parameter OUTSIDE the arena (REPA projector / resampler tensors that share the denoiser's param group,
+        examples/train_repa.py) resumed from a torch.optim.AdamW checkpoint: rename exp_avg / exp_avg_sq to this class's m / v"""
+        if "m" not in st and "exp_avg" in st and "exp_avg_sq" in st:
+            st["m"] = st.pop("exp_avg").to(device=p.device, dtype=torch.float32).contiguous()
+            st["v"] = st.pop("exp_avg_sq").to(device=p.device, dtype=torch.float32).contiguous()
+            st.pop("max_exp_avg_sq", None)
+            st["step"] = int(st.get("step", 0))
+
     def _update(self, p: Tensor, g: Tensor, st: dict, group: dict, coef: Tensor | None) -> None:
         b1, b2 = group["betas"]
         if coef is None:
@@ -305,5 +324,110 @@ class FusedAdamW(torch.optim.Optimizer):
                         st["m"], st["v"] = st["m"].to(p.device), st["v"].to(p.device)
                     st["step"] = int(st["step"]) + 1
                     self._update(p.data, p.grad, st, group, coef)
+            bump_param_epoch()
+        return loss
+
+
+class FusedSGD(FusedArenaOptimizer):
+    """``torch.optim.SGD``'s update (``configs/optimizer/sgd.yaml``: momentum, dampening, weight decay, Nesterov, maximize) in ONE
+    `dl_sgd_step` launch per arena and one per tensor outside it; ``max_grad_norm``, ``grad_scale`` and graph mode as in
+    `FusedArenaOptimizer`.  State: one arena-sized ``buf`` plus ``step`` under the group's first arena parameter, ``buf`` / ``step``
+    per tensor outside the arena, and no buffer at all with ``momentum == 0``.  As in torch, a tensor's first step with momentum
+    copies the gradient into the buffer (no dampening).  ``foreach`` / ``fused`` / ``differentiable`` are accepted, as a config may
+    pass them, and ignored."""
+
+    def __init__(self, params, lr: float = 1e-3, momentum: float = 0, dampening: float = 0, weight_decay: float = 0,
+                 nesterov: bool = False, maximize: bool = False, max_grad_norm: float | None = None, foreach=None, fused=None,
+                 differentiable: bool = False) -> None:
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                                      maximize=maximize), max_grad_norm)
+
+    def _graph_scalars(self, group: dict, step: int) -> list[float]:
+        # ([5], [6] are unused; dl_sgd_step_dev reads grad_scale at [4], dl_clip_coef at [7])
+        return [group["lr"], group["momentum"], group["dampening"], group["weight_decay"], self.grad_scale, 0.0, 0.0, self.grad_scale]
+
+    def _adopt_reference_state(self, pb: Tensor, group: dict, inside: list, key: Tensor) -> None:
+        """torch.optim.SGD state (the reference's optimizer.pt: per-parameter ``momentum_buffer``) -> the arena buffer: every arena
+        parameter's buffer is copied to its offset.  Buffers that are all None (or no state at all): the first step.  Both kinds
+        side by side cannot be one launch's state (torch would dampen the one and not the other): refused"""
+        have = [p for p in inside if (self.state.get(p) or {}).get("momentum_buffer") is not None]
+        if have and len(have) != len(inside):
+            index = {id(p): i for i, p in enumerate(group["params"])}
+            ids = {id(p) for p in have}
+            without = [index[id(p)] for p in inside if id(p) not in ids]
+            raise RuntimeError(f"torch.optim.SGD checkpoint: {len(have)} arena parameters have a 'momentum_buffer' and {len(without)} "
+                               f"have none (positions {without[:8]}{' ...' if len(without) > 8 else ''} of the group; state keys "
+                               f"{[sorted(self.state.get(group['params'][i]) or {}) for i in without[:8]]}): the arena update has one "
+                               "buffer for all of them")
+        buf = torch.zeros_like(pb) if have else None
+        base = pb.storage_offset()
+        for p in inside:
+            st = self.state.get(p)
+            if st is None:
+                continue
+            mb = st.pop("momentum_buffer", None)
+            if mb is not None:
+                o = p.data.storage_offset() - base
+                buf[o : o + p.numel()].copy_(mb.reshape(-1).to(pb.device, torch.float32))
+            if p is not key and not st:
+                del self.state[p]
+        if buf is not None:
+            self.state[key]["buf"] = buf
+
+    def _update(self, p: Tensor, g: Tensor, st: dict, group: dict, hyper: Tensor | None, coef: Tensor | None) -> None:
+        mom = group["momentum"]
+        buf = st.get("buf") if mom != 0 else None
+        first = mom != 0 and buf is None
+        if buf is not None and buf.numel() != p.numel():
+            raise RuntimeError(f"optimizer state does not match its parameter: a momentum buffer of {buf.numel()} elements for "
+                               f"{p.numel()} parameters")
+        if hyper is not None:  # captured step: the scalars come from the device buffer, advance() counts the step
+            if first:
+                raise RuntimeError("graph mode needs the momentum buffer: run one eager step() first (also after loading a checkpoint)")
+            ops.sgd_step_dev(p, g, buf, hyper, coef, group["nesterov"], group["maximize"])
+            return
+        if first:
+            buf = st["buf"] = torch.empty_like(p)  # (written, not read, by the first step)
+        elif buf is not None and buf.device != p.device:  # state loaded before the model moved
+            buf = st["buf"] = buf.to(p.device)
+        st["step"] = int(st.get("step", 0)) + 1
+        ops.sgd_step(p, g, buf, group["lr"], mom, group["dampening"], group["weight_decay"], self.grad_scale, coef,
+                     group["nesterov"], first, group["maximize"])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        coef = self._clip_pass() if self.max_grad_norm is not None else None
+        for gi, group in enumerate(self.param_groups):
+            hyper = self._graph_hyper[gi][0] if self._graph_hyper is not None else None
+            flat = self._flat(group)
+            rest = group["params"]
+            if flat is not None:
+                pb, gb, rest = flat
+                # (keyed on the group's first arena parameter, for the reason FusedAdamW.step gives)
+                key = self._arena_key(group, rest)
+                st = self.state[key]
+                if group["momentum"] != 0 and "buf" not in st and hyper is None:  # the first step, or a torch.optim.SGD checkpoint
+                    skip = {id(p) for p in rest}
+                    self._adopt_reference_state(pb, group, [p for p in group["params"] if id(p) not in skip and p.requires_grad], key)
+                self._update(pb, gb, st, group, hyper, coef)
+                bump_param_epoch()  # raw-pointer writes bump no torch version counter: tell the engines
+            for p in rest:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if "momentum_buffer" in st:  # a torch.optim.SGD checkpoint: its buffer under this class's name (None: first step)
+                    mb = st.pop("momentum_buffer")
+                    if mb is not None and "buf" not in st:
+                        st["buf"] = mb.to(device=p.device, dtype=torch.float32).contiguous()
+                self._update(p.data, p.grad, st, group, hyper, coef)
             bump_param_epoch()
         return loss

@@ -2,7 +2,7 @@
 
 ``training_step`` keeps the reference's order of operations (base_trainer.py:138-153): zero_grad -> draw timesteps (CPU generator)
 -> compute_loss -> every loss into the tracker (the reference's ``.item()``; here a device scalar the meter reads back lazily) -> backward -> [clip by
-global gradient norm when ``max_grad_norm`` is set: fused into the AdamW update, ``train/grad_norm`` into the tracker] -> optimizer.step -> scheduler -> EMA update.
+global gradient norm when ``max_grad_norm`` is set: fused into the AdamW / SGD update, ``train/grad_norm`` into the tracker] -> optimizer.step -> scheduler -> EMA update.
 What Accelerate did implicitly is spelled out (see trainers/common.py): loss / gradient_accumulation_step before backward,
 ``zero_grad`` / ``step`` / scheduler gated on the synchronising micro-step (so with k > 1 the default reproduces the reference's
 "(1/k) * gradient of the last micro-batch" update), EMA on every micro-step, gradient all-reduce overlapped

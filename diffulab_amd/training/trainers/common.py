@@ -163,7 +163,7 @@ class Trainer(ABC):
                 if hasattr(optimizer, "grad_scale"):
                     optimizer.grad_scale = self._reducer.grad_scale
                 else:
-                    raise RuntimeError("data-parallel training needs diffulab_amd.training.FusedAdamW (grad_scale = 1/world)")
+                    raise RuntimeError("data-parallel training needs diffulab_amd.training.FusedAdamW or FusedSGD (grad_scale = 1/world)")
 
     def broadcast_extra_losses(self, diffuser: "Diffuser") -> None:
         """accelerator.prepare(loss) DDP-wraps the auxiliary loss heads (REPA projector / resampler): every rank starts from
@@ -265,13 +265,14 @@ class Trainer(ABC):
                     off += g.numel()
 
     def clip_gradients(self, optimizer: Optimizer):
-        """before ``optimizer.step()`` of the synchronising micro-step, the reducer done: ``FusedAdamW`` takes the bound and clips
-        inside its update (None is returned: the norm exists after the step, ``optimizer.last_grad_norm``); any other optimizer has
-        its gradients scaled in place here, and the total-norm device scalar is returned"""
-        from ..optim import FusedAdamW
+        """before ``optimizer.step()`` of the synchronising micro-step, the reducer done: a fused optimizer (``FusedAdamW``,
+        ``FusedSGD``) takes the bound and clips inside its update (None is returned: the norm exists after the step,
+        ``optimizer.last_grad_norm``); any other optimizer has its gradients scaled in place here, and the total-norm device scalar
+        is returned"""
+        from ..optim import FusedArenaOptimizer
         from ..utils import clip_grad_norm_
 
-        if isinstance(optimizer, FusedAdamW):
+        if isinstance(optimizer, FusedArenaOptimizer):
             optimizer.max_grad_norm = self.max_grad_norm
             return None
         params = [p for group in optimizer.param_groups for p in group["params"]]

@@ -495,9 +495,32 @@ DL_API int dl_adamw_step_clip(float* p, const float* g, float* m, float* v, int6
                               const float* coef, dl_stream_t stream);
 DL_API int dl_adamw_step_dev_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const float* coef,
                                   dl_stream_t stream);
-/* g *= *coef in place (4-byte aligned, any n): clip_grad_norm_'s own write-back, for optimizers other than the fused AdamW
- * (configs/optimizer/sgd.yaml).  *coef == 1 leaves the buffer untouched. */
+/* g *= *coef in place (4-byte aligned, any n): clip_grad_norm_'s own write-back, for optimizers other than the fused ones
+ * (a stock torch.optim optimizer on the arena views).  *coef == 1 leaves the buffer untouched. */
 DL_API int dl_scale_inplace(float* g, int64_t n, const float* coef, dl_stream_t stream);
+/* torch.optim.SGD single-tensor math (configs/optimizer/sgd.yaml; the optimizer.step() of base_trainer.py:149) over a flat f32
+ * buffer, one launch:
+ *   gr = g * gs  (gs = grad_scale, or grad_scale * *coef with `coef` non-NULL: &out[1] of dl_clip_coef, a DEVICE pointer)
+ *   MAXIMIZE: gr = -gr ;  weight_decay != 0: gr += weight_decay * p
+ *   momentum != 0:  buf = gr (FIRST: torch clones the gradient, no dampening on the first step)
+ *                   buf = momentum * buf + (1 - dampening) * gr (otherwise) ;  gr = NESTEROV ? gr + momentum * buf : buf
+ *   p -= lr * gr
+ * p, g, buf: any 4-byte aligned pointers and any n > 0 (float4 when the three share one 16-byte phase, with a scalar head and
+ * tail; a scalar loop when the phases differ).  momentum == 0: buf may be NULL and is neither read nor written.  FIRST writes
+ * buf without reading it.  g is never written.  *coef == 1 gives bit for bit the plain update, and coefficient c the plain update
+ * with grad_scale = float32(grad_scale * c).  Refused with DL_ERR_INVALID before any launch: NULL p or g, n <= 0, momentum != 0
+ * with NULL buf, NESTEROV with momentum == 0 or dampening != 0, unknown flag bits. */
+enum { DL_SGD_NESTEROV = 1, DL_SGD_FIRST = 2, DL_SGD_MAXIMIZE = 4 };
+DL_API int dl_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float dampening,
+                       float weight_decay, float grad_scale, const float* coef, int flags, dl_stream_t stream);
+/* the same update (bit for bit on the same scalars) with its scalars in device memory: hyper = f32[8] {lr, momentum, dampening,
+ * weight_decay, grad_scale, 0, 0, 0}.  No per-step value travels in the launch (a captured hipGraph of the training step,
+ * base_trainer.py:138-151, replays with the host refreshing 32 bytes).  The host cannot see the momentum here: buf != NULL means
+ * "with momentum" (hyper[1] must then be non-zero), buf == NULL "without" (hyper[1] is ignored).  FIRST is refused: the momentum
+ * buffer must already exist, as the moments must for dl_adamw_step_dev.  hyper[5..7] are not read here; a caller that also clips
+ * repeats grad_scale in hyper[7], where dl_clip_coef reads it. */
+DL_API int dl_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const float* hyper, const float* coef, int flags,
+                           dl_stream_t stream);
 /* bf16 shadow of an f32 [R,C] weight: dst [R, ld_dst] (cols >= C zeroed up to ld_dst) and/or the transpose
  * dstT [C, ld_t] (cols >= R zeroed up to ld_t).  Either destination may be NULL. */
 DL_API int dl_cast_weight(const float* src, int64_t R, int64_t C, void* dst, int64_t ld_dst, void* dstT,

@@ -353,6 +353,68 @@ extern "C" int dl_ddpm_step(const float* pred, const float* pred_uncond, float g
   return DL_OK;
 }
 
+// learned variances (ddpm.py:212-222, 268-282): pred / pu are [B, 2 chw], element (b, r) has its mean output at b 2chw + r and its raw
+// variance output at b 2chw + chw + r, both read in place.  tab: f32 [6][T] = sqrt_ab, ab, coef1, coef2, posterior_log_variance_clipped,
+// betas.  The log-variance of one element, shared with the hybrid loss below:
+__device__ __forceinline__ float learned_log_var(int var_mode, float v, float min_log, float beta) {
+  if (var_mode == DL_VAR_LEARNED) return v;
+  const float w = (v + 1.0f) / 2.0f;  // ddpm.py:218-221; log(betas[t]) in f32 after the gather
+  return w * logf(beta) + (1.0f - w) * min_log;
+}
+__global__ void ddpm_step_lv_k(const float* __restrict__ pred, const float* __restrict__ pu, float g,
+                               const float* __restrict__ xt, const float* __restrict__ noise,
+                               const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T, int mean_type,
+                               int var_mode, int clamp_x, float* __restrict__ xp, float* __restrict__ x0o,
+                               float* __restrict__ mo, float* __restrict__ so, float* __restrict__ lp, int64_t n,
+                               int64_t chw) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t b = i / chw;
+    const int32_t ti = t[b];
+    const float sab = tab[ti], ab = tab[T + ti], c1 = tab[2 * T + ti], c2 = tab[3 * T + ti];
+    const float min_log = tab[4 * T + ti], beta = tab[5 * T + ti];
+    const int64_t pi = i + b * chw;
+    float o = pred[pi], v = pred[pi + chw];
+    if (pu) {  // the CFG combine acts on the whole 2C tensor before the chunk (gaussian_diffusion.py:253-255)
+      const float uo = pu[pi], uv = pu[pi + chw];
+      o = uo + g * (o - uo);
+      v = uv + g * (v - uv);
+    }
+    const float lv = learned_log_var(var_mode, v, min_log, beta);
+    const float var = expf(lv);
+    const float x = xt[i];
+    float x0 = x_start_from(mean_type, o, x, sab, ab, c1, c2);
+    if (clamp_x) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float m = c1 * x0 + c2 * x;
+    const float mask = ti > 0 ? 1.0f : 0.0f;
+    const float xpv = m + mask * noise[i] * expf(0.5f * lv);
+    xp[i] = xpv;
+    if (x0o) x0o[i] = x0;
+    if (mo) mo[i] = m;
+    const float vs = fmaxf(var, 1e-20f);
+    if (so) so[i] = sqrtf(vs);
+    if (lp) {
+      const float d = xpv - m;
+      lp[i] = (-(d * d) / (2.0f * vs) - logf(6.283185307179586f * vs) * 0.5f) * mask;
+    }
+  }
+}
+extern "C" int dl_ddpm_step_lv(const float* pred, const float* pred_uncond, float guidance, const float* xt,
+                               const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
+                               int var_mode, int clamp_x, float* x_prev, float* x0_est, float* mean, float* std,
+                               float* logprob, int64_t batch, int64_t chw, dl_stream_t stream) {
+  DL_CHECK_ARG(pred && xt && noise && t && tables && x_prev && batch > 0 && chw > 0 && T > 0, "dl_ddpm_step_lv: bad args");
+  DL_CHECK_ARG(mean_type >= 0 && mean_type <= 2, "dl_ddpm_step_lv: mean_type %d", mean_type);
+  DL_CHECK_ARG(var_mode == DL_VAR_LEARNED || var_mode == DL_VAR_LEARNED_RANGE, "dl_ddpm_step_lv: var_mode %d", var_mode);
+  const int64_t n = batch * chw;
+  hipLaunchKernelGGL(ddpm_step_lv_k, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t,
+                     tables, T, mean_type, var_mode, clamp_x, x_prev, x0_est, mean, std, logprob, n, chw);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// HALVES: pred / pu are [B, 2 chw] and the step reads the mean half in place (learned variances, which DDIM discards: ddim.py:89)
+template <bool HALVES>
 __global__ void ddim_step_k(const float* __restrict__ pred, const float* __restrict__ pu, float g,
                             const float* __restrict__ xt, const float* __restrict__ noise,
                             const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T, int mean_type,
@@ -365,9 +427,10 @@ __global__ void ddim_step_k(const float* __restrict__ pred, const float* __restr
     const int32_t ti = t[i / chw];
     const float sab = tab[ti], ab = tab[T + ti], abp = tab[2 * T + ti];
     const float c1 = coefs ? coefs[ti] : 1.0f, c2 = coefs ? coefs[T + ti] : 0.0f;
-    float o = pred[i];
+    const int64_t pi = HALVES ? i + (i / chw) * chw : i;
+    float o = pred[pi];
     if (pu) {
-      const float u = pu[i];
+      const float u = pu[pi];
       o = u + g * (o - u);
     }
     const float x = xt[i];
@@ -396,8 +459,152 @@ extern "C" int dl_ddim_step(const float* pred, const float* pred_uncond, float g
   DL_CHECK_ARG(pred && xt && noise && t && tables && x_prev && batch > 0 && chw > 0 && T > 0, "dl_ddim_step: bad args");
   DL_CHECK_ARG(mean_type != DL_MEAN_XPREV || ddpm_coefs, "dl_ddim_step: xprev needs ddpm_coefs");
   const int64_t n = batch * chw;
-  hipLaunchKernelGGL(ddim_step_k, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t,
+  hipLaunchKernelGGL(ddim_step_k<false>, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t,
                      tables, T, mean_type, ddpm_coefs, clamp_x, eta, x_prev, x0_est, mean, std, logprob, n, chw);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_ddim_step_lv(const float* pred, const float* pred_uncond, float guidance, const float* xt,
+                               const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
+                               const float* ddpm_coefs, int clamp_x, float eta, float* x_prev, float* x0_est,
+                               float* mean, float* std, float* logprob, int64_t batch, int64_t chw,
+                               dl_stream_t stream) {
+  DL_CHECK_ARG(pred && xt && noise && t && tables && x_prev && batch > 0 && chw > 0 && T > 0, "dl_ddim_step_lv: bad args");
+  DL_CHECK_ARG(mean_type >= 0 && mean_type <= 2, "dl_ddim_step_lv: mean_type %d", mean_type);
+  DL_CHECK_ARG(mean_type != DL_MEAN_XPREV || ddpm_coefs, "dl_ddim_step_lv: xprev needs ddpm_coefs");
+  const int64_t n = batch * chw;
+  hipLaunchKernelGGL(ddim_step_k<true>, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t,
+                     tables, T, mean_type, ddpm_coefs, clamp_x, eta, x_prev, x0_est, mean, std, logprob, n, chw);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// ---------------------------------------------------------------- hybrid loss of a learned-variance model
+// L_simple + L_vlb of Nichol & Dhariwal, "Improved Denoising Diffusion Probabilistic Models" (2021), eq. 16, which the reference
+// announces and leaves unwritten (gaussian_diffusion.py:267).  One element's variational-bound term in nats and, where GRAD, its
+// derivative with respect to the raw variance output v.  The predicted mean m_p is a constant of that term (the paper's stop-gradient):
+// nothing flows into the mean output from here.  tab as in ddpm_step_lv_k.
+#define VLB_SQRT_2_OVER_PI 0.7978845608028654f
+__device__ __forceinline__ float approx_cdf(float z, float* dz) {  // 0.5 (1 + tanh(sqrt(2/pi) (z + 0.044715 z^3))) and its derivative
+  const float th = tanhf(VLB_SQRT_2_OVER_PI * (z + 0.044715f * z * z * z));
+  if (dz) *dz = 0.5f * (1.0f - th * th) * VLB_SQRT_2_OVER_PI * (1.0f + 3.0f * 0.044715f * z * z);
+  return 0.5f * (1.0f + th);
+}
+template <bool GRAD>
+__device__ __forceinline__ float vlb_elem(int mean_type, int var_mode, int32_t ti, float o, float v, float x0, float x, float sab,
+                                          float ab, float c1, float c2, float lv_q, float beta, float* dterm_dv) {
+  const float m_p = c1 * x_start_from(mean_type, o, x, sab, ab, c1, c2) + c2 * x;  // no clamp
+  const float lv_p = learned_log_var(var_mode, v, lv_q, beta);
+  float term, dlv;
+  if (ti > 0) {  // KL(q(x_{t-1} | x_t, x_0) || p(x_{t-1} | x_t))
+    const float d = c1 * x0 + c2 * x - m_p;
+    const float r = expf(lv_q - lv_p), q = d * d * expf(-lv_p);
+    term = 0.5f * (-1.0f + lv_p - lv_q + r + q);
+    dlv = 0.5f * (1.0f - r - q);
+  } else {  // -log of the discretised Gaussian likelihood of x0 (bins of width 2/255), log_scale = lv_p / 2
+    const float c = x0 - m_p, s = expf(-0.5f * lv_p);
+    const float zp = s * (c + 1.0f / 255.0f), zm = s * (c - 1.0f / 255.0f);
+    float dP = 0.f, dQ = 0.f;
+    const float P = approx_cdf(zp, GRAD ? &dP : nullptr), Q = approx_cdf(zm, GRAD ? &dQ : nullptr);
+    // d z / d lv_p = -z / 2;  a clamped max(., 1e-12) passes no gradient (torch.clamp)
+    float prob, dprob;
+    if (x0 < -0.999f) prob = P, dprob = dP * (-0.5f * zp);
+    else if (x0 > 0.999f) prob = 1.0f - Q, dprob = -dQ * (-0.5f * zm);
+    else prob = P - Q, dprob = dP * (-0.5f * zp) - dQ * (-0.5f * zm);
+    term = -logf(fmaxf(prob, 1e-12f));
+    dlv = prob > 1e-12f ? -dprob / prob : 0.0f;
+  }
+  if (GRAD) *dterm_dv = dlv * (var_mode == DL_VAR_LEARNED ? 1.0f : 0.5f * (logf(beta) - lv_q));
+  return term;
+}
+// partial[blk] = sum (eps - o)^2 and partial[np + blk] = sum of the bound terms over the block's MSE_ELEMS_PER_BLOCK elements, in the
+// element-to-thread order of mse_partial_k (the first sum is bit for bit that kernel's on the mean half)
+__global__ void vlb_partial_k(const float* __restrict__ pred, const float* __restrict__ eps, const float* __restrict__ x0,
+                              const float* __restrict__ xt, const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T,
+                              int mean_type, int var_mode, float* __restrict__ partial, int64_t np, int64_t n, int64_t chw) {
+  __shared__ float red[2][MSE_BLOCK / DL_WAVE];
+  const int64_t base = (int64_t)blockIdx.x * MSE_ELEMS_PER_BLOCK;
+  float acc = 0.f, vacc = 0.f;
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int64_t i = base + (int64_t)j * MSE_BLOCK + threadIdx.x;
+    if (i < n) {
+      const int64_t b = i / chw, pi = i + b * chw;
+      const int32_t ti = t[b];
+      const float o = pred[pi];
+      const float d = eps[i] - o;
+      acc += d * d;
+      vacc += vlb_elem<false>(mean_type, var_mode, ti, o, pred[pi + chw], x0[i], xt[i], tab[ti], tab[T + ti], tab[2 * T + ti],
+                              tab[3 * T + ti], tab[4 * T + ti], tab[5 * T + ti], nullptr);
+    }
+  }
+  acc = wave_sum(acc);
+  vacc = wave_sum(vacc);
+  if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = acc, red[1][threadIdx.x >> 6] = vacc;
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    float s = 0.f;
+    for (int w = 0; w < MSE_BLOCK / DL_WAVE; ++w) s += red[threadIdx.x][w];
+    partial[threadIdx.x * np + blockIdx.x] = s;
+  }
+}
+__global__ void vlb_final_k(const float* __restrict__ partial, float* __restrict__ loss, int64_t np, float inv_n, float inv_n_ln2) {
+  __shared__ float red[2][256 / DL_WAVE];
+  float acc = 0.f, vacc = 0.f;
+  for (int64_t i = threadIdx.x; i < np; i += 256) acc += partial[i], vacc += partial[np + i];
+  acc = wave_sum(acc);
+  vacc = wave_sum(vacc);
+  if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = acc, red[1][threadIdx.x >> 6] = vacc;
+  __syncthreads();
+  if (threadIdx.x < 2)
+    loss[threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]) * (threadIdx.x ? inv_n_ln2 : inv_n);
+}
+static int vlb_check(const char* who, const void* pred, const void* eps, const void* x0, const void* xt, const void* t,
+                     const void* tables, int32_t T, int mean_type, int var_mode, int64_t batch, int64_t chw) {
+  DL_CHECK_ARG(pred && eps && x0 && xt && t && tables && batch > 0 && chw > 0 && T > 0, "%s: bad args", who);
+  DL_CHECK_ARG(mean_type >= 0 && mean_type <= 2, "%s: mean_type %d", who, mean_type);
+  DL_CHECK_ARG(var_mode == DL_VAR_LEARNED || var_mode == DL_VAR_LEARNED_RANGE, "%s: var_mode %d", who, var_mode);
+  return DL_OK;
+}
+extern "C" int dl_vlb_loss_fwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                               const float* tables, int32_t T, int mean_type, int var_mode, float* partial, float* loss,
+                               int64_t batch, int64_t chw, dl_stream_t stream) {
+  if (int rc = vlb_check("dl_vlb_loss_fwd", pred, eps, x0, xt, t, tables, T, mean_type, var_mode, batch, chw)) return rc;
+  DL_CHECK_ARG(partial && loss, "dl_vlb_loss_fwd: bad args (partial, loss)");
+  const int64_t n = batch * chw, np = dl_mse_loss_partials(n);
+  hipLaunchKernelGGL(vlb_partial_k, (int)np, MSE_BLOCK, 0, (hipStream_t)stream, pred, eps, x0, xt, t, tables, T, mean_type, var_mode,
+                     partial, np, n, chw);
+  hipLaunchKernelGGL(vlb_final_k, 1, 256, 0, (hipStream_t)stream, partial, loss, np, (float)(1.0 / (double)n),
+                     (float)(1.0 / ((double)n * 0.6931471805599453)));
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+__global__ void vlb_bwd_k(const float* __restrict__ pred, const float* __restrict__ eps, const float* __restrict__ x0,
+                          const float* __restrict__ xt, const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T,
+                          int mean_type, int var_mode, float coef_m, float coef_v, const float* __restrict__ g_mse,
+                          const float* __restrict__ g_vb, float* __restrict__ dpred, int64_t n, int64_t chw) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (g_mse) coef_m *= *g_mse;  // as mse_bwd_k forms its coefficient: the mean half is that kernel's output bit for bit
+  if (g_vb) coef_v *= *g_vb;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t b = i / chw, pi = i + b * chw;
+    const int32_t ti = t[b];
+    const float o = pred[pi];
+    float dv;
+    vlb_elem<true>(mean_type, var_mode, ti, o, pred[pi + chw], x0[i], xt[i], tab[ti], tab[T + ti], tab[2 * T + ti], tab[3 * T + ti],
+                   tab[4 * T + ti], tab[5 * T + ti], &dv);
+    dpred[pi] = coef_m * (o - eps[i]);
+    dpred[pi + chw] = coef_v * dv;
+  }
+}
+extern "C" int dl_vlb_loss_bwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                               const float* tables, int32_t T, int mean_type, int var_mode, const float* g_mse_dev,
+                               const float* g_vb_dev, float* dpred, int64_t batch, int64_t chw, dl_stream_t stream) {
+  if (int rc = vlb_check("dl_vlb_loss_bwd", pred, eps, x0, xt, t, tables, T, mean_type, var_mode, batch, chw)) return rc;
+  DL_CHECK_ARG(dpred, "dl_vlb_loss_bwd: bad args (dpred)");
+  const int64_t n = batch * chw;
+  hipLaunchKernelGGL(vlb_bwd_k, ew_grid(n), 256, 0, (hipStream_t)stream, pred, eps, x0, xt, t, tables, T, mean_type, var_mode,
+                     (float)(2.0 / (double)n), (float)(1.0 / ((double)n * 0.6931471805599453)), g_mse_dev, g_vb_dev, dpred, n, chw);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }

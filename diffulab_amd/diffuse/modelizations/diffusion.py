@@ -40,6 +40,35 @@ def mse_head(pred: Tensor, a: Tensor, b: Tensor | None, mode: int) -> Tensor:
     return ops.mse_loss_fwd(pred.float().contiguous(), a, b, mode)
 
 
+class _HybridHead(torch.autograd.Function):
+    """(mse, vb) of a learned-variance [B, 2C, ...] prediction -- dl_vlb_loss_fwd / _bwd.  mse = mean((eps - mean half)^2); vb = the
+    variational bound in bits per dimension with the predicted mean frozen, so it trains the variance half only (Nichol & Dhariwal
+    2021, eq. 16; the reference leaves this loss as a TODO, gaussian_diffusion.py:267)."""
+
+    @staticmethod
+    def forward(ctx, pred: Tensor, eps: Tensor, x0: Tensor, xt: Tensor, t: Tensor, tables: Tensor, mean_type: int, var_mode: int):
+        pred = pred.float().contiguous()
+        ctx.save_for_backward(pred, eps, x0, xt, t, tables)
+        ctx.modes = (mean_type, var_mode)
+        both = ops.vlb_loss_fwd(pred, eps, x0, xt, t, tables, mean_type, var_mode)
+        return both[0], both[1]
+
+    @staticmethod
+    def backward(ctx, g_mse: Tensor, g_vb: Tensor):
+        # both upstream gradients stay on the device (an unused output arrives as zeros); one kernel writes the whole dpred
+        dpred = ops.vlb_loss_bwd(*ctx.saved_tensors, *ctx.modes, g_mse.float().contiguous(), g_vb.float().contiguous())
+        return dpred, None, None, None, None, None, None, None
+
+
+def hybrid_head(pred: Tensor, eps: Tensor, x0: Tensor, xt: Tensor, t: Tensor, tables: Tensor, mean_type: int,
+                var_mode: int) -> tuple[Tensor, Tensor]:
+    eps, x0, xt = (v.float().contiguous() for v in (eps, x0, xt))
+    if pred.requires_grad:
+        return _HybridHead.apply(pred, eps, x0, xt, t, tables, mean_type, var_mode)
+    both = ops.vlb_loss_fwd(pred.float().contiguous(), eps, x0, xt, t, tables, mean_type, var_mode)
+    return both[0], both[1]
+
+
 class Diffusion(ABC):
     sampler_registry: dict[str, type[Sampler]]
 

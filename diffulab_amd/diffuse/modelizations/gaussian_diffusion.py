@@ -17,7 +17,7 @@ from ... import ops
 from ..samplers.common import StepResult
 from ..samplers.gaussian_diffusion import DDIM, DDPM
 from ..utils import SamplingOutput, f32_table, to_device
-from .diffusion import Diffusion, mse_head
+from .diffusion import Diffusion, hybrid_head, mse_head
 from .utils import space_timesteps
 
 try:
@@ -31,10 +31,12 @@ class GaussianDiffusion(Diffusion):
     sampler_registry = {"ddpm": DDPM, "ddim": DDIM}
 
     def __init__(self, n_steps: int = 1000, sampling_method: str = "ddpm", schedule: str = "linear",
-                 latent_diffusion: bool = False, sampler_parameters: dict[str, Any] = {}) -> None:
+                 latent_diffusion: bool = False, sampler_parameters: dict[str, Any] = {}, vlb_weight: float | None = None) -> None:
         if sampling_method not in ["ddpm", "ddim"]:
             raise ValueError("sampling method must be one of ['ddpm', 'ddim']")
         self.training_steps = n_steps
+        # weight of the variational-bound term of a learned-variance model's loss: Improved DDPM rescales it by T / 1000
+        self.vlb_weight = n_steps / 1000 if vlb_weight is None else float(vlb_weight)
         self._dev: dict[torch.device, tuple[Tensor, Tensor]] = {}
         super().__init__(n_steps=self.training_steps, sampling_method=sampling_method, schedule=schedule,
                          latent_diffusion=latent_diffusion, sampler_parameters=sampler_parameters)
@@ -108,9 +110,28 @@ class GaussianDiffusion(Diffusion):
 
     def compute_loss(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None = None, extra_losses=[],
                      extra_args: dict[str, Any] = {}) -> dict[str, Tensor]:
+        if self.sampler.learned_variance:
+            return self._compute_loss_learned_variance(model, model_inputs, timesteps, noise, extra_losses, extra_args)
         model_inputs["x"], noise = self.add_noise(model_inputs["x"], timesteps, noise)
         prediction = model(**model_inputs, timesteps=self._remap(timesteps))["x"]
         loss_dict = {"loss": mse_head(prediction, noise, None, ops.LOSS_EPS)}
+        for extra_loss in extra_losses:
+            loss_dict[extra_loss.name] = extra_loss(**extra_args)
+        return loss_dict
+
+    def _compute_loss_learned_variance(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None, extra_losses,
+                                       extra_args: dict[str, Any]) -> dict[str, Tensor]:
+        """L_hybrid of Nichol & Dhariwal (2021), eq. 16, for a [B, 2C, ...] denoiser (the reference leaves it as a TODO,
+        gaussian_diffusion.py:267): "loss" = the usual MSE on the mean half, "vb" = vlb_weight * the variational bound in bits per
+        dimension, which trains the variance half only.  The trainer sums the dict and logs each entry."""
+        x0 = model_inputs["x"].float().contiguous()  # kept: add_noise's result replaces model_inputs["x"]
+        model_inputs["x"], noise = self.add_noise(x0, timesteps, noise)
+        xt = model_inputs["x"]
+        prediction = model(**model_inputs, timesteps=self._remap(timesteps))["x"]
+        self.sampler._check_halves(prediction, xt)
+        mse, vb = hybrid_head(prediction, noise, x0, xt, to_device(timesteps, xt.device, torch.int32), self.sampler._tables(xt.device),
+                              ops.MEAN_TYPES[self.sampler.mean_type], ops.VAR_MODES[self.sampler.var_type])
+        loss_dict = {"loss": mse, "vb": self.vlb_weight * vb}
         for extra_loss in extra_losses:
             loss_dict[extra_loss.name] = extra_loss(**extra_args)
         return loss_dict

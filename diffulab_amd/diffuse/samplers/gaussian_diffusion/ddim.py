@@ -26,11 +26,13 @@ class DDIM(DDPM):
              prediction_uncond: Tensor | None = None, guidance_scale: float = 0.0) -> StepResult:
         self._variance_tables()  # same var_type validation as DDPM._get_p_mean_var (ddim.py:89)
         tab, coefs = self._ddim_tables(xt.device)
+        if self.learned_variance:  # the 2C prediction's variance half is discarded (ddim.py:89); the mean half is read in place
+            self._check_halves(model_prediction, xt)
         noise = torch.randn_like(xt)  # ddim.py:63
         xp, x0, mean, std, lp = ops.ddim_step(
             model_prediction.float().contiguous(), None if prediction_uncond is None else prediction_uncond.float().contiguous(),
             guidance_scale, xt.float().contiguous(), noise, timesteps.to(torch.int32).contiguous(), tab, coefs,
-            _MEAN.index(self.mean_type), clamp_x, eta)
+            _MEAN.index(self.mean_type), clamp_x, eta, halves=self.learned_variance)
         out = StepResult(x_prev=xp, estimated_x0=x0, x_prev_mean=mean)
         if eta > 0:
             out["x_prev_std"] = std

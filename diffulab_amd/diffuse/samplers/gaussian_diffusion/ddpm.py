@@ -52,8 +52,18 @@ class DDPM(GaussianSampler):
         if self.var_type == "fixed_large":
             v = torch.cat([self.posterior_variance[1:2], self.betas[1:]])
             return v, torch.log(v)
-        raise NotImplementedError(
-            f"var_type={self.var_type!r}: learned variances need a 2x-channel denoiser head; not on the HIP path yet")
+        # learned / learned_range (ddpm.py:212-222): the variance comes from the prediction's second half; the kernel needs the two
+        # ends of the range, rows 4 and 5 of the learned table
+        return self.posterior_log_variance_clipped, self.betas
+
+    @property
+    def learned_variance(self) -> bool:
+        return self.var_type in ops.VAR_MODES
+
+    def _check_halves(self, model_prediction: Tensor, xt: Tensor) -> None:
+        assert model_prediction.shape[1] % 2 == 0, "a learned-variance prediction has an even channel count (ddpm.py:271)"
+        assert model_prediction.shape[1] == 2 * xt.shape[1] and model_prediction.shape[2:] == xt.shape[2:], (
+            f"var_type={self.var_type!r} takes a [B, 2C, ...] prediction for xt {tuple(xt.shape)}, got {tuple(model_prediction.shape)}")
 
     def _tables(self, device: torch.device) -> Tensor:
         key = ("ddpm", device, self.var_type)
@@ -66,6 +76,13 @@ class DDPM(GaussianSampler):
     def step(self, model_prediction: Tensor, timesteps: Tensor, xt: Tensor, clamp_x: bool = False,
              prediction_uncond: Tensor | None = None, guidance_scale: float = 0.0) -> StepResult:
         noise = torch.randn_like(xt)  # ddpm.py:302 (drawn for every t, masked at t == 0)
+        if self.learned_variance:  # `_tables` rows 4, 5 are then (posterior_log_variance_clipped, betas)
+            self._check_halves(model_prediction, xt)
+            xp, x0, mean, std, lp = ops.ddpm_step_lv(
+                model_prediction.float().contiguous(), None if prediction_uncond is None else prediction_uncond.float().contiguous(),
+                guidance_scale, xt.float().contiguous(), noise, timesteps.to(torch.int32).contiguous(), self._tables(xt.device),
+                _MEAN.index(self.mean_type), ops.VAR_MODES[self.var_type], clamp_x)
+            return StepResult(x_prev=xp, estimated_x0=x0, x_prev_mean=mean, x_prev_std=std, logprob=lp)
         xp, x0, mean, std, lp = ops.ddpm_step(
             model_prediction.float().contiguous(), None if prediction_uncond is None else prediction_uncond.float().contiguous(),
             guidance_scale, xt.float().contiguous(), noise, timesteps.to(torch.int32).contiguous(), self._tables(xt.device),

@@ -21,6 +21,7 @@ BF16, F32 = 0, 1
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 LOSS_FLOW, LOSS_EPS = 0, 1
 MEAN_TYPES = {"epsilon": 0, "xstart": 1, "xprev": 2}
+VAR_MODES = {"learned": 0, "learned_range": 1}
 PATCH_CPP, PATCH_PPC = 0, 1
 
 
@@ -163,6 +164,29 @@ def mse_loss_bwd(pred: Tensor, a: Tensor, b: Tensor | None, gscale: float, mode:
     return out
 
 
+def vlb_loss_fwd(pred: Tensor, eps: Tensor, x0: Tensor, xt: Tensor, t: Tensor, tables: Tensor, mean_type: int, var_mode: int,
+                 out: Tensor | None = None) -> Tensor:
+    """-> f32 [2] = (mse of the mean half, variational bound in bits / dim) of a [B, 2C, ...] prediction (dl_vlb_loss_fwd)"""
+    B, n = xt.shape[0], xt.numel()
+    assert pred.numel() == 2 * n and eps.numel() == n and x0.numel() == n
+    partial = torch.empty(2 * lib().call("dl_mse_loss_partials", n), device=pred.device, dtype=torch.float32)
+    out = torch.empty(2, device=pred.device, dtype=torch.float32) if out is None else out
+    _call("dl_vlb_loss_fwd", _p(pred), _p(eps), _p(x0), _p(xt), _p(t), _p(tables), tables.shape[1], mean_type, var_mode,
+          _p(partial), _p(out), B, n // B, _s())
+    return out
+
+
+def vlb_loss_bwd(pred: Tensor, eps: Tensor, x0: Tensor, xt: Tensor, t: Tensor, tables: Tensor, mean_type: int, var_mode: int,
+                 g_mse: Tensor | None, g_vb: Tensor | None, out: Tensor | None = None) -> Tensor:
+    """dpred [B, 2C, ...] in one pass; g_mse / g_vb: the two scalars' upstream gradients as device scalars (None = 1)"""
+    B, n = xt.shape[0], xt.numel()
+    assert pred.numel() == 2 * n and eps.numel() == n and x0.numel() == n
+    out = torch.empty_like(pred) if out is None else out
+    _call("dl_vlb_loss_bwd", _p(pred), _p(eps), _p(x0), _p(xt), _p(t), _p(tables), tables.shape[1], mean_type, var_mode,
+          _p(g_mse), _p(g_vb), _p(out), B, n // B, _s())
+    return out
+
+
 def flow_x_to_v(z: Tensor, xhat: Tensor, t: Tensor) -> Tensor:
     v = torch.empty_like(z)
     B = z.shape[0]
@@ -204,12 +228,29 @@ def ddpm_step(pred, pred_uncond, guidance, xt, noise, t, tables, mean_type: int,
     return xp, x0, mean, std, lp
 
 
-def ddim_step(pred, pred_uncond, guidance, xt, noise, t, tables, coefs, mean_type: int, clamp_x: bool, eta: float):
+def ddpm_step_lv(pred, pred_uncond, guidance, xt, noise, t, tables, mean_type: int, var_mode: int, clamp_x: bool, out=None):
+    """learned variances: pred / pred_uncond are [B, 2C, ...], read in place; tables f32 [6, T] with rows 4, 5 =
+    posterior_log_variance_clipped, betas; out: the five [B, C, ...] outputs, allocated here when None"""
     B = xt.shape[0]
-    xp, x0, mean = (torch.empty_like(xt) for _ in range(3))
-    std = torch.empty_like(xt) if eta > 0 else None
-    lp = torch.empty_like(xt) if eta > 0 else None
-    _call("dl_ddim_step", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables),
+    assert pred.numel() == 2 * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    xp, x0, mean, std, lp = (torch.empty_like(xt) for _ in range(5)) if out is None else out
+    _call("dl_ddpm_step_lv", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables),
+          tables.shape[1], mean_type, var_mode, int(clamp_x), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
+    return xp, x0, mean, std, lp
+
+
+def ddim_step(pred, pred_uncond, guidance, xt, noise, t, tables, coefs, mean_type: int, clamp_x: bool, eta: float,
+              halves: bool = False, out=None):
+    """halves: pred / pred_uncond are the [B, 2C, ...] prediction of a learned-variance model; its mean half is read in place"""
+    B = xt.shape[0]
+    assert pred.numel() == (2 if halves else 1) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    if out is not None:
+        xp, x0, mean, std, lp = out
+    else:
+        xp, x0, mean = (torch.empty_like(xt) for _ in range(3))
+        std = torch.empty_like(xt) if eta > 0 else None
+        lp = torch.empty_like(xt) if eta > 0 else None
+    _call("dl_ddim_step_lv" if halves else "dl_ddim_step", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables),
           tables.shape[1], mean_type, _p(coefs), int(clamp_x), float(eta), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B,
           xt.numel() // B, _s())
     return xp, x0, mean, std, lp

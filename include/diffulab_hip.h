@@ -34,6 +34,7 @@ enum { DL_BF16 = 0, DL_F32 = 1 };
 enum { DL_ACT_NONE = 0, DL_ACT_SILU = 1, DL_ACT_GELU = 2 };  /* GELU: exact erf form (nn.GELU default) */
 enum { DL_LOSS_FLOW = 0, DL_LOSS_EPS = 1 };                       /* target = a - b | target = a */
 enum { DL_MEAN_EPSILON = 0, DL_MEAN_XSTART = 1, DL_MEAN_XPREV = 2 };
+enum { DL_VAR_LEARNED = 0, DL_VAR_LEARNED_RANGE = 1 };            /* lv = v | lv = w log beta_t + (1 - w) log post_var_t, w = (v + 1) / 2 */
 enum { DL_PATCH_CPP = 0, DL_PATCH_PPC = 1 };                      /* feature order (c p1 p2) | (p1 p2 c) */
 
 /* ------------------------------------------------------------------ library */
@@ -75,6 +76,27 @@ DL_API int dl_mse_loss_fwd(const float* pred, const float* a, const float* b, fl
  * optional DEVICE scalar, so autograd's incoming gradient never forces a device->host sync) */
 DL_API int dl_mse_loss_bwd(const float* pred, const float* a, const float* b, float gscale,
                            const float* gscale_dev, float* dpred, int64_t n, int mode, dl_stream_t stream);
+/* Hybrid loss of a learned-variance model.  The reference leaves it as a TODO (gaussian_diffusion.py:267, "Need to add compute loss
+ * for different parameterization + variance learned"); this is L_hybrid = L_simple + lambda L_vlb of Nichol & Dhariwal, "Improved
+ * Denoising Diffusion Probabilistic Models" (2021), eq. 16, with L_vlb's terms as in eq. 4-7 and the mean frozen inside them.
+ * pred [B, 2 chw] is read in place (mean half o, raw variance half v, the chunk of ddpm.py:272); eps, x0, xt [B, chw]; tables f32
+ * [6][T] as for dl_ddpm_step_lv.  Per element: m_p = coef1 x0_pred(o) + coef2 xt (mean_type, no clamp), lv_p from v by var_mode,
+ * m_q = coef1 x0 + coef2 xt, lv_q = posterior_log_variance_clipped[t];
+ *   t > 0:  term = 0.5 (-1 + lv_p - lv_q + exp(lv_q - lv_p) + (m_q - m_p)^2 exp(-lv_p))
+ *   t == 0: term = -log max(prob, 1e-12), prob the mass a Gaussian (m_p, exp(lv_p / 2)) puts on x0's bin of width 2/255 (open at
+ *           x0 < -0.999 / x0 > 0.999), with the tanh approximation of the normal CDF.
+ * loss[0] = mean (eps - o)^2 (DL_LOSS_EPS on the mean half), loss[1] = mean term / ln 2 (bits per dimension).
+ * `partial` is caller scratch of 2 * dl_mse_loss_partials(batch * chw) floats; reduction order is fixed, no float atomics. */
+DL_API int dl_vlb_loss_fwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                           const float* tables, int32_t T, int mean_type, int var_mode, float* partial, float* loss,
+                           int64_t batch, int64_t chw, dl_stream_t stream);
+/* dpred [B, 2 chw] in one pass: mean half = (*g_mse_dev) 2 (o - eps) / n (dl_mse_loss_bwd's values bit for bit), variance half =
+ * (*g_vb_dev) / (n ln 2) * d term / d lv_p * d lv_p / d v, with d lv_p / d v = 1 (learned) or 0.5 (log beta_t - lv_q) (learned_range)
+ * and zero where the 1e-12 clamp is active.  The bound sends nothing into the mean half (stop-gradient on m_p).  The upstream
+ * gradients of the two scalars are DEVICE scalars (NULL = 1), n = batch * chw. */
+DL_API int dl_vlb_loss_bwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                           const float* tables, int32_t T, int mean_type, int var_mode, const float* g_mse_dev,
+                           const float* g_vb_dev, float* dpred, int64_t batch, int64_t chw, dl_stream_t stream);
 /* Flow.compute_loss x-prediction branch flow.py:300-303: v = (z - xhat) / t[b] ; backward dxhat = -dv / t[b] */
 DL_API int dl_flow_x_to_v(const float* z, const float* xhat, const float* t, float* v, int64_t batch,
                           int64_t chw, dl_stream_t stream);
@@ -99,12 +121,27 @@ DL_API int dl_ddpm_step(const float* pred, const float* pred_uncond, float guida
                         const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
                         int clamp_x, float* x_prev, float* x0_est, float* mean, float* std, float* logprob,
                         int64_t batch, int64_t chw, dl_stream_t stream);
+/* DDPM.step with learned variances, ddpm.py:212-222 (get_variance) and 268-282 (the chunk of the 2C prediction), then :330-363 as
+ * above.  pred / pred_uncond are [B, 2 chw] and are read in place: mean output of element (b, r) at b 2chw + r, raw variance output
+ * v at b 2chw + chw + r; the CFG combine (gaussian_diffusion.py:253-255) acts on both.  tables: f32 [6][T] = sqrt_ab, ab,
+ * posterior_mean_coef1, coef2, posterior_log_variance_clipped, betas.  DL_VAR_LEARNED: lv = v; DL_VAR_LEARNED_RANGE:
+ * w = (v + 1) / 2, lv = w logf(betas[t]) + (1 - w) posterior_log_variance_clipped[t]; var = expf(lv). */
+DL_API int dl_ddpm_step_lv(const float* pred, const float* pred_uncond, float guidance, const float* xt,
+                           const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
+                           int var_mode, int clamp_x, float* x_prev, float* x0_est, float* mean, float* std,
+                           float* logprob, int64_t batch, int64_t chw, dl_stream_t stream);
 /* DDIM.step ddim.py:68-103.  tables: f32 [3][T] = sqrt_ab, ab, ab_prev.  std/logprob may be NULL (eta == 0). */
 DL_API int dl_ddim_step(const float* pred, const float* pred_uncond, float guidance, const float* xt,
                         const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
                         const float* ddpm_coefs /* f32 [2][T] coef1, coef2; only for DL_MEAN_XPREV */,
                         int clamp_x, float eta, float* x_prev, float* x0_est, float* mean, float* std,
                         float* logprob, int64_t batch, int64_t chw, dl_stream_t stream);
+/* the same step on the [B, 2 chw] prediction of a learned-variance model: DDIM inherits the chunk (ddpm.py:268-272) and discards the
+ * variance half (ddim.py:89), so only the mean half is read, in place */
+DL_API int dl_ddim_step_lv(const float* pred, const float* pred_uncond, float guidance, const float* xt,
+                           const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
+                           const float* ddpm_coefs, int clamp_x, float eta, float* x_prev, float* x0_est, float* mean,
+                           float* std, float* logprob, int64_t batch, int64_t chw, dl_stream_t stream);
 
 /* ------------------------------------------------------------------ GEMMs (bf16 in, f32 MFMA accumulate) */
 /* nn.Linear forward / dgrad (mmdit.py:81,102,260-264; nn.py:530; mmdit.py:542-548):

@@ -305,6 +305,7 @@ __device__ __forceinline__ float x_start_from(int mean_type, float out, float xt
                                               float c2) {
   if (mean_type == DL_MEAN_XSTART) return out;
   if (mean_type == DL_MEAN_EPSILON) return (1.0f / sab) * xt - (sqrtf(1.0f - ab) / sab) * out;  // ddpm.py:118-121
+  if (mean_type == DL_MEAN_V) return sab * xt - sqrtf(1.0f - ab) * out;  // Salimans & Ho (2022): v = sab eps - sqrt(1 - ab) x0
   return (1.0f / c1) * out - (c2 / c1) * xt;                                                    // ddpm.py:99-102
 }
 
@@ -457,6 +458,7 @@ extern "C" int dl_ddim_step(const float* pred, const float* pred_uncond, float g
                             float* mean, float* std, float* logprob, int64_t batch, int64_t chw,
                             dl_stream_t stream) {
   DL_CHECK_ARG(pred && xt && noise && t && tables && x_prev && batch > 0 && chw > 0 && T > 0, "dl_ddim_step: bad args");
+  DL_CHECK_ARG(mean_type >= 0 && mean_type <= 2, "dl_ddim_step: mean_type %d", mean_type);
   DL_CHECK_ARG(mean_type != DL_MEAN_XPREV || ddpm_coefs, "dl_ddim_step: xprev needs ddpm_coefs");
   const int64_t n = batch * chw;
   hipLaunchKernelGGL(ddim_step_k<false>, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t,
@@ -475,6 +477,48 @@ extern "C" int dl_ddim_step_lv(const float* pred, const float* pred_uncond, floa
   const int64_t n = batch * chw;
   hipLaunchKernelGGL(ddim_step_k<true>, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t,
                      tables, T, mean_type, ddpm_coefs, clamp_x, eta, x_prev, x0_est, mean, std, logprob, n, chw);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// v-prediction (Salimans & Ho 2022) through the same kernel bodies: x_start_from's DL_MEAN_V case.  One entry point per sampler takes
+// the [B, chw] prediction of a fixed-variance model (DL_VAR_FIXED: tables as for dl_ddpm_step / dl_ddim_step) and the [B, 2 chw] one
+// of a learned-variance model (tables as for the _lv entry points).
+static int step_v_check(const char* who, const void* pred, const void* xt, const void* noise, const void* t, const void* tables,
+                        const void* x_prev, int32_t T, int var_mode, int64_t batch, int64_t chw) {
+  DL_CHECK_ARG(pred && xt && noise && t && tables && x_prev && batch > 0 && chw > 0 && T > 0, "%s: bad args", who);
+  DL_CHECK_ARG(var_mode == DL_VAR_FIXED || var_mode == DL_VAR_LEARNED || var_mode == DL_VAR_LEARNED_RANGE, "%s: var_mode %d", who,
+               var_mode);
+  return DL_OK;
+}
+extern "C" int dl_ddpm_step_v(const float* pred, const float* pred_uncond, float guidance, const float* xt, const float* noise,
+                              const int32_t* t, const float* tables, int32_t T, int var_mode, int clamp_x, float* x_prev,
+                              float* x0_est, float* mean, float* std, float* logprob, int64_t batch, int64_t chw,
+                              dl_stream_t stream) {
+  if (int rc = step_v_check("dl_ddpm_step_v", pred, xt, noise, t, tables, x_prev, T, var_mode, batch, chw)) return rc;
+  const int64_t n = batch * chw;
+  if (var_mode == DL_VAR_FIXED)
+    hipLaunchKernelGGL(ddpm_step_k, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t, tables, T,
+                       DL_MEAN_V, clamp_x, x_prev, x0_est, mean, std, logprob, n, chw);
+  else
+    hipLaunchKernelGGL(ddpm_step_lv_k, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t, tables,
+                       T, DL_MEAN_V, var_mode, clamp_x, x_prev, x0_est, mean, std, logprob, n, chw);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_ddim_step_v(const float* pred, const float* pred_uncond, float guidance, const float* xt, const float* noise,
+                              const int32_t* t, const float* tables, int32_t T, int var_mode, int clamp_x, float eta,
+                              float* x_prev, float* x0_est, float* mean, float* std, float* logprob, int64_t batch, int64_t chw,
+                              dl_stream_t stream) {
+  if (int rc = step_v_check("dl_ddim_step_v", pred, xt, noise, t, tables, x_prev, T, var_mode, batch, chw)) return rc;
+  const int64_t n = batch * chw;
+  const float* no_coefs = nullptr;  // the posterior-mean coefficients serve DL_MEAN_XPREV only
+  if (var_mode == DL_VAR_FIXED)
+    hipLaunchKernelGGL(ddim_step_k<false>, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t,
+                       tables, T, DL_MEAN_V, no_coefs, clamp_x, eta, x_prev, x0_est, mean, std, logprob, n, chw);
+  else
+    hipLaunchKernelGGL(ddim_step_k<true>, ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, noise, t,
+                       tables, T, DL_MEAN_V, no_coefs, clamp_x, eta, x_prev, x0_est, mean, std, logprob, n, chw);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
@@ -605,6 +649,165 @@ extern "C" int dl_vlb_loss_bwd(const float* pred, const float* eps, const float*
   const int64_t n = batch * chw;
   hipLaunchKernelGGL(vlb_bwd_k, ew_grid(n), 256, 0, (hipStream_t)stream, pred, eps, x0, xt, t, tables, T, mean_type, var_mode,
                      (float)(2.0 / (double)n), (float)(1.0 / ((double)n * 0.6931471805599453)), g_mse_dev, g_vb_dev, dpred, n, chw);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// ---------------------------------------------------------------- loss head of every parameterisation
+// dl_mse_loss_* (mode EPS) and dl_vlb_loss_* generalised: the regression target of the mean output is formed per element from eps,
+// x0, xt (never written to memory), the squared error may carry a per-timestep weight, and the prediction is [B, chw] (LV false) or
+// [B, 2 chw] with the variational bound on its variance half (LV true).  Only what the mode needs is loaded: the epsilon target
+// with fixed variances and no weight reads pred and eps alone, as mse_partial_k does.
+// Both are rounded in one defined way (no contraction): the posterior mean as ddpm_step_k rounds its `mean` output, fma(c2, xt, c1 x0),
+// and v as two products and a difference, which is also how an f32 host evaluation rounds it.
+__device__ __forceinline__ float gd_target(int target, float e, float x0, float x, float sab, float ab, float c1, float c2) {
+#pragma clang fp contract(off)
+  if (target == DL_MEAN_EPSILON) return e;
+  if (target == DL_MEAN_XSTART) return x0;
+  if (target == DL_MEAN_XPREV) return __builtin_fmaf(c2, x, c1 * x0);  // ddpm.py:156-174, the posterior mean of (x0, xt)
+  return sab * e - sqrtf(1.0f - ab) * x0;  // v; sqrtf(1 - ab) as ddpm_add_noise_k and x_start_from evaluate it
+}
+__device__ __forceinline__ float gd_sub(float a, float b) {  // a - b, never fused into the arithmetic that formed a
+#pragma clang fp contract(off)
+  return a - b;
+}
+struct gd_elem {
+  int32_t ti;
+  int64_t pi;
+  float o, tgt, x0, x, sab, ab, c1, c2;
+};
+template <bool LV, bool W>
+__device__ __forceinline__ gd_elem gd_load(int64_t i, const float* __restrict__ pred, const float* __restrict__ eps,
+                                           const float* __restrict__ x0, const float* __restrict__ xt,
+                                           const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T, int target,
+                                           int64_t chw) {
+  gd_elem g;
+  const bool rows = LV || target >= DL_MEAN_XPREV;
+  g.ti = 0;
+  g.pi = i;
+  if (rows || W) {
+    const int64_t b = i / chw;
+    g.ti = t[b];
+    if (LV) g.pi = i + b * chw;
+  }
+  g.o = pred[g.pi];
+  const float e = (target == DL_MEAN_EPSILON || target == DL_MEAN_V) ? eps[i] : 0.0f;
+  g.x0 = (LV || target != DL_MEAN_EPSILON) ? x0[i] : 0.0f;
+  g.x = (LV || target == DL_MEAN_XPREV) ? xt[i] : 0.0f;
+  g.sab = g.ab = g.c1 = g.c2 = 0.0f;
+  if (rows) g.sab = tab[g.ti], g.ab = tab[T + g.ti], g.c1 = tab[2 * T + g.ti], g.c2 = tab[3 * T + g.ti];
+  g.tgt = gd_target(target, e, g.x0, g.x, g.sab, g.ab, g.c1, g.c2);
+  return g;
+}
+// partial[blk] = sum w (target - o)^2 and, LV, partial[np + blk] = sum of the bound terms, in the element-to-thread order of
+// mse_partial_k / vlb_partial_k.  W false is w == 1: the sum is then accumulated as those kernels accumulate it (acc += d * d), so
+// that the epsilon target reproduces their scalars bit for bit.
+template <bool LV, bool W>
+__global__ void gd_partial_k(const float* __restrict__ pred, const float* __restrict__ eps, const float* __restrict__ x0,
+                             const float* __restrict__ xt, const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T,
+                             int target, const float* __restrict__ weight, int var_mode, float* __restrict__ partial, int64_t np,
+                             int64_t n, int64_t chw) {
+  __shared__ float red[2][MSE_BLOCK / DL_WAVE];
+  const int64_t base = (int64_t)blockIdx.x * MSE_ELEMS_PER_BLOCK;
+  float acc = 0.f, vacc = 0.f;
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int64_t i = base + (int64_t)j * MSE_BLOCK + threadIdx.x;
+    if (i < n) {
+      const gd_elem g = gd_load<LV, W>(i, pred, eps, x0, xt, t, tab, T, target, chw);
+      const float d = gd_sub(g.tgt, g.o);
+      if (W)
+        acc += weight[g.ti] * (d * d);
+      else
+        acc += d * d;
+      if (LV)
+        vacc += vlb_elem<false>(target, var_mode, g.ti, g.o, pred[g.pi + chw], g.x0, g.x, g.sab, g.ab, g.c1, g.c2, tab[4 * T + g.ti],
+                                tab[5 * T + g.ti], nullptr);
+    }
+  }
+  acc = wave_sum(acc);
+  if (LV) vacc = wave_sum(vacc);
+  if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = acc, red[1][threadIdx.x >> 6] = vacc;
+  __syncthreads();
+  if (threadIdx.x < (LV ? 2 : 1)) {
+    float s = 0.f;
+    for (int w = 0; w < MSE_BLOCK / DL_WAVE; ++w) s += red[threadIdx.x][w];
+    partial[threadIdx.x * np + blockIdx.x] = s;
+  }
+}
+template <bool LV, bool W>
+__global__ void gd_bwd_k(const float* __restrict__ pred, const float* __restrict__ eps, const float* __restrict__ x0,
+                         const float* __restrict__ xt, const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T,
+                         int target, const float* __restrict__ weight, int var_mode, float coef_m, float coef_v,
+                         const float* __restrict__ g_mse, const float* __restrict__ g_vb, float* __restrict__ dpred, int64_t n,
+                         int64_t chw) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (g_mse) coef_m *= *g_mse;  // as mse_bwd_k / vlb_bwd_k form their coefficient
+  if (LV && g_vb) coef_v *= *g_vb;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const gd_elem g = gd_load<LV, W>(i, pred, eps, x0, xt, t, tab, T, target, chw);
+    const float cm = W ? coef_m * weight[g.ti] : coef_m;
+    dpred[g.pi] = cm * gd_sub(g.o, g.tgt);
+    if (LV) {
+      float dv;
+      vlb_elem<true>(target, var_mode, g.ti, g.o, pred[g.pi + chw], g.x0, g.x, g.sab, g.ab, g.c1, g.c2, tab[4 * T + g.ti],
+                     tab[5 * T + g.ti], &dv);
+      dpred[g.pi + chw] = coef_v * dv;
+    }
+  }
+}
+static int gd_check(const char* who, const void* pred, const void* eps, const void* x0, const void* xt, const void* t,
+                    const void* tables, int32_t T, int target, int var_mode, int64_t batch, int64_t chw) {
+  DL_CHECK_ARG(pred && t && tables && batch > 0 && chw > 0 && T > 0, "%s: bad args", who);
+  DL_CHECK_ARG(target >= DL_MEAN_EPSILON && target <= DL_MEAN_V, "%s: target %d", who, target);
+  DL_CHECK_ARG(var_mode == DL_VAR_FIXED || var_mode == DL_VAR_LEARNED || var_mode == DL_VAR_LEARNED_RANGE, "%s: var_mode %d", who,
+               var_mode);
+  const bool lv = var_mode != DL_VAR_FIXED;
+  DL_CHECK_ARG(eps || target == DL_MEAN_XSTART || target == DL_MEAN_XPREV, "%s: target %d needs eps", who, target);
+  DL_CHECK_ARG(x0 || (!lv && target == DL_MEAN_EPSILON), "%s: target %d, var_mode %d need x0", who, target, var_mode);
+  DL_CHECK_ARG(xt || (!lv && target != DL_MEAN_XPREV), "%s: target %d, var_mode %d need xt", who, target, var_mode);
+  return DL_OK;
+}
+extern "C" int dl_gd_loss_fwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                              const float* tables, int32_t T, int target, const float* weight, int var_mode, float* partial,
+                              float* loss, int64_t batch, int64_t chw, dl_stream_t stream) {
+  if (int rc = gd_check("dl_gd_loss_fwd", pred, eps, x0, xt, t, tables, T, target, var_mode, batch, chw)) return rc;
+  DL_CHECK_ARG(partial && loss, "dl_gd_loss_fwd: bad args (partial, loss)");
+  const int64_t n = batch * chw, np = dl_mse_loss_partials(n);
+  const bool lv = var_mode != DL_VAR_FIXED;
+#define GD_FWD(LV, W)                                                                                                            \
+  hipLaunchKernelGGL((gd_partial_k<LV, W>), (int)np, MSE_BLOCK, 0, (hipStream_t)stream, pred, eps, x0, xt, t, tables, T, target, \
+                     weight, var_mode, partial, np, n, chw)
+  if (lv) {
+    if (weight) GD_FWD(true, true); else GD_FWD(true, false);
+    hipLaunchKernelGGL(vlb_final_k, 1, 256, 0, (hipStream_t)stream, partial, loss, np, (float)(1.0 / (double)n),
+                       (float)(1.0 / ((double)n * 0.6931471805599453)));
+  } else {
+    if (weight) GD_FWD(false, true); else GD_FWD(false, false);
+    hipLaunchKernelGGL(mse_final_k, 1, 256, 0, (hipStream_t)stream, partial, loss, np, (float)(1.0 / (double)n));
+  }
+#undef GD_FWD
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_gd_loss_bwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                              const float* tables, int32_t T, int target, const float* weight, int var_mode,
+                              const float* g_mse_dev, const float* g_vb_dev, float* dpred, int64_t batch, int64_t chw,
+                              dl_stream_t stream) {
+  if (int rc = gd_check("dl_gd_loss_bwd", pred, eps, x0, xt, t, tables, T, target, var_mode, batch, chw)) return rc;
+  DL_CHECK_ARG(dpred, "dl_gd_loss_bwd: bad args (dpred)");
+  const int64_t n = batch * chw;
+  const bool lv = var_mode != DL_VAR_FIXED;
+  const float coef_m = (float)(2.0 / (double)n), coef_v = (float)(1.0 / ((double)n * 0.6931471805599453));
+#define GD_BWD(LV, W)                                                                                                              \
+  hipLaunchKernelGGL((gd_bwd_k<LV, W>), ew_grid(n), 256, 0, (hipStream_t)stream, pred, eps, x0, xt, t, tables, T, target, weight, \
+                     var_mode, coef_m, coef_v, g_mse_dev, g_vb_dev, dpred, n, chw)
+  if (lv) {
+    if (weight) GD_BWD(true, true); else GD_BWD(true, false);
+  } else {
+    if (weight) GD_BWD(false, true); else GD_BWD(false, false);
+  }
+#undef GD_BWD
   DL_LAUNCH_CHECK();
   return DL_OK;
 }

@@ -69,6 +69,41 @@ def hybrid_head(pred: Tensor, eps: Tensor, x0: Tensor, xt: Tensor, t: Tensor, ta
     return both[0], both[1]
 
 
+class _GDHead(torch.autograd.Function):
+    """the loss of any parameterisation of the mean output -- dl_gd_loss_fwd / _bwd.  The regression target (epsilon, x0, the posterior
+    mean or v) is formed inside the kernels from eps, x0, xt; `weight` is a per-timestep table or None.  Fixed variances: one scalar,
+    the weighted mse.  Learned variances: (weighted mse of the mean half, variational bound in bits per dimension), the bound as
+    `_HybridHead` has it, with the predicted mean derived from the same parameterisation and frozen."""
+
+    @staticmethod
+    def forward(ctx, pred: Tensor, eps, x0, xt, t: Tensor, tables: Tensor, weight, target: int, var_mode: int):
+        pred = pred.float().contiguous()
+        ctx.save_for_backward(pred, eps, x0, xt, t, tables, weight)
+        ctx.modes = (target, var_mode)
+        out = ops.gd_loss_fwd(pred, eps, x0, xt, t, tables, target, weight, var_mode)
+        return out if var_mode == ops.VAR_FIXED else (out[0], out[1])
+
+    @staticmethod
+    def backward(ctx, g_mse: Tensor, g_vb: Tensor | None = None):
+        # the upstream gradients stay on the device (an unused output arrives as zeros); one kernel writes the whole dpred
+        pred, eps, x0, xt, t, tables, weight = ctx.saved_tensors
+        target, var_mode = ctx.modes
+        dpred = ops.gd_loss_bwd(pred, eps, x0, xt, t, tables, target, weight, var_mode, g_mse.float().contiguous(),
+                                None if g_vb is None else g_vb.float().contiguous())
+        return dpred, None, None, None, None, None, None, None, None
+
+
+def gd_head(pred: Tensor, eps: Tensor | None, x0: Tensor | None, xt: Tensor | None, t: Tensor, tables: Tensor, target: int,
+            weight: Tensor | None = None, var_mode: int = ops.VAR_FIXED):
+    """-> the scalar loss (var_mode VAR_FIXED) or (mse, vb) (learned variances); eps / x0 / xt may be None where the mode does not
+    read them (the epsilon target with fixed variances reads eps only)"""
+    eps, x0, xt = (None if v is None else v.float().contiguous() for v in (eps, x0, xt))
+    if pred.requires_grad:
+        return _GDHead.apply(pred, eps, x0, xt, t, tables, weight, target, var_mode)
+    out = ops.gd_loss_fwd(pred.float().contiguous(), eps, x0, xt, t, tables, target, weight, var_mode)
+    return out if var_mode == ops.VAR_FIXED else (out[0], out[1])
+
+
 class Diffusion(ABC):
     sampler_registry: dict[str, type[Sampler]]
 

@@ -17,7 +17,7 @@ from ... import ops
 from ..samplers.common import StepResult
 from ..samplers.gaussian_diffusion import DDIM, DDPM
 from ..utils import SamplingOutput, f32_table, to_device
-from .diffusion import Diffusion, hybrid_head, mse_head
+from .diffusion import Diffusion, gd_head, hybrid_head, mse_head
 from .utils import space_timesteps
 
 try:
@@ -27,13 +27,55 @@ except ImportError:  # pragma: no cover
         return it
 
 
+LOSS_TARGETS = ("epsilon", "mean_type")
+LOSS_WEIGHTINGS = (None, "min_snr")
+
+
+def min_snr_weights(alphas_bar: Tensor, target: str, gamma: float = 5.0) -> Tensor:
+    """Min-SNR-gamma loss weights (Hang et al., "Efficient Diffusion Training via Min-SNR Weighting Strategy", 2023) of one chain,
+    fp64 [T]: with snr_t = ab_t / (1 - ab_t), the weight min(snr, gamma) of the x0 loss expressed for the target that is regressed."""
+    ab = alphas_bar.double()
+    snr = ab / (1.0 - ab)
+    clipped = snr.clamp(max=gamma)
+    if target == "epsilon":
+        return clipped / snr
+    if target == "xstart":
+        return clipped
+    if target == "v":
+        return clipped / (snr + 1.0)
+    raise ValueError(f"loss_weighting='min_snr' is defined for the targets epsilon, xstart and v, not for {target!r}")
+
+
 class GaussianDiffusion(Diffusion):
     sampler_registry = {"ddpm": DDPM, "ddim": DDIM}
 
     def __init__(self, n_steps: int = 1000, sampling_method: str = "ddpm", schedule: str = "linear",
-                 latent_diffusion: bool = False, sampler_parameters: dict[str, Any] = {}, vlb_weight: float | None = None) -> None:
+                 latent_diffusion: bool = False, sampler_parameters: dict[str, Any] = {}, vlb_weight: float | None = None,
+                 loss_target: str = "epsilon", loss_weighting: str | None = None, min_snr_gamma: float = 5.0) -> None:
         if sampling_method not in ["ddpm", "ddim"]:
             raise ValueError("sampling method must be one of ['ddpm', 'ddim']")
+        if loss_target not in LOSS_TARGETS:
+            raise ValueError(f"loss_target must be one of {list(LOSS_TARGETS)}")
+        if loss_weighting not in LOSS_WEIGHTINGS:
+            raise ValueError(f"loss_weighting must be one of {list(LOSS_WEIGHTINGS)}")
+        # what compute_loss regresses the mean output on: the noise (the reference's loss, whatever the sampler's mean_type), or the
+        # parameterisation the sampler reads the output as
+        mean_type = sampler_parameters.get("mean_type", "epsilon")
+        if loss_target == "epsilon" and mean_type == "v":
+            raise ValueError('a sampler with mean_type="v" takes loss_target="mean_type": loss_target="epsilon" would train a noise '
+                             "predictor and sample it as a v predictor")
+        self.loss_target, self.loss_weighting, self.min_snr_gamma = loss_target, loss_weighting, float(min_snr_gamma)
+        self._target = mean_type if loss_target == "mean_type" else "epsilon"
+        if (loss_weighting is not None and loss_target == "epsilon" and mean_type != "epsilon"
+                and sampler_parameters.get("var_type", "fixed_small") in ops.VAR_MODES):
+            # the weighted head derives the bound's frozen mean from the regression target; the unweighted default derives it from
+            # mean_type.  A weight documented to touch "loss" alone must not move "vb", so the mixed form is not offered.
+            raise ValueError(f'loss_weighting with learned variances and mean_type={mean_type!r} takes loss_target="mean_type": with '
+                             'loss_target="epsilon" the variational bound would read the output as epsilon')
+        if loss_weighting == "min_snr" and self._target == "xprev":
+            raise ValueError('loss_weighting="min_snr" is defined for the targets epsilon, xstart and v, not for xprev')
+        self.loss_weight: Tensor | None = None  # fp64 [T], rebuilt with the chain
+        self._dev_weight: dict[torch.device, Tensor] = {}
         self.training_steps = n_steps
         # weight of the variational-bound term of a learned-variance model's loss: Improved DDPM rescales it by T / 1000
         self.vlb_weight = n_steps / 1000 if vlb_weight is None else float(vlb_weight)
@@ -47,6 +89,9 @@ class GaussianDiffusion(Diffusion):
         self.alphas_bar = self.alphas.cumprod(dim=0)
         self.sqrt_alphas_bar = self.alphas_bar.sqrt()
         self._dev.clear()
+        self._dev_weight.clear()
+        if self.loss_weighting == "min_snr":  # a respaced chain has its own alphas_bar
+            self.loss_weight = min_snr_weights(self.alphas_bar, self._target, self.min_snr_gamma)
         self.sampler.set_steps(betas)
 
     def set_steps(self, n_steps: int, schedule: str = "linear", section_counts: int | str | None = None) -> None:
@@ -110,6 +155,8 @@ class GaussianDiffusion(Diffusion):
 
     def compute_loss(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None = None, extra_losses=[],
                      extra_args: dict[str, Any] = {}) -> dict[str, Tensor]:
+        if self._target != "epsilon" or self.loss_weight is not None:
+            return self._compute_loss_gd(model, model_inputs, timesteps, noise, extra_losses, extra_args)
         if self.sampler.learned_variance:
             return self._compute_loss_learned_variance(model, model_inputs, timesteps, noise, extra_losses, extra_args)
         model_inputs["x"], noise = self.add_noise(model_inputs["x"], timesteps, noise)
@@ -132,6 +179,35 @@ class GaussianDiffusion(Diffusion):
         mse, vb = hybrid_head(prediction, noise, x0, xt, to_device(timesteps, xt.device, torch.int32), self.sampler._tables(xt.device),
                               ops.MEAN_TYPES[self.sampler.mean_type], ops.VAR_MODES[self.sampler.var_type])
         loss_dict = {"loss": mse, "vb": self.vlb_weight * vb}
+        for extra_loss in extra_losses:
+            loss_dict[extra_loss.name] = extra_loss(**extra_args)
+        return loss_dict
+
+    def _weight(self, device: torch.device) -> Tensor | None:
+        if self.loss_weight is None:
+            return None
+        if device not in self._dev_weight:
+            self._dev_weight[device] = f32_table(self.loss_weight, device)
+        return self._dev_weight[device]
+
+    def _compute_loss_gd(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None, extra_losses,
+                         extra_args: dict[str, Any]) -> dict[str, Tensor]:
+        """the loss of the parameterisation the sampler reads (loss_target="mean_type": x0, the posterior mean or v as the regression
+        target, formed inside the kernel) and / or a per-timestep weight on it.  Same keys as the other two paths: "loss", and "vb" for
+        a learned-variance model, whose bound derives its frozen mean from the same parameterisation and carries no weight.  (The
+        constructor refuses the one form in which that parameterisation would differ from the sampler's mean_type.)"""
+        x0 = model_inputs["x"].float().contiguous()
+        model_inputs["x"], noise = self.add_noise(x0, timesteps, noise)
+        xt = model_inputs["x"]
+        prediction = model(**model_inputs, timesteps=self._remap(timesteps))["x"]
+        t = to_device(timesteps, xt.device, torch.int32)
+        args = (t, self.sampler._tables(xt.device), ops.MEAN_TYPES[self._target], self._weight(xt.device))
+        if self.sampler.learned_variance:
+            self.sampler._check_halves(prediction, xt)
+            mse, vb = gd_head(prediction, noise, x0, xt, *args, ops.VAR_MODES[self.sampler.var_type])
+            loss_dict = {"loss": mse, "vb": self.vlb_weight * vb}
+        else:
+            loss_dict = {"loss": gd_head(prediction, noise, x0, xt, *args, ops.VAR_FIXED)}
         for extra_loss in extra_losses:
             loss_dict[extra_loss.name] = extra_loss(**extra_args)
         return loss_dict

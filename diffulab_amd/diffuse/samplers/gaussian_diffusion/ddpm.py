@@ -12,7 +12,7 @@ from .... import ops
 from ...utils import f32_table
 from ..common import Sampler, StepResult
 
-_MEAN = ("epsilon", "xstart", "xprev")
+_MEAN = ("epsilon", "xstart", "xprev", "v")  # "v" (Salimans & Ho 2022) is this project's; the reference has the first three
 _VAR = ("learned", "fixed_small", "fixed_large", "learned_range")
 
 
@@ -76,6 +76,14 @@ class DDPM(GaussianSampler):
     def step(self, model_prediction: Tensor, timesteps: Tensor, xt: Tensor, clamp_x: bool = False,
              prediction_uncond: Tensor | None = None, guidance_scale: float = 0.0) -> StepResult:
         noise = torch.randn_like(xt)  # ddpm.py:302 (drawn for every t, masked at t == 0)
+        if self.mean_type == "v":  # one entry point for [B, C] and [B, 2C] predictions; `_tables` follows var_type
+            if self.learned_variance:
+                self._check_halves(model_prediction, xt)
+            xp, x0, mean, std, lp = ops.ddpm_step_v(
+                model_prediction.float().contiguous(), None if prediction_uncond is None else prediction_uncond.float().contiguous(),
+                guidance_scale, xt.float().contiguous(), noise, timesteps.to(torch.int32).contiguous(), self._tables(xt.device),
+                ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED), clamp_x)
+            return StepResult(x_prev=xp, estimated_x0=x0, x_prev_mean=mean, x_prev_std=std, logprob=lp)
         if self.learned_variance:  # `_tables` rows 4, 5 are then (posterior_log_variance_clipped, betas)
             self._check_halves(model_prediction, xt)
             xp, x0, mean, std, lp = ops.ddpm_step_lv(

@@ -20,8 +20,9 @@ from . import tuning
 BF16, F32 = 0, 1
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 LOSS_FLOW, LOSS_EPS = 0, 1
-MEAN_TYPES = {"epsilon": 0, "xstart": 1, "xprev": 2}
+MEAN_TYPES = {"epsilon": 0, "xstart": 1, "xprev": 2, "v": 3}  # "v": the gd_loss_* / *_step_v entry points only
 VAR_MODES = {"learned": 0, "learned_range": 1}
+VAR_FIXED = -1
 PATCH_CPP, PATCH_PPC = 0, 1
 
 
@@ -187,6 +188,39 @@ def vlb_loss_bwd(pred: Tensor, eps: Tensor, x0: Tensor, xt: Tensor, t: Tensor, t
     return out
 
 
+def gd_loss_fwd(pred: Tensor, eps: Tensor | None, x0: Tensor | None, xt: Tensor | None, t: Tensor, tables: Tensor, target: int,
+                weight: Tensor | None, var_mode: int, out: Tensor | None = None, partial: Tensor | None = None) -> Tensor:
+    """the loss of any parameterisation (dl_gd_loss_fwd).  var_mode VAR_FIXED: pred [B, C, ...] -> f32 scalar, the weighted mse;
+    a learned var_mode: pred [B, 2C, ...] -> f32 [2] = (weighted mse of the mean half, variational bound in bits / dim).
+    weight: f32 [T] per-timestep weight or None; eps / x0 / xt may be None where the mode does not read them; partial: the scratch
+    of dl_mse_loss_partials(n) floats (twice that for learned variances), allocated here when None."""
+    fixed = var_mode == VAR_FIXED
+    B = pred.shape[0]
+    n = pred.numel() if fixed else pred.numel() // 2
+    assert all(v is None or v.numel() == n for v in (eps, x0, xt)) and (weight is None or weight.numel() == tables.shape[1])
+    npart = lib().call("dl_mse_loss_partials", n)
+    if partial is None:
+        partial = torch.empty(npart if fixed else 2 * npart, device=pred.device, dtype=torch.float32)
+    assert partial.numel() >= (npart if fixed else 2 * npart)
+    if out is None:
+        out = torch.empty(() if fixed else 2, device=pred.device, dtype=torch.float32)
+    _call("dl_gd_loss_fwd", _p(pred), _p(eps), _p(x0), _p(xt), _p(t), _p(tables), tables.shape[1], target, _p(weight), var_mode,
+          _p(partial), _p(out), B, n // B, _s())
+    return out
+
+
+def gd_loss_bwd(pred: Tensor, eps: Tensor | None, x0: Tensor | None, xt: Tensor | None, t: Tensor, tables: Tensor, target: int,
+                weight: Tensor | None, var_mode: int, g_mse: Tensor | None, g_vb: Tensor | None, out: Tensor | None = None) -> Tensor:
+    """dpred (the shape of pred) in one pass; g_mse / g_vb: the scalars' upstream gradients as device scalars (None = 1)"""
+    B = pred.shape[0]
+    n = pred.numel() if var_mode == VAR_FIXED else pred.numel() // 2
+    assert all(v is None or v.numel() == n for v in (eps, x0, xt)) and (weight is None or weight.numel() == tables.shape[1])
+    out = torch.empty_like(pred) if out is None else out
+    _call("dl_gd_loss_bwd", _p(pred), _p(eps), _p(x0), _p(xt), _p(t), _p(tables), tables.shape[1], target, _p(weight), var_mode,
+          _p(g_mse), _p(g_vb), _p(out), B, n // B, _s())
+    return out
+
+
 def flow_x_to_v(z: Tensor, xhat: Tensor, t: Tensor) -> Tensor:
     v = torch.empty_like(z)
     B = z.shape[0]
@@ -253,6 +287,31 @@ def ddim_step(pred, pred_uncond, guidance, xt, noise, t, tables, coefs, mean_typ
     _call("dl_ddim_step_lv" if halves else "dl_ddim_step", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables),
           tables.shape[1], mean_type, _p(coefs), int(clamp_x), float(eta), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B,
           xt.numel() // B, _s())
+    return xp, x0, mean, std, lp
+
+
+def ddpm_step_v(pred, pred_uncond, guidance, xt, noise, t, tables, var_mode: int, clamp_x: bool, out=None):
+    """v-prediction: pred / pred_uncond [B, C, ...] and ddpm_step's tables (VAR_FIXED), or [B, 2C, ...] and ddpm_step_lv's"""
+    B = xt.shape[0]
+    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    xp, x0, mean, std, lp = (torch.empty_like(xt) for _ in range(5)) if out is None else out
+    _call("dl_ddpm_step_v", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables), tables.shape[1],
+          var_mode, int(clamp_x), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
+    return xp, x0, mean, std, lp
+
+
+def ddim_step_v(pred, pred_uncond, guidance, xt, noise, t, tables, var_mode: int, clamp_x: bool, eta: float, out=None):
+    """v-prediction: pred / pred_uncond [B, C, ...] (VAR_FIXED) or [B, 2C, ...], whose mean half is read in place; tables f32 [3, T]"""
+    B = xt.shape[0]
+    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    if out is not None:
+        xp, x0, mean, std, lp = out
+    else:
+        xp, x0, mean = (torch.empty_like(xt) for _ in range(3))
+        std = torch.empty_like(xt) if eta > 0 else None
+        lp = torch.empty_like(xt) if eta > 0 else None
+    _call("dl_ddim_step_v", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables), tables.shape[1],
+          var_mode, int(clamp_x), float(eta), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
     return xp, x0, mean, std, lp
 
 

@@ -33,8 +33,9 @@ enum { DL_OK = 0, DL_ERR_INVALID = -1, DL_ERR_LAUNCH = -2, DL_ERR_UNSUPPORTED = 
 enum { DL_BF16 = 0, DL_F32 = 1 };
 enum { DL_ACT_NONE = 0, DL_ACT_SILU = 1, DL_ACT_GELU = 2 };  /* GELU: exact erf form (nn.GELU default) */
 enum { DL_LOSS_FLOW = 0, DL_LOSS_EPS = 1 };                       /* target = a - b | target = a */
-enum { DL_MEAN_EPSILON = 0, DL_MEAN_XSTART = 1, DL_MEAN_XPREV = 2 };
+enum { DL_MEAN_EPSILON = 0, DL_MEAN_XSTART = 1, DL_MEAN_XPREV = 2, DL_MEAN_V = 3 }; /* V: dl_gd_loss_*, dl_ddpm_step_v, dl_ddim_step_v only */
 enum { DL_VAR_LEARNED = 0, DL_VAR_LEARNED_RANGE = 1 };            /* lv = v | lv = w log beta_t + (1 - w) log post_var_t, w = (v + 1) / 2 */
+enum { DL_VAR_FIXED = -1 };                                       /* [B, chw] prediction, variances from the tables (dl_gd_loss_*, the _v steps) */
 enum { DL_PATCH_CPP = 0, DL_PATCH_PPC = 1 };                      /* feature order (c p1 p2) | (p1 p2 c) */
 
 /* ------------------------------------------------------------------ library */
@@ -97,6 +98,33 @@ DL_API int dl_vlb_loss_fwd(const float* pred, const float* eps, const float* x0,
 DL_API int dl_vlb_loss_bwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
                            const float* tables, int32_t T, int mean_type, int var_mode, const float* g_mse_dev,
                            const float* g_vb_dev, float* dpred, int64_t batch, int64_t chw, dl_stream_t stream);
+/* The loss of every parameterisation the samplers accept, which the reference leaves as the same TODO (gaussian_diffusion.py:267,
+ * "Need to add compute loss for different parameterization + variance learned"): a superset of dl_mse_loss_* (mode DL_LOSS_EPS) and
+ * dl_vlb_loss_*.  pred is [B, chw] (var_mode DL_VAR_FIXED) or [B, 2 chw] read in place as dl_vlb_loss_* reads it; eps, x0, xt
+ * [B, chw]; tables f32 [6][T], the rows of DDPM._tables (sqrt_ab, ab, posterior_mean_coef1, coef2, then variance, log_variance for
+ * fixed variances, which this loss does not read, or posterior_log_variance_clipped, betas for learned ones).  The regression target
+ * of the mean output o is formed per element and never written to memory:
+ *   DL_MEAN_EPSILON  eps                                   DL_MEAN_XPREV  coef1 x0 + coef2 xt   (ddpm.py:156-174)
+ *   DL_MEAN_XSTART   x0                                    DL_MEAN_V      sqrt_ab eps - sqrtf(1 - ab) x0   (Salimans & Ho 2022)
+ * loss[0] = (1 / n) sum_i w[t[b(i)]] (target_i - o_i)^2, n = batch * chw; loss[1], learned variances only, = the variational bound
+ * of dl_vlb_loss_fwd in bits per dimension, unweighted, with m_p = coef1 x0_pred(o) + coef2 xt derived from o by `target` and frozen.
+ * With DL_VAR_FIXED only loss[0] is written.  Loads follow the mode: eps is read for the epsilon and v targets; x0 unless the target
+ * is epsilon with fixed variances; xt for the xprev target and for learned variances; t and the tables for xprev, v, a weight or
+ * learned variances -- a pointer the mode does not read may be NULL.  With target DL_MEAN_EPSILON and weight NULL the results are
+ * those of dl_mse_loss_fwd (DL_VAR_FIXED) / dl_vlb_loss_fwd bit for bit: same element-to-thread order, same two-stage reduction.
+ * `partial` is caller scratch of dl_mse_loss_partials(n) floats (twice that for learned variances); no float atomics. */
+DL_API int dl_gd_loss_fwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                          const float* tables, int32_t T, int target,
+                          const float* weight /* f32 [T], per-timestep loss weight; NULL = 1 */, int var_mode, float* partial,
+                          float* loss, int64_t batch, int64_t chw, dl_stream_t stream);
+/* dpred in one pass: mean output = (*g_mse_dev) 2 w[t[b]] (o - target) / n; variance half (learned variances) as dl_vlb_loss_bwd
+ * writes it, = (*g_vb_dev) / (n ln 2) d term / d v, nothing from the bound into the mean output.  Upstream gradients are DEVICE
+ * scalars (NULL = 1); g_vb_dev is not read with DL_VAR_FIXED. */
+DL_API int dl_gd_loss_bwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                          const float* tables, int32_t T, int target,
+                          const float* weight /* f32 [T], per-timestep loss weight; NULL = 1 */, int var_mode,
+                          const float* g_mse_dev, const float* g_vb_dev, float* dpred, int64_t batch, int64_t chw,
+                          dl_stream_t stream);
 /* Flow.compute_loss x-prediction branch flow.py:300-303: v = (z - xhat) / t[b] ; backward dxhat = -dv / t[b] */
 DL_API int dl_flow_x_to_v(const float* z, const float* xhat, const float* t, float* v, int64_t batch,
                           int64_t chw, dl_stream_t stream);
@@ -130,7 +158,9 @@ DL_API int dl_ddpm_step_lv(const float* pred, const float* pred_uncond, float gu
                            const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
                            int var_mode, int clamp_x, float* x_prev, float* x0_est, float* mean, float* std,
                            float* logprob, int64_t batch, int64_t chw, dl_stream_t stream);
-/* DDIM.step ddim.py:68-103.  tables: f32 [3][T] = sqrt_ab, ab, ab_prev.  std/logprob may be NULL (eta == 0). */
+/* DDIM.step ddim.py:68-103.  tables: f32 [3][T] = sqrt_ab, ab, ab_prev.  std/logprob may be NULL (eta == 0).
+ * mean_type outside DL_MEAN_EPSILON .. DL_MEAN_XPREV is refused, as dl_ddpm_step refuses it (before DL_MEAN_V existed such a value
+ * fell through to the xprev formula; v goes through dl_ddim_step_v). */
 DL_API int dl_ddim_step(const float* pred, const float* pred_uncond, float guidance, const float* xt,
                         const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
                         const float* ddpm_coefs /* f32 [2][T] coef1, coef2; only for DL_MEAN_XPREV */,
@@ -142,6 +172,20 @@ DL_API int dl_ddim_step_lv(const float* pred, const float* pred_uncond, float gu
                            const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
                            const float* ddpm_coefs, int clamp_x, float eta, float* x_prev, float* x0_est, float* mean,
                            float* std, float* logprob, int64_t batch, int64_t chw, dl_stream_t stream);
+/* v-prediction (Salimans & Ho, "Progressive Distillation for Fast Sampling of Diffusion Models", 2022), which the reference's
+ * DDPM.get_x_start (ddpm.py:124-154) does not have: the prediction is v = sqrt_ab eps - sqrtf(1 - ab) x0, so
+ * x0 = sqrt_ab xt - sqrtf(1 - ab) v, and the step goes on as ddpm.py:330-363 / ddim.py:68-103 from there (clamp, posterior mean,
+ * noise, logprob; CFG combine fused).  var_mode DL_VAR_FIXED: pred / pred_uncond [B, chw], tables as for dl_ddpm_step /
+ * dl_ddim_step; DL_VAR_LEARNED / DL_VAR_LEARNED_RANGE: [B, 2 chw] read in place, tables as for dl_ddpm_step_lv / dl_ddim_step_lv
+ * (DDIM discards the variance half).  No ddpm_coefs: only DL_MEAN_XPREV reads them. */
+DL_API int dl_ddpm_step_v(const float* pred, const float* pred_uncond, float guidance, const float* xt, const float* noise,
+                          const int32_t* t, const float* tables, int32_t T, int var_mode, int clamp_x, float* x_prev,
+                          float* x0_est, float* mean, float* std, float* logprob, int64_t batch, int64_t chw,
+                          dl_stream_t stream);
+DL_API int dl_ddim_step_v(const float* pred, const float* pred_uncond, float guidance, const float* xt, const float* noise,
+                          const int32_t* t, const float* tables, int32_t T, int var_mode, int clamp_x, float eta, float* x_prev,
+                          float* x0_est, float* mean, float* std, float* logprob, int64_t batch, int64_t chw,
+                          dl_stream_t stream);
 
 /* ------------------------------------------------------------------ GEMMs (bf16 in, f32 MFMA accumulate) */
 /* nn.Linear forward / dgrad (mmdit.py:81,102,260-264; nn.py:530; mmdit.py:542-548):

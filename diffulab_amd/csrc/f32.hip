@@ -13,6 +13,14 @@
 //
 // Reference arithmetic restated per kernel: see the entry points' comments in include/diffulab_hip.h.
 #include "common.h"
+#include "f32_paths.h"
+
+#include <atomic>
+
+// the path code of the last GEMM / softmax launch (f32_paths.h): one relaxed host-side store per call, read by the tests
+static std::atomic<int> g_last_f32_path{DL_F32_PATH_NONE};
+static void f32_note_path(int path) { g_last_f32_path.store(path, std::memory_order_relaxed); }
+extern "C" __attribute__((visibility("default"))) int dl_lab_last_f32_path() { return g_last_f32_path.load(std::memory_order_relaxed); }
 
 // ============================================================================================================ GEMM
 #define FG_BM 128
@@ -266,6 +274,7 @@ extern "C" int dl_f32_gemm(const dl_f32_gemm_t* d, dl_stream_t stream) {
     else if (d->trans_a && !d->trans_b) FG_GO(true, false, V);  \
     else FG_GO(true, true, V);                     \
   } while (0)
+  f32_note_path(g.splits > 1 ? (vec ? F32_GEMM_VEC_SPLITK : F32_GEMM_SCALAR_SPLITK) : (vec ? F32_GEMM_VEC : F32_GEMM_SCALAR));
   if (vec) FG_PICK(true);
   else FG_PICK(false);
 #undef FG_PICK
@@ -926,10 +935,12 @@ extern "C" int dl_f32_softmax_fwd(float* s, int64_t rows, int64_t cols, dl_strea
   DL_CHECK_ARG(s && rows > 0 && cols > 0 && cols < (1ll << 31) && ((uintptr_t)s & 3) == 0, "dl_f32_softmax_fwd: rows=%lld cols=%lld",
                (long long)rows, (long long)cols);
   if (cols % 4 != 0 || cols > 256 * FS_NJ || ((uintptr_t)s & 15) != 0) {
+    f32_note_path(F32_SOFTMAX_FWD_ANY);
     hipLaunchKernelGGL(f32_softmax_fwd_any_k, grid_1d(rows, 4, 16384), 256, 0, (hipStream_t)stream, s, rows, (int)cols);
     DL_LAUNCH_CHECK();
     return DL_OK;
   }
+  f32_note_path(F32_SOFTMAX_FWD_VEC);
   hipLaunchKernelGGL(f32_softmax_fwd_k, grid_1d(rows, 4, 16384), 256, 0, (hipStream_t)stream, s, rows, (int)cols);
   DL_LAUNCH_CHECK();
   return DL_OK;
@@ -938,10 +949,12 @@ extern "C" int dl_f32_softmax_bwd(const float* p, float* dp, int64_t rows, int64
   DL_CHECK_ARG(p && dp && rows > 0 && cols > 0 && cols < (1ll << 31) && (((uintptr_t)p | (uintptr_t)dp) & 3) == 0,
                "dl_f32_softmax_bwd: rows=%lld cols=%lld", (long long)rows, (long long)cols);
   if (cols % 4 != 0 || cols > 256 * FS_NJ || (((uintptr_t)p | (uintptr_t)dp) & 15) != 0) {
+    f32_note_path(F32_SOFTMAX_BWD_ANY);
     hipLaunchKernelGGL(f32_softmax_bwd_any_k, grid_1d(rows, 4, 16384), 256, 0, (hipStream_t)stream, p, dp, rows, (int)cols);
     DL_LAUNCH_CHECK();
     return DL_OK;
   }
+  f32_note_path(F32_SOFTMAX_BWD_VEC);
   hipLaunchKernelGGL(f32_softmax_bwd_k, grid_1d(rows, 4, 16384), 256, 0, (hipStream_t)stream, p, dp, rows, (int)cols);
   DL_LAUNCH_CHECK();
   return DL_OK;
@@ -972,6 +985,7 @@ extern "C" int dl_f32_softmax_keymask_fwd(float* s, const float* key_bias, int64
                                           dl_stream_t stream) {
   DL_CHECK_ARG(s && B > 0 && rows_per_sample > 0 && cols > 0 && cols < (1ll << 31) && (((uintptr_t)s | (uintptr_t)key_bias) & 3) == 0,
                "dl_f32_softmax_keymask_fwd: B=%lld rows=%lld cols=%lld", (long long)B, (long long)rows_per_sample, (long long)cols);
+  f32_note_path(F32_SOFTMAX_KEYMASK);
   hipLaunchKernelGGL(f32_softmax_keymask_fwd_k, grid_1d(B * rows_per_sample, 4, 16384), 256, 0, (hipStream_t)stream, s, key_bias,
                      B * rows_per_sample, rows_per_sample, (int)cols);
   DL_LAUNCH_CHECK();

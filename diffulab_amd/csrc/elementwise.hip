@@ -523,6 +523,48 @@ extern "C" int dl_ddim_step_v(const float* pred, const float* pred_uncond, float
   return DL_OK;
 }
 
+// ---------------------------------------------------------------- image-to-image / inpainting (Flow.denoise, GaussianDiffusion.denoise)
+// The known region of SDEdit (Meng et al. 2022) / RePaint (Lugmayr et al. 2022) sampling, after a sampler step: known = a ref + b noise
+// is the reference image at the noise level the step arrived at, and out = x where the mask generates, known where it keeps, the
+// convex mix on a soft edge.  m >= 1 and m <= 0 are selects, so nothing non-finite crosses from the discarded side and the kept side
+// is returned bit for bit.  Without a mask (MASK false) out = known: RePaint's re-noise x_t = a x_prev + b noise between the repeats of
+// a step.  x, ref and out carry no __restrict__: out may be x or ref (every element is read before it alone is written).
+template <bool MASK>
+__global__ void inpaint_blend_k(const float* x, const float* ref, const float* __restrict__ noise, const float* __restrict__ mask,
+                                float a, float b, float* out, int64_t n, int64_t chw, int64_t hw, int mask_full) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float known = a * ref[i];
+    if (noise) known += b * noise[i];
+    if (MASK) {
+      const float m = mask[mask_full ? i : (i / chw) * hw + i % hw];
+      const float xi = x[i];
+      out[i] = m >= 1.0f ? xi : (m <= 0.0f ? known : m * xi + (1.0f - m) * known);
+    } else {
+      out[i] = known;
+    }
+  }
+}
+extern "C" int dl_inpaint_blend(const float* x, const float* ref, const float* noise, const float* mask, float a, float b,
+                                float* out, int64_t batch, int64_t channels, int64_t hw, int64_t mask_channels,
+                                dl_stream_t stream) {
+  DL_CHECK_ARG(ref && out, "dl_inpaint_blend: bad args (ref, out non-null)");
+  DL_CHECK_ARG(batch > 0 && channels > 0 && hw > 0, "dl_inpaint_blend: bad args (batch, channels, hw > 0)");
+  DL_CHECK_ARG(noise || b == 0.0f, "dl_inpaint_blend: b != 0 needs noise");
+  DL_CHECK_ARG((mask != nullptr) == (x != nullptr), "dl_inpaint_blend: a mask needs x, and x needs a mask (mask NULL: out = a ref + b noise)");
+  DL_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == channels, "dl_inpaint_blend: mask_channels %lld is neither 1 nor channels %lld",
+               (long long)mask_channels, (long long)channels);
+  const int64_t chw = channels * hw, n = batch * chw;
+  if (b == 0.0f) noise = nullptr;  // (the final Gaussian step: known = ref, nothing is read from noise)
+  if (mask)
+    hipLaunchKernelGGL(inpaint_blend_k<true>, ew_grid(n), 256, 0, (hipStream_t)stream, x, ref, noise, mask, a, b, out, n, chw, hw,
+                       (int)(mask_channels == channels));
+  else
+    hipLaunchKernelGGL(inpaint_blend_k<false>, ew_grid(n), 256, 0, (hipStream_t)stream, x, ref, noise, mask, a, b, out, n, chw, hw, 0);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
 // ---------------------------------------------------------------- hybrid loss of a learned-variance model
 // L_simple + L_vlb of Nichol & Dhariwal, "Improved Denoising Diffusion Probabilistic Models" (2021), eq. 16, which the reference
 // announces and leaves unwritten (gaussian_diffusion.py:267).  One element's variational-bound term in nats and, where GRAD, its

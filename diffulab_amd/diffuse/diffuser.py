@@ -53,10 +53,22 @@ class Diffuser:
 
     def generate(self, model_inputs, data_shape: tuple[int, ...] | None = None, use_tqdm: bool = True,
                  clamp_x: bool = False, guidance_scale: float = 0, sampler_args: dict[str, Any] = {},
-                 return_intermediates: bool = False, return_latents: bool = False) -> SamplingOutput:
+                 return_intermediates: bool = False, return_latents: bool = False, init_image: Tensor | None = None,
+                 strength: float = 1.0, mask: Tensor | None = None, resample: int = 1) -> SamplingOutput:
+        """init_image, strength, mask, resample (this project's; the reference starts from pure noise only): image-to-image (SDEdit)
+        and inpainting (RePaint) with every sampler.  init_image [B, C, *spatial] lives in the space the denoiser works in (with a
+        vision tower: scaled latents, no encoder is run); strength in (0, 1] is the fraction of the sampler's steps that is run, from
+        init_image noised to the level where they start; mask [B, 1, *spatial] or [B, C, *spatial], bool or float in [0, 1], is 1
+        where the image is generated and 0 where init_image is kept; resample >= 1 repeats every step but the last that many times
+        (RePaint's U).  model_inputs["x"] stays the initial noise.  A bad argument raises a ValueError that names it before any device
+        work; with all four at their defaults the call is what it was.  Details: `Flow._denoise_from_image`,
+        `GaussianDiffusion._denoise_from_image`."""
+        extra = {}
+        if init_image is not None or strength != 1.0 or mask is not None or resample != 1:
+            extra = dict(init_image=init_image, strength=strength, mask=mask, resample=resample)
         out = self.diffusion.denoise(self.denoiser, model_inputs=model_inputs, data_shape=data_shape, use_tqdm=use_tqdm,
                                      clamp_x=clamp_x, guidance_scale=guidance_scale, sampler_args=sampler_args,
-                                     return_intermediates=return_intermediates)
+                                     return_intermediates=return_intermediates, **extra)
         if self.vision_tower and not return_latents:  # decode latents with the (external) VAE, diffuser.py:220-227
             scale, bias = self.latent_scale, self.latent_bias
             if isinstance(scale, Tensor):

@@ -11,7 +11,7 @@ from torch import Tensor
 
 from ... import ops
 from ..samplers.common import Sampler, StepResult
-from ..utils import SamplingOutput
+from ..utils import SamplingOutput, check_image_conditioning
 
 
 class _MSEHead(torch.autograd.Function):
@@ -135,10 +135,41 @@ class Diffusion(ABC):
     @abstractmethod
     def denoise(self, model, model_inputs, data_shape=None, use_tqdm: bool = True, clamp_x: bool = False,
                 guidance_scale: float = 0, sampler_args: dict[str, Any] = {},
-                return_intermediates: bool = False) -> SamplingOutput: ...
+                return_intermediates: bool = False, init_image: Tensor | None = None, strength: float = 1.0,
+                mask: Tensor | None = None, resample: int = 1) -> SamplingOutput: ...
 
     @abstractmethod
     def draw_timesteps(self, batch_size: int) -> Tensor: ...
+
+    # Image-to-image (SDEdit, Meng et al. 2022) and inpainting (RePaint, Lugmayr et al. 2022), which the reference does not have.
+    # Shared by both heads: the arguments are validated on the host before anything touches the device, then brought to the f32
+    # contiguous form `ops.inpaint_blend` reads.
+    @staticmethod
+    def _image_conditioning(model, model_inputs, data_shape, init_image: Tensor | None, strength: float, mask: Tensor | None,
+                            resample: int) -> tuple[Tensor, Tensor, Tensor | None] | None:
+        """-> None with all four arguments at their defaults (the caller then takes the plain sampling path untouched), else
+        (init_image, eps0, mask or None) as f32 contiguous tensors on the model's device; eps0 is the run's initial noise"""
+        shape = tuple(model_inputs["x"].shape) if "x" in model_inputs else (None if data_shape is None else tuple(data_shape))
+        if not check_image_conditioning(shape, init_image, strength, mask, resample):
+            return None
+        p0 = next(model.parameters())
+        init = init_image.to(device=p0.device, dtype=torch.float32).contiguous()
+        # model_inputs["x"] keeps its meaning: the initial noise
+        eps0 = model_inputs["x"] if "x" in model_inputs else torch.randn(tuple(init.shape), device=p0.device, dtype=p0.dtype)
+        eps0 = eps0.to(device=p0.device, dtype=torch.float32).contiguous()
+        m = None if mask is None else mask.to(device=p0.device, dtype=torch.float32).contiguous()
+        return init, eps0, m
+
+    @staticmethod
+    def _record(out: StepResult, xt, x0s, means, stds, lps) -> None:
+        xt.append(out["x_prev"])
+        x0s.append(out["estimated_x0"])
+        if "x_prev_mean" in out:
+            means.append(out["x_prev_mean"])
+        if "x_prev_std" in out:
+            stds.append(out["x_prev_std"])
+        if "logprob" in out:
+            lps.append(out["logprob"])
 
     # shared by both heads: stack what the sampler loop collected (flow.py:510-522 / gaussian_diffusion.py:436-445)
     @staticmethod

@@ -18,7 +18,7 @@ from torch import Tensor
 from ... import ops
 from ..samplers.common import StepResult
 from ..samplers.flow import Euler, EulerMaruyama
-from ..utils import SamplingOutput, to_device
+from ..utils import SamplingOutput, flow_renoise_coefs, strength_to_steps, to_device
 from .diffusion import Diffusion, mse_head
 
 try:
@@ -155,7 +155,14 @@ class Flow(Diffusion):
     @torch.inference_mode()
     def denoise(self, model, model_inputs, data_shape: tuple[int, ...] | None = None, use_tqdm: bool = True,
                 clamp_x: bool = False, guidance_scale: float = 0, sampler_args: dict[str, Any] = {},
-                return_intermediates: bool = False) -> SamplingOutput:
+                return_intermediates: bool = False, init_image: Tensor | None = None, strength: float = 1.0,
+                mask: Tensor | None = None, resample: int = 1) -> SamplingOutput:
+        """init_image / strength / mask / resample (this project's; the reference has neither): see `_denoise_from_image`.  At their
+        defaults this is the reference's loop, call for call."""
+        cond = self._image_conditioning(model, model_inputs, data_shape, init_image, strength, mask, resample)
+        if cond is not None:
+            return self._denoise_from_image(model, model_inputs, cond, strength, resample, use_tqdm, clamp_x, guidance_scale,
+                                            sampler_args, return_intermediates)
         p0 = next(model.parameters())
         if "x" not in model_inputs:
             assert data_shape is not None, "'data_shape' must be provided if 'x' is not in model_inputs"
@@ -183,3 +190,47 @@ class Flow(Diffusion):
         if clamp_x:
             model_inputs["x"] = model_inputs["x"].clamp(-1, 1)
         return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=0)  # std stacked on dim 0 (flow.py:520)
+
+    def _denoise_from_image(self, model, model_inputs, cond, strength: float, resample: int, use_tqdm: bool, clamp_x: bool,
+                            guidance_scale: float, sampler_args: dict[str, Any], return_intermediates: bool) -> SamplingOutput:
+        """Image-to-image (SDEdit, Meng et al. 2022) and inpainting (RePaint, Lugmayr et al. 2022) on the grid of `self.timesteps`.
+
+        Start: k = strength_to_steps(steps, strength) steps are run, from index i0 = steps - k: x = (1 - t) init_image + t eps0 at
+        t = timesteps[i0], eps0 = model_inputs["x"] (the initial noise, as in the plain call) or a fresh draw.  strength 1 starts at
+        t = 1, i.e. from eps0 itself.
+        Known region (mask 0): after every step to t_prev it is set to (1 - t_prev) init_image + t_prev eps0 -- always the same eps0,
+        so it follows one trajectory and ends at init_image exactly.
+        resample (RePaint's U, jump length 1): every step but the last runs `resample` times; between two repeats x_prev goes back to
+        t_curr by x_t = a x_prev + s randn, a = (1 - t_curr) / (1 - t_prev), s = sqrt(t_curr^2 - a^2 t_prev^2), which keeps the
+        marginal (1 - t_curr) x0 + t_curr eps.  The denoiser runs resample (k - 1) + 1 times (twice that where CFG makes two forwards).
+        Intermediates: `xt` holds the starting x and each step's x_prev after the blend (of the last repeat); estimated_x0, xt_mean,
+        xt_std and logprob are what the sampler returned, before the blend.  clamp_x clamps the final sample, as in the plain loop (the
+        known region too, where init_image leaves [-1, 1])."""
+        init, eps0, m = cond
+        k = strength_to_steps(self.steps, strength)
+        i0 = self.steps - k
+        B = init.shape[0]
+        model_inputs["x"], _ = self.add_noise(init, torch.full((B,), self.timesteps[i0], dtype=torch.float32), eps0)
+        keep = return_intermediates
+        xt = [model_inputs["x"]] if keep else None
+        x0s: list[Tensor] = []
+        means: list[Tensor] = []
+        stds: list[Tensor] = []
+        lps: list[Tensor] = []
+        pairs = list(zip(self.timesteps[i0:-1], self.timesteps[i0 + 1:]))
+        for j, (t_curr, t_prev) in enumerate(tqdm(pairs, desc="generating image", total=k, disable=not use_tqdm, leave=False)):
+            repeats = resample if j + 1 < k else 1
+            for r in range(repeats):
+                out = self.one_step_denoise(model, model_inputs, t_curr=t_curr, t_prev=t_prev, guidance_scale=guidance_scale,
+                                            sampler_args=sampler_args)
+                if m is not None:  # in place: the sampler's x_prev is a fresh tensor
+                    out["x_prev"] = ops.inpaint_blend(out["x_prev"], init, eps0, m, 1.0 - t_prev, t_prev, out=out["x_prev"])
+                model_inputs["x"] = out["x_prev"]
+                if r + 1 < repeats:
+                    a, s = flow_renoise_coefs(t_curr, t_prev)
+                    model_inputs["x"] = ops.inpaint_blend(None, out["x_prev"], torch.randn_like(out["x_prev"]), None, a, s)
+            if keep:
+                self._record(out, xt, x0s, means, stds, lps)
+        if clamp_x:
+            model_inputs["x"] = model_inputs["x"].clamp(-1, 1)
+        return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=0)

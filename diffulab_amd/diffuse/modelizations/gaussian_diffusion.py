@@ -16,7 +16,7 @@ from torch import Tensor
 from ... import ops
 from ..samplers.common import StepResult
 from ..samplers.gaussian_diffusion import DDIM, DDPM
-from ..utils import SamplingOutput, f32_table, to_device
+from ..utils import SamplingOutput, f32_table, strength_to_steps, to_device
 from .diffusion import Diffusion, gd_head, hybrid_head, mse_head
 from .utils import space_timesteps
 
@@ -230,7 +230,14 @@ class GaussianDiffusion(Diffusion):
     @torch.no_grad()
     def denoise(self, model, model_inputs, data_shape: tuple[int, ...] | None = None, use_tqdm: bool = True,
                 clamp_x: bool = False, guidance_scale: float = 0, sampler_args: dict[str, Any] = {},
-                return_intermediates: bool = False) -> SamplingOutput:
+                return_intermediates: bool = False, init_image: Tensor | None = None, strength: float = 1.0,
+                mask: Tensor | None = None, resample: int = 1) -> SamplingOutput:
+        """init_image / strength / mask / resample (this project's; the reference has neither): see `_denoise_from_image`.  At their
+        defaults this is the reference's loop, call for call."""
+        cond = self._image_conditioning(model, model_inputs, data_shape, init_image, strength, mask, resample)
+        if cond is not None:
+            return self._denoise_from_image(model, model_inputs, cond, strength, resample, use_tqdm, clamp_x, guidance_scale,
+                                            sampler_args, return_intermediates)
         if "x" not in model_inputs:
             assert data_shape is not None, "'data_shape' must be provided if 'x' is not in model_inputs"
             p0 = next(model.parameters())
@@ -255,4 +262,51 @@ class GaussianDiffusion(Diffusion):
                     stds.append(out["x_prev_std"])
                 if "logprob" in out:
                     lps.append(out["logprob"])
+        return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=1)
+
+    def _denoise_from_image(self, model, model_inputs, cond, strength: float, resample: int, use_tqdm: bool, clamp_x: bool,
+                            guidance_scale: float, sampler_args: dict[str, Any], return_intermediates: bool) -> SamplingOutput:
+        """Image-to-image (SDEdit, Meng et al. 2022) and inpainting (RePaint, Lugmayr et al. 2022) on the (respaced) chain.
+
+        Start: k = strength_to_steps(steps, strength) steps are run, t = k - 1 .. 0, from x = q(x_t | init_image) at t = k - 1 with
+        the noise eps0 = model_inputs["x"] (the initial noise, as in the plain call) or a fresh draw.  strength 1 therefore starts
+        from q(x_{T-1} | init_image), not from pure noise: the chain's last level still carries sqrt(alphas_bar[T-1]) of the image
+        (6.4e-3 on the linear 1000-step chain).
+        Known region (mask 0): after the step at index t, whose x_prev lives at t - 1, it is set to
+        sqrt_alphas_bar[t-1] init_image + sqrt(1 - alphas_bar[t-1]) randn with a fresh draw per step, as RePaint does, and to init_image
+        itself after the step at t == 0.  The coefficients are the chain's fp64 tables, cast to f32 once per step.
+        resample (RePaint's U, jump length 1): every step but the last runs `resample` times; between two repeats x_prev goes back one
+        level by x_t = sqrt(1 - betas[t]) x_prev + sqrt(betas[t]) randn.  The denoiser runs resample (k - 1) + 1 times (twice that
+        where CFG makes two forwards).
+        Intermediates: `xt` holds the starting x and each step's x_prev after the blend (of the last repeat); estimated_x0, xt_mean,
+        xt_std and logprob are what the sampler returned, before the blend."""
+        init, eps0, m = cond
+        k = strength_to_steps(self.steps, strength)
+        B = init.shape[0]
+        model_inputs["x"], _ = self.add_noise(init, torch.full((B,), k - 1, dtype=torch.int32), eps0)
+        keep = return_intermediates
+        xt = [model_inputs["x"]] if keep else None
+        x0s: list[Tensor] = []
+        means: list[Tensor] = []
+        stds: list[Tensor] = []
+        lps: list[Tensor] = []
+        for t in tqdm(list(range(k))[::-1], desc="generating image", total=k, disable=not use_tqdm, leave=False):
+            repeats = resample if t > 0 else 1
+            for r in range(repeats):
+                out = self.one_step_denoise(model=model, model_inputs=model_inputs, t=t, clamp_x=clamp_x,
+                                            guidance_scale=guidance_scale, sampler_args=sampler_args)
+                if m is not None:  # in place: the sampler's x_prev is a fresh tensor
+                    xp = out["x_prev"]
+                    if t > 0:
+                        a, b = float(self.sqrt_alphas_bar[t - 1]), float((1.0 - self.alphas_bar[t - 1]).sqrt())
+                        out["x_prev"] = ops.inpaint_blend(xp, init, torch.randn_like(xp), m, a, b, out=xp)
+                    else:
+                        out["x_prev"] = ops.inpaint_blend(xp, init, None, m, 1.0, 0.0, out=xp)
+                model_inputs["x"] = out["x_prev"]
+                if r + 1 < repeats:
+                    beta = float(self.betas[t])
+                    model_inputs["x"] = ops.inpaint_blend(None, out["x_prev"], torch.randn_like(out["x_prev"]), None,
+                                                          (1.0 - beta) ** 0.5, beta**0.5)
+            if keep:
+                self._record(out, xt, x0s, means, stds, lps)
         return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=1)

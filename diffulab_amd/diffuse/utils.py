@@ -2,6 +2,7 @@
 
 from __future__ import annotations
 
+import math
 from typing import TypedDict
 
 import torch
@@ -26,6 +27,56 @@ def f32_table(table_fp64: Tensor, device: torch.device) -> Tensor:
     """fp64 schedule table -> fp32 device table: the same rounding `extract_into_tensor` applies per gather
     (diffuse/utils.py:16 `.float()`), hoisted out of the loop."""
     return table_fp64.to(torch.float32).to(device).contiguous()
+
+
+def strength_to_steps(steps: int, strength: float) -> int:
+    """the number of sampler steps an image-to-image run makes: k = clamp(floor(strength * steps + 0.5), 1, steps).  strength 1 runs
+    the whole chain; a strength too small for one step still runs the last one."""
+    return max(1, min(int(steps), int(math.floor(float(strength) * steps + 0.5))))
+
+
+def flow_renoise_coefs(t_curr: float, t_prev: float) -> tuple[float, float]:
+    """(a, s) of x_t = a x_prev + s randn, which takes the rectified-flow marginal (1 - t_prev) x0 + t_prev eps back to
+    (1 - t_curr) x0 + t_curr eps: a = (1 - t_curr) / (1 - t_prev), s^2 = t_curr^2 - a^2 t_prev^2 (t_prev < t_curr, t_prev < 1)"""
+    a = (1.0 - t_curr) / (1.0 - t_prev)
+    return a, max(t_curr * t_curr - a * a * t_prev * t_prev, 0.0) ** 0.5
+
+
+def check_image_conditioning(shape: tuple[int, ...] | None, init_image: Tensor | None, strength: float, mask: Tensor | None,
+                             resample: int) -> bool:
+    """validate the image-to-image / inpainting arguments of `Diffuser.generate` / `Diffusion.denoise` against `shape`, the shape of the
+    generated tensor (None: it follows init_image).  Host checks only, apart from one min / max over the mask.  -> False when all four
+    are at their defaults (the plain sampling path), else True; a ValueError names the offending argument."""
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength must be a number in (0, 1], got {strength!r}")
+    if isinstance(resample, bool) or not isinstance(resample, int) or resample < 1:
+        raise ValueError(f"resample must be an integer >= 1, got {resample!r}")
+    if init_image is None:
+        if strength < 1.0:
+            raise ValueError(f"strength={strength} < 1 needs init_image: without one the sampler starts from pure noise")
+        if mask is not None:
+            raise ValueError("mask needs init_image: the region it keeps is taken from there")
+        if resample > 1:
+            raise ValueError(f"resample={resample} > 1 needs mask (and init_image): it is RePaint's resampling of an inpainting run")
+        return False
+    if resample > 1 and mask is None:
+        raise ValueError(f"resample={resample} > 1 needs mask: it is RePaint's resampling of an inpainting run")
+    if not isinstance(init_image, Tensor) or init_image.dim() < 3:
+        raise ValueError("init_image must be a [B, C, *spatial] tensor")
+    if shape is not None and tuple(init_image.shape) != tuple(shape):
+        raise ValueError(f"init_image has shape {tuple(init_image.shape)}, the generated tensor {tuple(shape)}")
+    if mask is not None:
+        B, C, spatial = init_image.shape[0], init_image.shape[1], tuple(init_image.shape[2:])
+        if not isinstance(mask, Tensor) or tuple(mask.shape) not in ((B, 1) + spatial, (B, C) + spatial):
+            got = tuple(mask.shape) if isinstance(mask, Tensor) else type(mask).__name__
+            raise ValueError(f"mask must have shape {(B, 1) + spatial} or {(B, C) + spatial}, got {got}")
+        if mask.dtype != torch.bool:
+            if not mask.dtype.is_floating_point:
+                raise ValueError(f"mask must be bool or floating point, got {mask.dtype}")
+            lo, hi = torch.aminmax(mask.detach().float())
+            if not (float(lo) >= 0.0 and float(hi) <= 1.0):  # (a NaN fails both comparisons)
+                raise ValueError(f"mask values must lie in [0, 1], got min {float(lo)}, max {float(hi)}")
+    return True
 
 
 class _PinnedRing:

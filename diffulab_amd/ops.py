@@ -315,6 +315,26 @@ def ddim_step_v(pred, pred_uncond, guidance, xt, noise, t, tables, var_mode: int
     return xp, x0, mean, std, lp
 
 
+def inpaint_blend(x: Tensor | None, ref: Tensor, noise: Tensor | None, mask: Tensor | None, a: float, b: float,
+                  out: Tensor | None = None) -> Tensor:
+    """known = a ref + b noise; with a mask ([B, 1, *spatial] or [B, C, *spatial], f32, 1 = generate) out = x where mask >= 1, known
+    where mask <= 0, mask x + (1 - mask) known between; mask None (then x None): out = known, the re-noise form.  noise may be None
+    when b == 0.  All tensors f32 and contiguous, ref [B, C, *spatial]; out may be x or ref, allocated here when None."""
+    assert ref.dim() >= 2 and ref.dtype == torch.float32 and ref.is_contiguous()
+    B, C = ref.shape[0], ref.shape[1]
+    hw = ref.numel() // (B * C) if ref.numel() else 0
+    for other in (x, noise, out):
+        assert other is None or (other.shape == ref.shape and other.dtype == torch.float32 and other.is_contiguous())
+    mc = 0
+    if mask is not None:
+        assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.dim() == ref.dim()
+        assert mask.shape[0] == B and mask.shape[2:] == ref.shape[2:], (tuple(mask.shape), tuple(ref.shape))
+        mc = mask.shape[1]
+    out = torch.empty_like(ref) if out is None else out
+    _call("dl_inpaint_blend", _p(x), _p(ref), _p(noise), _p(mask), float(a), float(b), _p(out), B, C, hw, mc, _s())
+    return out
+
+
 # ------------------------------------------------------------------ GEMMs
 def gemm_nt(a: Tensor, b: Tensor, out: Tensor, *, bias: Tensor | None = None, act: int = ACT_NONE,
             pre_out: Tensor | None = None, resid: Tensor | None = None, gate: Tensor | None = None,

@@ -186,6 +186,21 @@ DL_API int dl_ddim_step_v(const float* pred, const float* pred_uncond, float gui
                           const int32_t* t, const float* tables, int32_t T, int var_mode, int clamp_x, float eta, float* x_prev,
                           float* x0_est, float* mean, float* std, float* logprob, int64_t batch, int64_t chw,
                           dl_stream_t stream);
+/* Image-to-image and inpainting, which the reference does not have: the known region of Meng et al., "SDEdit: Guided Image Synthesis
+ * and Editing with Stochastic Differential Equations" (2022) and Lugmayr et al., "RePaint: Inpainting using Denoising Diffusion
+ * Probabilistic Models" (2022), for the loops of diffuse/modelizations/flow.py (Flow.denoise) and gaussian_diffusion.py
+ * (GaussianDiffusion.denoise).  x, ref, noise, out are [batch, channels, hw]; mask is [batch, mask_channels, hw] with mask_channels 1
+ * (one plane for every channel) or channels; 1 = generate, 0 = keep.  Per element
+ *   known = a ref + b noise                 (b == 0: noise is not read and may be NULL)
+ *   out   = m >= 1 ? x : (m <= 0 ? known : m x + (1 - m) known)
+ * where the two hard cases are selects: a NaN or inf of the discarded side does not reach out, the kept side arrives bit for bit.
+ * After a sampler step to t_prev, ref = init_image and (a, b) = (1 - t_prev, t_prev) with the run's initial noise (flow), or
+ * (sqrt_ab[t-1], sqrt(1 - ab[t-1])) with fresh noise, (1, 0) after the last step (Gaussian diffusion, RePaint alg. 1 line 4-5).
+ * mask == NULL (then x must be NULL too): out = known, RePaint's re-noise between the repeats of a step (alg. 1 line 10) with
+ * ref = x_prev.  out may be x or ref (in place); it must not overlap noise or mask. */
+DL_API int dl_inpaint_blend(const float* x, const float* ref, const float* noise, const float* mask, float a, float b,
+                            float* out, int64_t batch, int64_t channels, int64_t hw, int64_t mask_channels,
+                            dl_stream_t stream);
 
 /* ------------------------------------------------------------------ GEMMs (bf16 in, f32 MFMA accumulate) */
 /* nn.Linear forward / dgrad (mmdit.py:81,102,260-264; nn.py:530; mmdit.py:542-548):

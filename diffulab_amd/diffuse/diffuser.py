@@ -10,7 +10,7 @@ from torch import Tensor
 from .modelizations.diffusion import Diffusion
 from .modelizations.flow import Flow
 from .modelizations.gaussian_diffusion import GaussianDiffusion
-from .utils import SamplingOutput
+from .utils import SamplingOutput, guidance_kwargs
 
 
 class Diffuser:
@@ -53,6 +53,8 @@ class Diffuser:
 
     def generate(self, model_inputs, data_shape: tuple[int, ...] | None = None, use_tqdm: bool = True,
                  clamp_x: bool = False, guidance_scale: float = 0, sampler_args: dict[str, Any] = {},
+                 guidance_rescale: float = 0.0, guidance_interval: tuple[float, float] | None = None,
+                 dynamic_threshold: float | None = None, threshold_max: float | None = None,
                  return_intermediates: bool = False, return_latents: bool = False, init_image: Tensor | None = None,
                  strength: float = 1.0, mask: Tensor | None = None, resample: int = 1) -> SamplingOutput:
         """init_image, strength, mask, resample (this project's; the reference starts from pure noise only): image-to-image (SDEdit)
@@ -62,10 +64,18 @@ class Diffuser:
         where the image is generated and 0 where init_image is kept; resample >= 1 repeats every step but the last that many times
         (RePaint's U).  model_inputs["x"] stays the initial noise.  A bad argument raises a ValueError that names it before any device
         work; with all four at their defaults the call is what it was.  Details: `Flow._denoise_from_image`,
-        `GaussianDiffusion._denoise_from_image`."""
-        extra = {}
+        `GaussianDiffusion._denoise_from_image`.
+
+        guidance_rescale, guidance_interval, dynamic_threshold, threshold_max (this project's): guided sampling at a high
+        guidance_scale.  guidance_rescale = phi in [0, 1] scales the guided prediction back to the conditional prediction's per-sample
+        standard deviation, mixed by phi (CFG rescale, Lin et al. 2023); guidance_interval = (lo, hi), 0 <= lo <= hi <= 1, guides only
+        the steps whose noise level lies inside it (flow: t; Gaussian diffusion: (training index + 1) / training steps) and runs one
+        forward elsewhere (Kynkaanniemi et al. 2024); dynamic_threshold = p in (0, 1] clamps every step's x0 to its own p-quantile
+        of |x0| (at least 1, at most threshold_max) and divides by it (Saharia et al. 2022; Gaussian diffusion only).  Same rule: a
+        ValueError before any device work, and the call is what it was with all four at their defaults."""
+        extra = guidance_kwargs(guidance_rescale, guidance_interval, dynamic_threshold, threshold_max)
         if init_image is not None or strength != 1.0 or mask is not None or resample != 1:
-            extra = dict(init_image=init_image, strength=strength, mask=mask, resample=resample)
+            extra.update(init_image=init_image, strength=strength, mask=mask, resample=resample)
         out = self.diffusion.denoise(self.denoiser, model_inputs=model_inputs, data_shape=data_shape, use_tqdm=use_tqdm,
                                      clamp_x=clamp_x, guidance_scale=guidance_scale, sampler_args=sampler_args,
                                      return_intermediates=return_intermediates, **extra)

@@ -134,7 +134,9 @@ class Diffusion(ABC):
 
     @abstractmethod
     def denoise(self, model, model_inputs, data_shape=None, use_tqdm: bool = True, clamp_x: bool = False,
-                guidance_scale: float = 0, sampler_args: dict[str, Any] = {},
+                guidance_scale: float = 0, sampler_args: dict[str, Any] = {}, guidance_rescale: float = 0.0,
+                guidance_interval: tuple[float, float] | None = None, dynamic_threshold: float | None = None,
+                threshold_max: float | None = None,
                 return_intermediates: bool = False, init_image: Tensor | None = None, strength: float = 1.0,
                 mask: Tensor | None = None, resample: int = 1) -> SamplingOutput: ...
 

@@ -18,7 +18,8 @@ from torch import Tensor
 from ... import ops
 from ..samplers.common import StepResult
 from ..samplers.flow import Euler, EulerMaruyama
-from ..utils import SamplingOutput, flow_renoise_coefs, strength_to_steps, to_device
+from ..utils import (SamplingOutput, check_guidance, flow_renoise_coefs, guidance_kwargs, in_guidance_interval, strength_to_steps,
+                     to_device)
 from .diffusion import Diffusion, mse_head
 
 try:
@@ -109,7 +110,17 @@ class Flow(Diffusion):
         return tuple((model_inputs["x"] - pred) / max(t_curr, 0.05) for pred in pair)
 
     def one_step_denoise(self, model, model_inputs, t_prev: float, t_curr: float, guidance_scale: float,
-                         sampler_args: dict[str, Any] = {}) -> StepResult:
+                         sampler_args: dict[str, Any] = {}, guidance_rescale: float = 0.0,
+                         guidance_interval: tuple[float, float] | None = None, dynamic_threshold: float | None = None,
+                         threshold_max: float | None = None) -> StepResult:
+        """guidance_rescale / guidance_interval (this project's): CFG rescale reaches the sampler as a keyword; a step whose t_curr lies
+        outside the interval makes the one conditional forward.  dynamic_threshold is refused: the flow step has no x0 clamp."""
+        if guidance_rescale or guidance_interval is not None or dynamic_threshold is not None or threshold_max is not None:
+            check_guidance(guidance_scale, guidance_rescale, guidance_interval, dynamic_threshold, threshold_max, flow=True)
+            if guidance_rescale:
+                sampler_args = {**sampler_args, "guidance_rescale": guidance_rescale}
+            if not in_guidance_interval(guidance_interval, t_curr):
+                guidance_scale = 0
         if guidance_scale > 0:
             # flow.py:256-259 makes two forwards (p = 0, then p = 1: every label dropped).  A denoiser whose `p` only reaches the
             # label drop runs them as ONE forward over [x ; x] (FlatArenaDenoiser.forward_cfg_pair: same values per row, half the
@@ -155,14 +166,19 @@ class Flow(Diffusion):
     @torch.inference_mode()
     def denoise(self, model, model_inputs, data_shape: tuple[int, ...] | None = None, use_tqdm: bool = True,
                 clamp_x: bool = False, guidance_scale: float = 0, sampler_args: dict[str, Any] = {},
+                guidance_rescale: float = 0.0, guidance_interval: tuple[float, float] | None = None,
+                dynamic_threshold: float | None = None, threshold_max: float | None = None,
                 return_intermediates: bool = False, init_image: Tensor | None = None, strength: float = 1.0,
                 mask: Tensor | None = None, resample: int = 1) -> SamplingOutput:
-        """init_image / strength / mask / resample (this project's; the reference has neither): see `_denoise_from_image`.  At their
-        defaults this is the reference's loop, call for call."""
+        """init_image / strength / mask / resample (this project's; the reference has neither): see `_denoise_from_image`.
+        guidance_rescale / guidance_interval (this project's): see `one_step_denoise`; validated here, before any device work.  At
+        their defaults this is the reference's loop, call for call."""
+        check_guidance(guidance_scale, guidance_rescale, guidance_interval, dynamic_threshold, threshold_max, flow=True)
+        guided = guidance_kwargs(guidance_rescale, guidance_interval, dynamic_threshold, threshold_max)
         cond = self._image_conditioning(model, model_inputs, data_shape, init_image, strength, mask, resample)
         if cond is not None:
             return self._denoise_from_image(model, model_inputs, cond, strength, resample, use_tqdm, clamp_x, guidance_scale,
-                                            sampler_args, return_intermediates)
+                                            sampler_args, return_intermediates, guided)
         p0 = next(model.parameters())
         if "x" not in model_inputs:
             assert data_shape is not None, "'data_shape' must be provided if 'x' is not in model_inputs"
@@ -176,7 +192,7 @@ class Flow(Diffusion):
         pairs = zip(self.timesteps[:-1], self.timesteps[1:])
         for t_curr, t_prev in tqdm(pairs, desc="generating image", total=self.steps, disable=not use_tqdm, leave=False):
             out = self.one_step_denoise(model, model_inputs, t_curr=t_curr, t_prev=t_prev, guidance_scale=guidance_scale,
-                                        sampler_args=sampler_args)
+                                        sampler_args=sampler_args, **guided)
             model_inputs["x"] = out["x_prev"]
             if keep:
                 xt.append(out["x_prev"])
@@ -192,7 +208,8 @@ class Flow(Diffusion):
         return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=0)  # std stacked on dim 0 (flow.py:520)
 
     def _denoise_from_image(self, model, model_inputs, cond, strength: float, resample: int, use_tqdm: bool, clamp_x: bool,
-                            guidance_scale: float, sampler_args: dict[str, Any], return_intermediates: bool) -> SamplingOutput:
+                            guidance_scale: float, sampler_args: dict[str, Any], return_intermediates: bool,
+                            guided: dict[str, Any] = {}) -> SamplingOutput:
         """Image-to-image (SDEdit, Meng et al. 2022) and inpainting (RePaint, Lugmayr et al. 2022) on the grid of `self.timesteps`.
 
         Start: k = strength_to_steps(steps, strength) steps are run, from index i0 = steps - k: x = (1 - t) init_image + t eps0 at
@@ -205,7 +222,7 @@ class Flow(Diffusion):
         marginal (1 - t_curr) x0 + t_curr eps.  The denoiser runs resample (k - 1) + 1 times (twice that where CFG makes two forwards).
         Intermediates: `xt` holds the starting x and each step's x_prev after the blend (of the last repeat); estimated_x0, xt_mean,
         xt_std and logprob are what the sampler returned, before the blend.  clamp_x clamps the final sample, as in the plain loop (the
-        known region too, where init_image leaves [-1, 1])."""
+        known region too, where init_image leaves [-1, 1]).  guided: the guided-sampling keywords of `one_step_denoise`."""
         init, eps0, m = cond
         k = strength_to_steps(self.steps, strength)
         i0 = self.steps - k
@@ -222,7 +239,7 @@ class Flow(Diffusion):
             repeats = resample if j + 1 < k else 1
             for r in range(repeats):
                 out = self.one_step_denoise(model, model_inputs, t_curr=t_curr, t_prev=t_prev, guidance_scale=guidance_scale,
-                                            sampler_args=sampler_args)
+                                            sampler_args=sampler_args, **guided)
                 if m is not None:  # in place: the sampler's x_prev is a fresh tensor
                     out["x_prev"] = ops.inpaint_blend(out["x_prev"], init, eps0, m, 1.0 - t_prev, t_prev, out=out["x_prev"])
                 model_inputs["x"] = out["x_prev"]

@@ -16,7 +16,8 @@ from torch import Tensor
 from ... import ops
 from ..samplers.common import StepResult
 from ..samplers.gaussian_diffusion import DDIM, DDPM
-from ..utils import SamplingOutput, f32_table, strength_to_steps, to_device
+from ..utils import (SamplingOutput, check_guidance, f32_table, guidance_kwargs, in_guidance_interval, strength_to_steps,
+                     to_device)
 from .diffusion import Diffusion, gd_head, hybrid_head, mse_head
 from .utils import space_timesteps
 
@@ -133,8 +134,27 @@ class GaussianDiffusion(Diffusion):
             return table[timesteps]
         return timesteps
 
+    def guidance_level(self, t: int) -> float:
+        """the noise level of the step at index t, as `guidance_interval` reads it: (tau + 1) / training_steps, tau the index the
+        denoiser is given (timestep_map[t] on a respaced chain, else t)"""
+        tau = self.timestep_map[t] if self.timestep_map else t
+        return (tau + 1) / self.training_steps
+
     def one_step_denoise(self, model, model_inputs, t: int, clamp_x: bool = False, guidance_scale: float = 0.0,
-                         sampler_args: dict[str, Any] = {}) -> StepResult:
+                         sampler_args: dict[str, Any] = {}, guidance_rescale: float = 0.0,
+                         guidance_interval: tuple[float, float] | None = None, dynamic_threshold: float | None = None,
+                         threshold_max: float | None = None) -> StepResult:
+        """guidance_rescale / guidance_interval / dynamic_threshold / threshold_max (this project's): CFG rescale and the dynamic
+        threshold reach the sampler as keywords; a step whose `guidance_level` lies outside the interval makes the one conditional
+        forward (no combine, no rescale; the threshold still applies)."""
+        if guidance_rescale or guidance_interval is not None or dynamic_threshold is not None or threshold_max is not None:
+            check_guidance(guidance_scale, guidance_rescale, guidance_interval, dynamic_threshold, threshold_max)
+            extra_args = {"guidance_rescale": guidance_rescale} if guidance_rescale else {}
+            if dynamic_threshold is not None:
+                extra_args.update(dynamic_threshold=dynamic_threshold, threshold_max=threshold_max)
+            sampler_args = {**sampler_args, **extra_args}
+            if not in_guidance_interval(guidance_interval, self.guidance_level(t)):
+                guidance_scale = 0.0
         device = next(model.parameters()).device
         timesteps = torch.full((model_inputs["x"].shape[0],), t, device=device, dtype=torch.int32)
         t_model = self._remap(timesteps)
@@ -230,14 +250,19 @@ class GaussianDiffusion(Diffusion):
     @torch.no_grad()
     def denoise(self, model, model_inputs, data_shape: tuple[int, ...] | None = None, use_tqdm: bool = True,
                 clamp_x: bool = False, guidance_scale: float = 0, sampler_args: dict[str, Any] = {},
+                guidance_rescale: float = 0.0, guidance_interval: tuple[float, float] | None = None,
+                dynamic_threshold: float | None = None, threshold_max: float | None = None,
                 return_intermediates: bool = False, init_image: Tensor | None = None, strength: float = 1.0,
                 mask: Tensor | None = None, resample: int = 1) -> SamplingOutput:
-        """init_image / strength / mask / resample (this project's; the reference has neither): see `_denoise_from_image`.  At their
-        defaults this is the reference's loop, call for call."""
+        """init_image / strength / mask / resample (this project's; the reference has neither): see `_denoise_from_image`.
+        guidance_rescale / guidance_interval / dynamic_threshold / threshold_max (this project's): see `one_step_denoise`; validated
+        here, before any device work.  At their defaults this is the reference's loop, call for call."""
+        check_guidance(guidance_scale, guidance_rescale, guidance_interval, dynamic_threshold, threshold_max)
+        guided = guidance_kwargs(guidance_rescale, guidance_interval, dynamic_threshold, threshold_max)
         cond = self._image_conditioning(model, model_inputs, data_shape, init_image, strength, mask, resample)
         if cond is not None:
             return self._denoise_from_image(model, model_inputs, cond, strength, resample, use_tqdm, clamp_x, guidance_scale,
-                                            sampler_args, return_intermediates)
+                                            sampler_args, return_intermediates, guided)
         if "x" not in model_inputs:
             assert data_shape is not None, "'data_shape' must be provided if 'x' is not in model_inputs"
             p0 = next(model.parameters())
@@ -251,7 +276,7 @@ class GaussianDiffusion(Diffusion):
         for t in tqdm(list(range(self.steps))[::-1], desc="generating image", total=self.steps, disable=not use_tqdm,
                       leave=False):
             out = self.one_step_denoise(model=model, model_inputs=model_inputs, t=t, clamp_x=clamp_x,
-                                        guidance_scale=guidance_scale, sampler_args=sampler_args)
+                                        guidance_scale=guidance_scale, sampler_args=sampler_args, **guided)
             model_inputs["x"] = out["x_prev"]
             if keep:
                 xt.append(out["x_prev"])
@@ -265,7 +290,8 @@ class GaussianDiffusion(Diffusion):
         return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=1)
 
     def _denoise_from_image(self, model, model_inputs, cond, strength: float, resample: int, use_tqdm: bool, clamp_x: bool,
-                            guidance_scale: float, sampler_args: dict[str, Any], return_intermediates: bool) -> SamplingOutput:
+                            guidance_scale: float, sampler_args: dict[str, Any], return_intermediates: bool,
+                            guided: dict[str, Any] = {}) -> SamplingOutput:
         """Image-to-image (SDEdit, Meng et al. 2022) and inpainting (RePaint, Lugmayr et al. 2022) on the (respaced) chain.
 
         Start: k = strength_to_steps(steps, strength) steps are run, t = k - 1 .. 0, from x = q(x_t | init_image) at t = k - 1 with
@@ -279,7 +305,8 @@ class GaussianDiffusion(Diffusion):
         level by x_t = sqrt(1 - betas[t]) x_prev + sqrt(betas[t]) randn.  The denoiser runs resample (k - 1) + 1 times (twice that
         where CFG makes two forwards).
         Intermediates: `xt` holds the starting x and each step's x_prev after the blend (of the last repeat); estimated_x0, xt_mean,
-        xt_std and logprob are what the sampler returned, before the blend."""
+        xt_std and logprob are what the sampler returned, before the blend.  guided: the guided-sampling keywords of
+        `one_step_denoise`."""
         init, eps0, m = cond
         k = strength_to_steps(self.steps, strength)
         B = init.shape[0]
@@ -294,7 +321,7 @@ class GaussianDiffusion(Diffusion):
             repeats = resample if t > 0 else 1
             for r in range(repeats):
                 out = self.one_step_denoise(model=model, model_inputs=model_inputs, t=t, clamp_x=clamp_x,
-                                            guidance_scale=guidance_scale, sampler_args=sampler_args)
+                                            guidance_scale=guidance_scale, sampler_args=sampler_args, **guided)
                 if m is not None:  # in place: the sampler's x_prev is a fresh tensor
                     xp = out["x_prev"]
                     if t > 0:

@@ -23,7 +23,8 @@ class DDIM(DDPM):
         return self._dev_tables[key], self._dev_tables[("ddim_c", device)]
 
     def step(self, model_prediction: Tensor, timesteps: Tensor, xt: Tensor, clamp_x: bool = False, eta: float = 0.0,
-             prediction_uncond: Tensor | None = None, guidance_scale: float = 0.0) -> StepResult:
+             prediction_uncond: Tensor | None = None, guidance_scale: float = 0.0, guidance_rescale: float = 0.0,
+             dynamic_threshold: float | None = None, threshold_max: float | None = None) -> StepResult:
         self._variance_tables()  # same var_type validation as DDPM._get_p_mean_var (ddim.py:89)
         tab, coefs = self._ddim_tables(xt.device)
         if self.learned_variance:  # the 2C prediction's variance half is discarded (ddim.py:89); the mean half is read in place
@@ -31,7 +32,13 @@ class DDIM(DDPM):
         noise = torch.randn_like(xt)  # ddim.py:63
         pred = model_prediction.float().contiguous()
         pu = None if prediction_uncond is None else prediction_uncond.float().contiguous()
-        if self.mean_type == "v":
+        if guidance_rescale > 0 or dynamic_threshold is not None:  # this project's: see `DDPM._guided`
+            pred, pu, x, t, mul, thr = self._guided(model_prediction, prediction_uncond, guidance_scale, xt, timesteps, tab, coefs,
+                                                    guidance_rescale, dynamic_threshold, threshold_max)
+            xp, x0, mean, std, lp = ops.ddim_step_g(pred, pu, guidance_scale, mul, thr, x, noise, t, tab, coefs,
+                                                    _MEAN.index(self.mean_type), ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED),
+                                                    clamp_x, eta)
+        elif self.mean_type == "v":
             xp, x0, mean, std, lp = ops.ddim_step_v(pred, pu, guidance_scale, xt.float().contiguous(), noise,
                                                     timesteps.to(torch.int32).contiguous(), tab,
                                                     ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED), clamp_x, eta)

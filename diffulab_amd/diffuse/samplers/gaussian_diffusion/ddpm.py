@@ -9,7 +9,7 @@ import torch
 from torch import Tensor
 
 from .... import ops
-from ...utils import f32_table
+from ...utils import f32_table, quantile_position
 from ..common import Sampler, StepResult
 
 _MEAN = ("epsilon", "xstart", "xprev", "v")  # "v" (Salimans & Ho 2022) is this project's; the reference has the first three
@@ -73,9 +73,40 @@ class DDPM(GaussianSampler):
             self._dev_tables[key] = f32_table(t, device)
         return self._dev_tables[key]
 
+    def _guided(self, model_prediction: Tensor, prediction_uncond: Tensor | None, guidance_scale: float, xt: Tensor,
+                timesteps: Tensor, tab: Tensor, coefs: Tensor, guidance_rescale: float, dynamic_threshold: float | None,
+                threshold_max: float | None):
+        """the per-sample device scalars of a guided step, two launches that materialise nothing the size of the image:
+        cfg_mul, the CFG-rescale factor (Lin et al. 2023) of the combined prediction's mean half -- only where the step is guided;
+        x0_thr, the dynamic threshold (Saharia et al. 2022) of the x0 the step kernel will form from the same arguments.
+        -> (pred, pred_uncond, xt, t) in the form the kernels read, cfg_mul or None, x0_thr or None"""
+        pred = model_prediction.float().contiguous()
+        pu = None if prediction_uncond is None else prediction_uncond.float().contiguous()
+        x, t = xt.float().contiguous(), timesteps.to(torch.int32).contiguous()
+        halves = self.learned_variance
+        mul = ops.cfg_rescale_coef(pred, pu, guidance_scale, guidance_rescale, halves) if guidance_rescale > 0 and pu is not None else None
+        thr = None
+        if dynamic_threshold is not None:
+            k, f = quantile_position(dynamic_threshold, x.numel() // x.shape[0])
+            thr = ops.x0_threshold(pred, pu, guidance_scale, mul, x, t, tab, coefs, _MEAN.index(self.mean_type), k, f, threshold_max,
+                                   halves)
+        return pred, pu, x, t, mul, thr
+
     def step(self, model_prediction: Tensor, timesteps: Tensor, xt: Tensor, clamp_x: bool = False,
-             prediction_uncond: Tensor | None = None, guidance_scale: float = 0.0) -> StepResult:
+             prediction_uncond: Tensor | None = None, guidance_scale: float = 0.0, guidance_rescale: float = 0.0,
+             dynamic_threshold: float | None = None, threshold_max: float | None = None) -> StepResult:
+        """guidance_rescale / dynamic_threshold / threshold_max (this project's): see `_guided`.  At their defaults the call below is
+        what it was."""
         noise = torch.randn_like(xt)  # ddpm.py:302 (drawn for every t, masked at t == 0)
+        if guidance_rescale > 0 or dynamic_threshold is not None:
+            if self.learned_variance:
+                self._check_halves(model_prediction, xt)
+            tab = self._tables(xt.device)
+            pred, pu, x, t, mul, thr = self._guided(model_prediction, prediction_uncond, guidance_scale, xt, timesteps, tab, tab[2:4],
+                                                    guidance_rescale, dynamic_threshold, threshold_max)
+            xp, x0, mean, std, lp = ops.ddpm_step_g(pred, pu, guidance_scale, mul, thr, x, noise, t, tab, _MEAN.index(self.mean_type),
+                                                    ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED), clamp_x)
+            return StepResult(x_prev=xp, estimated_x0=x0, x_prev_mean=mean, x_prev_std=std, logprob=lp)
         if self.mean_type == "v":  # one entry point for [B, C] and [B, 2C] predictions; `_tables` follows var_type
             if self.learned_variance:
                 self._check_halves(model_prediction, xt)

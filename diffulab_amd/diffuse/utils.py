@@ -79,6 +79,69 @@ def check_image_conditioning(shape: tuple[int, ...] | None, init_image: Tensor |
     return True
 
 
+GUIDANCE_DEFAULTS = dict(guidance_rescale=0.0, guidance_interval=None, dynamic_threshold=None, threshold_max=None)
+
+
+def _number(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and v == v
+
+
+def check_guidance(guidance_scale: float, guidance_rescale: float = 0.0, guidance_interval=None, dynamic_threshold=None,
+                   threshold_max=None, flow: bool = False) -> bool:
+    """validate the guided-sampling arguments of `Diffuser.generate` / `Diffusion.denoise`: guidance_rescale (phi of CFG rescale, Lin et
+    al. 2023) in [0, 1]; guidance_interval (lo, hi) with 0 <= lo <= hi <= 1 (Kynkaanniemi et al. 2024); dynamic_threshold p in (0, 1]
+    (Saharia et al. 2022); threshold_max >= 1, the cap on the threshold.  Host checks only.  -> False when all four are at their
+    defaults (the plain sampling path), else True; a ValueError names the offending argument."""
+    if not _number(guidance_rescale) or not 0.0 <= guidance_rescale <= 1.0:
+        raise ValueError(f"guidance_rescale must be a number in [0, 1], got {guidance_rescale!r}")
+    if guidance_interval is not None:
+        ok = isinstance(guidance_interval, (tuple, list)) and len(guidance_interval) == 2 and all(_number(v) for v in guidance_interval)
+        if not ok or not 0.0 <= guidance_interval[0] <= guidance_interval[1] <= 1.0:
+            raise ValueError(f"guidance_interval must be (lo, hi) with 0 <= lo <= hi <= 1, got {guidance_interval!r}")
+    if dynamic_threshold is not None and (not _number(dynamic_threshold) or not 0.0 < dynamic_threshold <= 1.0):
+        raise ValueError(f"dynamic_threshold must be a number in (0, 1], got {dynamic_threshold!r}")
+    if threshold_max is not None:
+        if not _number(threshold_max) or not threshold_max >= 1.0:
+            raise ValueError(f"threshold_max must be a number >= 1, got {threshold_max!r}")
+        if dynamic_threshold is None:
+            raise ValueError("threshold_max needs dynamic_threshold: it caps the threshold that one computes")
+    if not guidance_scale > 0:
+        if guidance_rescale > 0:
+            raise ValueError(f"guidance_rescale={guidance_rescale} needs guidance_scale > 0: it rescales the guided prediction")
+        if guidance_interval is not None:
+            raise ValueError(f"guidance_interval={guidance_interval!r} needs guidance_scale > 0: it limits where guidance is applied")
+    if flow and dynamic_threshold is not None:
+        raise ValueError("dynamic_threshold is not available for flow samplers: the flow step has no per-step x0 clamp to replace "
+                         "(use a Gaussian-diffusion sampler, ddpm or ddim)")
+    return guidance_rescale > 0 or guidance_interval is not None or dynamic_threshold is not None
+
+
+def guidance_kwargs(guidance_rescale: float = 0.0, guidance_interval=None, dynamic_threshold=None, threshold_max=None) -> dict:
+    """the guided-sampling arguments that are not at their default, as keywords to pass on: a call with all four at their defaults
+    passes nothing and stays what it was"""
+    given = dict(guidance_rescale=guidance_rescale, guidance_interval=guidance_interval, dynamic_threshold=dynamic_threshold,
+                 threshold_max=threshold_max)
+    return {k: v for k, v in given.items() if v is not None and v != GUIDANCE_DEFAULTS[k]}
+
+
+def in_guidance_interval(guidance_interval, level: float) -> bool:
+    """is a step at noise level `level` (flow: t_curr; Gaussian diffusion: (training index + 1) / training steps) guided?  Both ends
+    are inclusive; None guides every step"""
+    return guidance_interval is None or guidance_interval[0] <= level <= guidance_interval[1]
+
+
+def quantile_position(p: float, n: int) -> tuple[int, float]:
+    """torch.quantile's `linear` position of the p-quantile among n sorted values, split for the kernels: pos = p (n - 1) in double,
+    k = floor(pos), f = float32(pos - k); the quantile is v[k] + f (v[min(k + 1, n - 1)] - v[k]).  Where the fraction rounds up to 1
+    in float32 the position moves to k + 1 with f = 0, which is the same value."""
+    pos = float(p) * (n - 1)
+    k = min(int(math.floor(pos)), n - 1)
+    f = float(torch.tensor(pos - k, dtype=torch.float64).float())
+    if f >= 1.0:
+        k, f = min(k + 1, n - 1), 0.0
+    return k, f
+
+
 class _PinnedRing:
     """pinned staging slots for small host -> device transfers (per-step timestep vectors): a pageable `.to(device)` blocks the host
     until the stream has drained everything queued before it, i.e. once per training step the host loses its whole lead over the GPU

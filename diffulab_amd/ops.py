@@ -20,7 +20,7 @@ from . import tuning
 BF16, F32 = 0, 1
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 LOSS_FLOW, LOSS_EPS = 0, 1
-MEAN_TYPES = {"epsilon": 0, "xstart": 1, "xprev": 2, "v": 3}  # "v": the gd_loss_* / *_step_v entry points only
+MEAN_TYPES = {"epsilon": 0, "xstart": 1, "xprev": 2, "v": 3}  # "v": the gd_loss_* / *_step_v / *_step_g / x0_threshold entry points only
 VAR_MODES = {"learned": 0, "learned_range": 1}
 VAR_FIXED = -1
 PATCH_CPP, PATCH_PPC = 0, 1
@@ -312,6 +312,95 @@ def ddim_step_v(pred, pred_uncond, guidance, xt, noise, t, tables, var_mode: int
         lp = torch.empty_like(xt) if eta > 0 else None
     _call("dl_ddim_step_v", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables), tables.shape[1],
           var_mode, int(clamp_x), float(eta), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
+    return xp, x0, mean, std, lp
+
+
+# guided sampling (CFG rescale, dynamic thresholding): per-sample coefficients that stay on the device, and the steps that read them
+def cfg_rescale_coef(pred: Tensor, pred_uncond: Tensor, guidance: float, phi: float, halves: bool = False,
+                     out: Tensor | None = None) -> Tensor:
+    """-> r f32 [B], the CFG-rescale factor of every sample (dl_cfg_rescale_coef).  halves: pred / pred_uncond are the [B, 2C, ...]
+    prediction of a learned-variance model; the mean half is read in place"""
+    B = pred.shape[0]
+    stride = pred.numel() // B
+    assert pred_uncond.numel() == pred.numel() and (not halves or stride % 2 == 0)
+    out = torch.empty(B, device=pred.device, dtype=torch.float32) if out is None else out
+    _call("dl_cfg_rescale_coef", _p(pred), _p(pred_uncond), float(guidance), float(phi), _p(out), B, stride // 2 if halves else stride,
+          stride, _s())
+    return out
+
+
+def abs_quantile_rows(x: Tensor, k: int, f: float, want_lohi: bool = False):
+    """x f32 [B, n] -> q f32 [B] = lo + f (hi - lo) over |x| per row, lo / hi the k-th and min(k + 1, n - 1)-th smallest (exact
+    selection, dl_abs_quantile_rows); with want_lohi also lohi f32 [B, 2]"""
+    assert x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous()
+    B, n = x.shape
+    q = torch.empty(B, device=x.device, dtype=torch.float32)
+    lohi = torch.empty(B, 2, device=x.device, dtype=torch.float32) if want_lohi else None
+    _call("dl_abs_quantile_rows", _p(x), int(k), float(f), _p(q), _p(lohi), B, n, _s())
+    return (q, lohi) if want_lohi else q
+
+
+def x0_threshold(pred, pred_uncond, guidance, cfg_mul, xt, t, tables, coefs, mean_type: int, k: int, f: float,
+                 threshold_max: float | None = None, halves: bool = False, want_lohi: bool = False):
+    """-> s f32 [B], the dynamic threshold min(max(quantile of |x0|, 1), threshold_max) of every sample, x0 as the `*_step_g` kernels
+    form it from the same arguments (dl_x0_threshold); tables: the step's own (rows 0, 1 are read); coefs f32 [2, T]: the posterior-mean
+    coefficients, needed for mean_type xprev only"""
+    B = xt.shape[0]
+    assert pred.numel() == (2 if halves else 1) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    s = torch.empty(B, device=xt.device, dtype=torch.float32)
+    lohi = torch.empty(B, 2, device=xt.device, dtype=torch.float32) if want_lohi else None
+    _call("dl_x0_threshold", _p(pred), _p(pred_uncond), float(guidance), _p(cfg_mul), _p(xt), _p(t), _p(tables), tables.shape[1],
+          mean_type, _p(coefs), int(k), float(f), float("inf") if threshold_max is None else float(threshold_max), _p(s), _p(lohi), B,
+          xt.numel() // B, pred.numel() // B, _s())
+    return (s, lohi) if want_lohi else s
+
+
+def euler_step_g(x: Tensor, v: Tensor, v_uncond: Tensor | None, guidance: float, cfg_mul: Tensor | None, t_curr: float, t_prev: float,
+                 want_x0: bool = True) -> tuple[Tensor, Tensor | None]:
+    B = x.shape[0]
+    xp = torch.empty_like(x)
+    x0 = torch.empty_like(x) if want_x0 else None
+    _call("dl_euler_step_g", _p(x), _p(v), _p(v_uncond), float(guidance), _p(cfg_mul), float(t_curr), float(t_curr - t_prev), _p(xp),
+          _p(x0), B, x.numel() // B, _s())
+    return xp, x0
+
+
+def euler_maruyama_step_g(x, v, v_uncond, guidance, cfg_mul, noise, x_prev_in, t_curr, t_prev, sigma):
+    B = x.shape[0]
+    dt = t_curr - t_prev
+    std = sigma * dt**0.5
+    xp, mean, x0, lp = (torch.empty_like(x) for _ in range(4))
+    _call("dl_euler_maruyama_step_g", _p(x), _p(v), _p(v_uncond), float(guidance), _p(cfg_mul), _p(noise), _p(x_prev_in),
+          float(t_curr), float(dt), float(sigma), float(std), _p(xp), _p(mean), _p(x0), _p(lp), B, x.numel() // B, _s())
+    return xp, mean, x0, lp, std
+
+
+def ddpm_step_g(pred, pred_uncond, guidance, cfg_mul, x0_thr, xt, noise, t, tables, mean_type: int, var_mode: int, clamp_x: bool,
+                out=None):
+    """any mean_type (v included) and var_mode: VAR_FIXED with pred [B, C, ...] and ddpm_step's tables, or a learned mode with
+    [B, 2C, ...] and ddpm_step_lv's; cfg_mul / x0_thr f32 [B] or None"""
+    B = xt.shape[0]
+    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    xp, x0, mean, std, lp = (torch.empty_like(xt) for _ in range(5)) if out is None else out
+    _call("dl_ddpm_step_g", _p(pred), _p(pred_uncond), float(guidance), _p(cfg_mul), _p(x0_thr), _p(xt), _p(noise), _p(t), _p(tables),
+          tables.shape[1], mean_type, var_mode, int(clamp_x), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
+    return xp, x0, mean, std, lp
+
+
+def ddim_step_g(pred, pred_uncond, guidance, cfg_mul, x0_thr, xt, noise, t, tables, coefs, mean_type: int, var_mode: int,
+                clamp_x: bool, eta: float, out=None):
+    """as ddpm_step_g, with ddim_step's tables f32 [3, T] and coefs (needed for mean_type xprev only)"""
+    B = xt.shape[0]
+    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    if out is not None:
+        xp, x0, mean, std, lp = out
+    else:
+        xp, x0, mean = (torch.empty_like(xt) for _ in range(3))
+        std = torch.empty_like(xt) if eta > 0 else None
+        lp = torch.empty_like(xt) if eta > 0 else None
+    _call("dl_ddim_step_g", _p(pred), _p(pred_uncond), float(guidance), _p(cfg_mul), _p(x0_thr), _p(xt), _p(noise), _p(t), _p(tables),
+          tables.shape[1], mean_type, var_mode, _p(coefs), int(clamp_x), float(eta), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B,
+          xt.numel() // B, _s())
     return xp, x0, mean, std, lp
 
 

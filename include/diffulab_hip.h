@@ -33,7 +33,7 @@ enum { DL_OK = 0, DL_ERR_INVALID = -1, DL_ERR_LAUNCH = -2, DL_ERR_UNSUPPORTED = 
 enum { DL_BF16 = 0, DL_F32 = 1 };
 enum { DL_ACT_NONE = 0, DL_ACT_SILU = 1, DL_ACT_GELU = 2 };  /* GELU: exact erf form (nn.GELU default) */
 enum { DL_LOSS_FLOW = 0, DL_LOSS_EPS = 1 };                       /* target = a - b | target = a */
-enum { DL_MEAN_EPSILON = 0, DL_MEAN_XSTART = 1, DL_MEAN_XPREV = 2, DL_MEAN_V = 3 }; /* V: dl_gd_loss_*, dl_ddpm_step_v, dl_ddim_step_v only */
+enum { DL_MEAN_EPSILON = 0, DL_MEAN_XSTART = 1, DL_MEAN_XPREV = 2, DL_MEAN_V = 3 }; /* V: dl_gd_loss_*, the _v and _g steps, dl_x0_threshold only */
 enum { DL_VAR_LEARNED = 0, DL_VAR_LEARNED_RANGE = 1 };            /* lv = v | lv = w log beta_t + (1 - w) log post_var_t, w = (v + 1) / 2 */
 enum { DL_VAR_FIXED = -1 };                                       /* [B, chw] prediction, variances from the tables (dl_gd_loss_*, the _v steps) */
 enum { DL_PATCH_CPP = 0, DL_PATCH_PPC = 1 };                      /* feature order (c p1 p2) | (p1 p2 c) */
@@ -186,6 +186,56 @@ DL_API int dl_ddim_step_v(const float* pred, const float* pred_uncond, float gui
                           const int32_t* t, const float* tables, int32_t T, int var_mode, int clamp_x, float eta, float* x_prev,
                           float* x0_est, float* mean, float* std, float* logprob, int64_t batch, int64_t chw,
                           dl_stream_t stream);
+/* Guided sampling, which the reference does not have beyond the plain combine u + g (c - u).  Three controls of Diffuser.generate:
+ *   CFG rescale          Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed" (2023), sec. 3.4, eq. 15-16
+ *   dynamic thresholding Saharia et al., "Photorealistic Text-to-Image Diffusion Models with Deep Language Understanding" (2022), sec. 2.3
+ *   guidance interval    Kynkaanniemi et al., "Applying Guidance in a Limited Interval Improves Sample and Distribution Quality in
+ *                        Diffusion Models" (2024): host logic in the loops, no kernel
+ * dl_cfg_rescale_coef (Lin et al. eq. 15-16): r[b] = 1 - phi + phi sqrt(S_c / S_o) with S_c = sum (c - mean c)^2 and S_o the same of
+ * o = u + g (c - u), over the chw elements of sample b (the ratio of standard deviations: the n - 1 cancels); r = 1 where S_o == 0.
+ * pred / pred_uncond are [batch, sample_stride] with sample_stride chw, or 2 chw for a learned-variance prediction whose mean half
+ * is read in place.  Centred (mean first, then the deviations), double accumulators, a fixed reduction order (two runs give the same
+ * bits), no floating-point atomics, no host synchronisation.  phi in [0, 1]. */
+DL_API int dl_cfg_rescale_coef(const float* pred, const float* pred_uncond, float guidance, float phi, float* r, int64_t batch,
+                               int64_t chw, int64_t sample_stride, dl_stream_t stream);
+/* The quantile of |x| along the rows of x [batch, n] by torch.quantile's `linear` rule with the position already split on the host
+ * (pos = p (n - 1) = k + f, 0 <= k < n, 0 <= f < 1): q[b] = lo + f (hi - lo), lo the k-th smallest |x[b, :]| (0-based), hi the
+ * min(k + 1, n - 1)-th.  The selection is exact (a radix select on the bit patterns of the non-negative keys, -0.0 as +0.0); inputs
+ * are finite.  lohi f32 [batch, 2] (may be NULL) receives (lo, hi).  This is the plain form of dl_x0_threshold's selection. */
+DL_API int dl_abs_quantile_rows(const float* x, int64_t k, float f, float* q, float* lohi, int64_t batch, int64_t n,
+                                dl_stream_t stream);
+/* Dynamic thresholding (Saharia et al. 2022, sec. 2.3): s[b] = min(max(a_b, 1), threshold_max), a_b the quantile above of
+ * |x0| over sample b, where x0 = x_start_from(mean_type, cfg_mul[b] (u + g (c - u)), xt) is recomputed per element exactly as the _g
+ * steps below form it (ddpm.py:99-154 and the v form), so no x0 tensor is materialised.  pred_uncond NULL: no combine; cfg_mul NULL:
+ * no rescale.  tables: f32 [>= 2][T], rows sqrt_ab, ab (the first two rows of any step's table); coefs f32 [2][T] =
+ * posterior_mean_coef1, coef2, read for DL_MEAN_XPREV only (else may be NULL).  sample_stride as above.  threshold_max >= 1,
+ * INFINITY for none.  lohi f32 [batch, 2] (may be NULL) receives the two order statistics. */
+DL_API int dl_x0_threshold(const float* pred, const float* pred_uncond, float guidance, const float* cfg_mul, const float* xt,
+                           const int32_t* t, const float* tables, int32_t T, int mean_type, const float* coefs, int64_t k, float f,
+                           float threshold_max, float* s, float* lohi, int64_t batch, int64_t chw, int64_t sample_stride,
+                           dl_stream_t stream);
+/* The four sampler steps above with the two per-sample arrays of guided sampling, both f32 [batch], either may be NULL:
+ *   cfg_mul  the combined prediction (its mean half; a variance half keeps the plain combine) is multiplied by cfg_mul[b]
+ *            (Lin et al. eq. 16 with r from dl_cfg_rescale_coef)
+ *   x0_thr   x0 = clamp(x0, -s, s) / s with s = x0_thr[b], wherever the step uses x0: posterior mean, DDIM eps, x0_est (Saharia et
+ *            al. sec. 2.3); applied before clamp_x.  The flow steps have no per-step x0 clamp and take cfg_mul only.
+ * dl_ddpm_step_g / dl_ddim_step_g take every mean_type (DL_MEAN_V included) and var_mode (DL_VAR_FIXED: [B, chw] prediction and the
+ * tables of dl_ddpm_step / dl_ddim_step; learned: [B, 2 chw] read in place and the tables of the _lv entry points).  With both arrays
+ * NULL the launch is the one the entry point without _g makes. */
+DL_API int dl_euler_step_g(const float* x, const float* v, const float* v_uncond, float guidance, const float* cfg_mul,
+                           float t_curr, float dt, float* x_prev, float* x0_est, int64_t batch, int64_t chw, dl_stream_t stream);
+DL_API int dl_euler_maruyama_step_g(const float* x, const float* v, const float* v_uncond, float guidance, const float* cfg_mul,
+                                    const float* noise, const float* x_prev_in, float t_curr, float dt, float sigma, float std,
+                                    float* x_prev, float* mean, float* x0_est, float* logprob, int64_t batch, int64_t chw,
+                                    dl_stream_t stream);
+DL_API int dl_ddpm_step_g(const float* pred, const float* pred_uncond, float guidance, const float* cfg_mul, const float* x0_thr,
+                          const float* xt, const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
+                          int var_mode, int clamp_x, float* x_prev, float* x0_est, float* mean, float* std, float* logprob,
+                          int64_t batch, int64_t chw, dl_stream_t stream);
+DL_API int dl_ddim_step_g(const float* pred, const float* pred_uncond, float guidance, const float* cfg_mul, const float* x0_thr,
+                          const float* xt, const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
+                          int var_mode, const float* ddpm_coefs, int clamp_x, float eta, float* x_prev, float* x0_est, float* mean,
+                          float* std, float* logprob, int64_t batch, int64_t chw, dl_stream_t stream);
 /* Image-to-image and inpainting, which the reference does not have: the known region of Meng et al., "SDEdit: Guided Image Synthesis
  * and Editing with Stochastic Differential Equations" (2022) and Lugmayr et al., "RePaint: Inpainting using Denoising Diffusion
  * Probabilistic Models" (2022), for the loops of diffuse/modelizations/flow.py (Flow.denoise) and gaussian_diffusion.py

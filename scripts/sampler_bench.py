@@ -20,6 +20,7 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--guidance", type=float, default=4.0)
+    ap.add_argument("--guidance-rescale", type=float, default=0.0, help="CFG rescale phi; 0 leaves the plain call")
     a = ap.parse_args()
     dev = "cuda"
     torch.manual_seed(0)
@@ -28,8 +29,10 @@ def main() -> None:
     d = Diffuser(m, sampling_method="euler", model_type="rectified_flow", n_steps=a.steps)
     y = torch.randint(0, 1000, (a.batch,), device=dev)
 
+    extra = {"guidance_rescale": a.guidance_rescale} if a.guidance_rescale > 0 else {}
+
     def run():
-        return d.generate({"y": y}, data_shape=(a.batch, 4, 32, 32), use_tqdm=False, guidance_scale=a.guidance)["x"]
+        return d.generate({"y": y}, data_shape=(a.batch, 4, 32, 32), use_tqdm=False, guidance_scale=a.guidance, **extra)["x"]
 
     run()
     torch.cuda.synchronize()
@@ -39,7 +42,7 @@ def main() -> None:
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.reps
     nfwd = a.steps * (2 if a.guidance > 0 else 1)
-    print(json.dumps({"workload": f"DiT-S/2 {a.steps}-step Euler sampling, CFG {a.guidance}", "batch": a.batch, "s_per_batch": dt,
+    print(json.dumps({"workload": f"DiT-S/2 {a.steps}-step Euler sampling, CFG {a.guidance}", "batch": a.batch, "guidance_rescale": a.guidance_rescale, "s_per_batch": dt,
                       "images_per_s": a.batch / dt, "ms_per_forward": dt / nfwd * 1e3, "finite": bool(torch.isfinite(out).all())}))
 
 

@@ -1,6 +1,13 @@
 // Stem / head / conditioning kernels of the DiT: patchify (im2row), unpatchify, sinusoidal timestep
 // embedding, label-embedding combine, small reductions.  All tiny and HBM/latency bound.
 #include "common.h"
+#include "aux_paths.h"
+#include <atomic>
+
+// the path code of the last auxiliary dispatch (aux_paths.h): one relaxed host-side store per call, read by the tests
+static std::atomic<int> g_last_aux_path{DL_AUX_PATH_NONE};
+void dl_note_aux_path(int path) { g_last_aux_path.store(path, std::memory_order_relaxed); }
+extern "C" __attribute__((visibility("default"))) int dl_lab_last_aux_path() { return g_last_aux_path.load(std::memory_order_relaxed); }
 
 // ---------------------------------------------------------------- patchify: x f32 [B,C,H,W] -> tok bf16 [M, ld]
 // one thread per (token, feature); feature order CPP: f = (c*p + p1)*p + p2 ; PPC: f = (p1*p + p2)*C + c
@@ -281,16 +288,18 @@ static int heads_launch(const void* src, int64_t ld, void* dst, int64_t B, int64
 extern "C" int dl_heads_split_rope(const void* src, int64_t ld, void* dst, int64_t B, int64_t H, int64_t n_src, int64_t n_dst,
                                    int64_t n_off, const float* cs, const float* sn, int64_t rot, dl_stream_t stream) {
   DL_CHECK_ARG(src && dst && B > 0 && H > 0 && n_src > 0 && n_off >= 0 && n_off + n_src <= n_dst && ld % 8 == 0 && ld >= H * 64 &&
-                   rot % 8 == 0 && rot <= 64 && ((cs == nullptr) == (sn == nullptr)),
-               "dl_heads_split_rope: bad args");
+                   rot % 8 == 0 && rot <= 64 && ((cs == nullptr) == (sn == nullptr)) &&
+                   (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)cs | (uintptr_t)sn) & 15) == 0,
+               "dl_heads_split_rope: bad args (16-byte aligned src, dst, cs, sn)");
   return heads_launch(src, ld, dst, B, H, n_src, n_dst, n_off, cs, sn, rot, 0, 0, stream);
 }
 extern "C" int dl_heads_merge_rope_bwd(const void* dst_grad, void* src_grad, int64_t ld, int64_t B, int64_t H, int64_t n_src,
                                        int64_t n_dst, int64_t n_off, const float* cs, const float* sn, int64_t rot,
                                        int accumulate, dl_stream_t stream) {
   DL_CHECK_ARG(dst_grad && src_grad && B > 0 && H > 0 && n_src > 0 && n_off >= 0 && n_off + n_src <= n_dst && ld % 8 == 0 &&
-                   ld >= H * 64 && rot % 8 == 0 && rot <= 64 && ((cs == nullptr) == (sn == nullptr)),
-               "dl_heads_merge_rope_bwd: bad args");
+                   ld >= H * 64 && rot % 8 == 0 && rot <= 64 && ((cs == nullptr) == (sn == nullptr)) &&
+                   (((uintptr_t)dst_grad | (uintptr_t)src_grad | (uintptr_t)cs | (uintptr_t)sn) & 15) == 0,
+               "dl_heads_merge_rope_bwd: bad args (16-byte aligned gradients, cs, sn)");
   return heads_launch(src_grad, ld, (void*)dst_grad, B, H, n_src, n_dst, n_off, cs, sn, rot, 1, accumulate, stream);
 }
 
@@ -378,6 +387,9 @@ __global__ __launch_bounds__(256) void colsum_vec_k(const bf16_t* __restrict__ x
 static bool colsum_vec_ok(const void* x, int dtype, int64_t ld, int64_t C) {
   return dtype != DL_F32 && C % 8 == 0 && ld % 8 == 0 && (((uintptr_t)x) & 15) == 0;
 }
+static int colsum_path(const void* x, int dtype, int64_t ld, int64_t C) {
+  return colsum_vec_ok(x, dtype, ld, C) ? AUX_COLSUM_BF16_VEC : dtype == DL_F32 ? AUX_COLSUM_F32 : AUX_COLSUM_BF16_SCALAR;
+}
 static int colsum_vl(int64_t C) {
   int vl = 1;
   while (vl * 8 < C && vl < 64) vl <<= 1;
@@ -394,6 +406,7 @@ extern "C" int dl_colsum_det(const void* x, int dtype, int64_t ld, float* out, i
   const int rps = (int)((R + slabs - 1) / slabs);
   slabs = (int)((R + rps - 1) / rps);
   dim3 grid(cdiv(C, 64), slabs);
+  dl_note_aux_path(colsum_path(x, dtype, ld, C));
   if (colsum_vec_ok(x, dtype, ld, C)) {
     const int vl = colsum_vl(C);
     hipLaunchKernelGGL(colsum_vec_k<false>, dim3(cdiv(C, vl * 8), slabs), 256, 0, (hipStream_t)stream, (const bf16_t*)x, ld, scratch, R,
@@ -411,6 +424,7 @@ extern "C" int dl_colsum(const void* x, int dtype, int64_t ld, float* out, int64
   if (slabs > 512) slabs = 512;
   const int rps = (int)((R + slabs - 1) / slabs);
   dim3 grid(cdiv(C, 64), slabs);
+  dl_note_aux_path(colsum_path(x, dtype, ld, C));
   if (colsum_vec_ok(x, dtype, ld, C)) {
     const int vl = colsum_vl(C);
     hipLaunchKernelGGL(colsum_vec_k<true>, dim3(cdiv(C, vl * 8), slabs), 256, 0, (hipStream_t)stream, (const bf16_t*)x, ld, out, R, (int)C,
@@ -482,6 +496,7 @@ extern "C" int dl_colsum_batched(const dl_colsum_desc_t* desc, int n, dl_stream_
   DL_CHECK_ARG(desc && n > 0, "dl_colsum_batched: bad args");
   ColsumBatch a;
   int k = 0, blocks = 0;
+  bool fell_back = false;
   auto flush = [&]() {
     if (k == 0) return;
     a.n = k;
@@ -496,6 +511,7 @@ extern "C" int dl_colsum_batched(const dl_colsum_desc_t* desc, int n, dl_stream_
     if (!colsum_vec_ok(d.x, DL_BF16, d.ld, d.C)) {  // (odd widths / alignment: the scalar kernel, a launch of its own)
       const int rc = dl_colsum(d.x, DL_BF16, d.ld, d.out, d.R, d.C, stream);
       if (rc != DL_OK) return rc;
+      fell_back = true;
       continue;
     }
     int slabs = (int)((d.R + 255) / 256);
@@ -515,6 +531,7 @@ extern "C" int dl_colsum_batched(const dl_colsum_desc_t* desc, int n, dl_stream_
     if (++k == DL_COLSUM_BATCH_MAX) flush();
   }
   flush();
+  dl_note_aux_path(fell_back ? AUX_COLSUM_BATCHED_FALLBACK : AUX_COLSUM_BATCHED);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
@@ -538,7 +555,7 @@ __global__ void reduce_rows_k(float* __restrict__ partial, float* __restrict__ o
   if (rl == 0 && c < n) unsafeAtomicAdd(&out[c], red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl]);
 }
 extern "C" int dl_reduce_rows_f32(float* partial, float* out, int64_t G, int64_t n, int clear_partial, dl_stream_t stream) {
-  DL_CHECK_ARG(partial && out && G > 0 && n > 0, "dl_reduce_rows_f32: bad args");
+  DL_CHECK_ARG(partial && out && G > 0 && n > 0 && (G + 63) / 64 < 65536, "dl_reduce_rows_f32: bad args (at most 65535 slices of 64 rows)");
   hipLaunchKernelGGL(reduce_rows_k, dim3(cdiv(n, 64), cdiv(G, 64)), 256, 0, (hipStream_t)stream, partial, out, (int)G, n,
                      clear_partial);
   DL_LAUNCH_CHECK();
@@ -571,7 +588,7 @@ __global__ __launch_bounds__(256) void reduce_rows_batched_k(const float* __rest
 }
 extern "C" int dl_reduce_rows_batched_f32(const float* partial, int64_t partial_stride, float* out, int64_t out_stride, int64_t K,
                                           int64_t G, int64_t n, dl_stream_t stream) {
-  DL_CHECK_ARG(partial && out && K > 0 && G > 0 && n > 0, "dl_reduce_rows_batched_f32: bad args");
+  DL_CHECK_ARG(partial && out && K > 0 && K < 65536 && G > 0 && n > 0, "dl_reduce_rows_batched_f32: bad args (K < 65536)");
   hipLaunchKernelGGL(reduce_rows_batched_k, dim3(cdiv(n, 16), (unsigned)K), 256, 0, (hipStream_t)stream, partial, partial_stride, out,
                      out_stride, (int)G, n);
   DL_LAUNCH_CHECK();
@@ -634,8 +651,8 @@ __global__ __launch_bounds__(256) void cosine_rows_bwd_k(const bf16_t* __restric
 extern "C" int dl_cosine_rows_fwd(const void* p, int64_t ldp, const float* d, int64_t ldd, float* cosv, float* pn2, float* dn2,
                                   int64_t M, int64_t E, float eps, dl_stream_t stream) {
   DL_CHECK_ARG(p && d && cosv && pn2 && dn2 && M > 0 && E > 0 && E % 8 == 0 && ldp % 8 == 0 && ldd % 4 == 0 &&
-                   (((uintptr_t)p | (uintptr_t)d) & 15) == 0,
-               "dl_cosine_rows_fwd: bad args");
+                   ldp >= E && ldd >= E && (((uintptr_t)p | (uintptr_t)d) & 15) == 0,
+               "dl_cosine_rows_fwd: bad args (E, ld % 8, ld >= E, 16-byte aligned p, d)");
   int grid = cdiv(M, 4);
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(cosine_rows_fwd_k, grid, 256, 0, (hipStream_t)stream, (const bf16_t*)p, ldp, d, ldd, cosv, pn2, dn2, M, (int)E,
@@ -646,8 +663,9 @@ extern "C" int dl_cosine_rows_fwd(const void* p, int64_t ldp, const float* d, in
 extern "C" int dl_cosine_rows_bwd(const void* p, int64_t ldp, const float* d, int64_t ldd, const float* cosv, const float* pn2,
                                   const float* dn2, float gscale, const float* gscale_dev, void* dp, int64_t lddp, int64_t M,
                                   int64_t E, float eps, dl_stream_t stream) {
-  DL_CHECK_ARG(p && d && cosv && pn2 && dn2 && dp && M > 0 && E > 0 && E % 8 == 0 && ldp % 8 == 0 && lddp % 8 == 0 && ldd % 4 == 0,
-               "dl_cosine_rows_bwd: bad args");
+  DL_CHECK_ARG(p && d && cosv && pn2 && dn2 && dp && M > 0 && E > 0 && E % 8 == 0 && ldp % 8 == 0 && lddp % 8 == 0 && ldd % 4 == 0 &&
+                   ldp >= E && ldd >= E && lddp >= E && (((uintptr_t)p | (uintptr_t)d | (uintptr_t)dp) & 15) == 0,
+               "dl_cosine_rows_bwd: bad args (E, ld % 8, ld >= E, 16-byte aligned p, d, dp)");
   int grid = cdiv(M, 4);
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(cosine_rows_bwd_k, grid, 256, 0, (hipStream_t)stream, (const bf16_t*)p, ldp, d, ldd, cosv, pn2, dn2, gscale,

@@ -220,7 +220,8 @@ extern "C" int dl_ddt_cond_fwd(const void* enc, int64_t ld, const float* temb, i
 }
 extern "C" int dl_ddt_cond_bwd(const void* dsz, const void* enc, int64_t ld, const float* temb, int64_t ld_t, int64_t B, int64_t N,
                                int64_t D, void* denc, float* dtemb, dl_stream_t stream) {
-  DL_CHECK_ARG(dsz && enc && temb && denc && dtemb && B > 0 && N > 0 && D > 0 && ld >= D && ld_t >= D, "dl_ddt_cond_bwd: bad args");
+  DL_CHECK_ARG(dsz && enc && temb && denc && dtemb && B > 0 && B < 65536 && N > 0 && D > 0 && ld >= D && ld_t >= D,
+               "dl_ddt_cond_bwd: bad args (B < 65536)");
   const int rows_per_wg = 16;
   hipLaunchKernelGGL(ddt_cond_bwd_k, dim3(cdiv(N, rows_per_wg), (unsigned)B), 256, 0, (hipStream_t)stream, (const bf16_t*)dsz,
                      (const bf16_t*)enc, ld, temb, ld_t, (int)N, (bf16_t*)denc, dtemb, (int)D, rows_per_wg);

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "attn_paths.h"
 #include "gn_paths.h"
+#include "aux_paths.h"
 #include <atomic>
 
 static inline int grid_for(int64_t n, int threads = 256, int cap = 4096) {
@@ -955,7 +956,9 @@ extern "C" int dl_im2col3x3(const void* x, int64_t ldx, void* cols, int64_t B, i
                             int64_t ld, dl_stream_t stream) {
   DL_CHECK_ARG(x && cols && B > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && rows >= B * H * W && ld >= 9 * C && ld % 8 == 0,
                "dl_im2col3x3: bad args");
-  if (C % 8 == 0 && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0)
+  const bool vec = C % 8 == 0 && ldx % 8 == 0 && ((uintptr_t)x & 15) == 0;
+  dl_note_aux_path(vec ? AUX_IM2COL_VEC : AUX_IM2COL_SCALAR);
+  if (vec)
     hipLaunchKernelGGL(im2col3x3_k, grid_for(rows * ld / 8), 256, 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)cols,
                        (int)B, (int)H, (int)W, (int)C, rows, ld);
   else
@@ -1009,11 +1012,13 @@ extern "C" int dl_cast_conv3x3_weight(const float* w, int64_t Co, int64_t Ci, vo
                                       dl_stream_t stream) {
   DL_CHECK_ARG(w && wf && wd && Co > 0 && Ci > 0 && ldf >= 9 * Ci && ldd >= 9 * Co, "dl_cast_conv3x3_weight: bad args");
   if (Co % CW_T == 0 && Ci % CW_T == 0 && ldf == 9 * Ci && ldd == 9 * Co && Co / CW_T <= 65535) {
+    dl_note_aux_path(AUX_CAST_CONV_TILED);
     hipLaunchKernelGGL(cast_conv3x3_tiled_k, dim3((unsigned)(Ci / CW_T), (unsigned)(Co / CW_T)), 256, 0, (hipStream_t)stream, w, (int)Co,
                        (int)Ci, (bf16_t*)wf, ldf, (bf16_t*)wd, ldd);
     DL_LAUNCH_CHECK();
     return DL_OK;
   }
+  dl_note_aux_path(AUX_CAST_CONV_DIRECT);
   hipLaunchKernelGGL(cast_conv3x3_k, grid_for(Co * ldf + Ci * ldd), 256, 0, (hipStream_t)stream, w, (int)Co, (int)Ci, (bf16_t*)wf,
                      ldf, (bf16_t*)wd, ldd);
   DL_LAUNCH_CHECK();
@@ -1154,11 +1159,13 @@ extern "C" int dl_conv3x3_wgrad_fold_batched(const dl_fold_conv_desc_t* desc_dev
 extern "C" int dl_conv3x3_wgrad_fold(const float* g, int64_t ldg, float* dw, int64_t Co, int64_t Ci, dl_stream_t stream) {
   DL_CHECK_ARG(g && dw && Co > 0 && Ci > 0 && ldg >= Co, "dl_conv3x3_wgrad_fold: bad args");
   if (Co % CW_T == 0 && Ci % CW_T == 0 && Co / CW_T <= 65535) {
+    dl_note_aux_path(AUX_FOLD_TILED);
     hipLaunchKernelGGL(conv3x3_wgrad_fold_tiled_k, dim3((unsigned)(Ci / CW_T), (unsigned)(Co / CW_T)), 256, 0, (hipStream_t)stream, g, ldg, dw,
                        (int)Co, (int)Ci);
     DL_LAUNCH_CHECK();
     return DL_OK;
   }
+  dl_note_aux_path(AUX_FOLD_DIRECT);
   hipLaunchKernelGGL(conv3x3_wgrad_fold_k, grid_for(Co * Ci * 9), 256, 0, (hipStream_t)stream, g, ldg, dw, (int)Co, (int)Ci);
   DL_LAUNCH_CHECK();
   return DL_OK;
@@ -1242,6 +1249,7 @@ extern "C" int dl_resample2x2_pair(const void* x0, void* out0, const void* x1, v
                                    float scale, int expand, dl_stream_t stream) {
   DL_CHECK_ARG(x0 && out0 && (x1 == nullptr) == (out1 == nullptr) && B > 0 && Hs > 0 && Ws > 0 && C > 0, "dl_resample2x2_pair: bad args");
   const bool vec = C % 8 == 0 && (((uintptr_t)x0 | (uintptr_t)out0 | (uintptr_t)x1 | (uintptr_t)out1) & 15) == 0;
+  dl_note_aux_path(!vec ? AUX_RESAMPLE_SCALAR : x1 ? AUX_RESAMPLE_VEC_PAIR : AUX_RESAMPLE_VEC_SINGLE);
   if (!vec) {
     for (int k = 0; k < (x1 ? 2 : 1); ++k) {
       const int rc = expand ? dl_expand2x2(k ? x1 : x0, k ? out1 : out0, B, Hs, Ws, C, scale, stream)
@@ -1286,14 +1294,16 @@ __global__ void stuff2x2_k(const bf16_t* __restrict__ dy, bf16_t* __restrict__ o
   }
 }
 extern "C" int dl_pick2x2(const void* x, void* out, int64_t B, int64_t Ho, int64_t Wo, int64_t C, dl_stream_t stream) {
-  DL_CHECK_ARG(x && out && B > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 8 == 0, "dl_pick2x2: bad args (C % 8)");
+  DL_CHECK_ARG(x && out && B > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 8 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0,
+               "dl_pick2x2: bad args (C % 8, 16-byte aligned)");
   hipLaunchKernelGGL(pick2x2_k, grid_for(B * Ho * Wo * C / 8), 256, 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)out, (int)B,
                      (int)Ho, (int)Wo, (int)(C / 8));
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
 extern "C" int dl_stuff2x2(const void* dy, void* out, int64_t B, int64_t Hi, int64_t Wi, int64_t C, dl_stream_t stream) {
-  DL_CHECK_ARG(dy && out && B > 0 && Hi > 0 && Wi > 0 && C > 0 && C % 8 == 0, "dl_stuff2x2: bad args (C % 8)");
+  DL_CHECK_ARG(dy && out && B > 0 && Hi > 0 && Wi > 0 && C > 0 && C % 8 == 0 && (((uintptr_t)dy | (uintptr_t)out) & 15) == 0,
+               "dl_stuff2x2: bad args (C % 8, 16-byte aligned)");
   hipLaunchKernelGGL(stuff2x2_k, grid_for(B * 4 * Hi * Wi * C / 8), 256, 0, (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)out,
                      (int)B, (int)Hi, (int)Wi, (int)(C / 8));
   DL_LAUNCH_CHECK();
@@ -1340,14 +1350,17 @@ __global__ __launch_bounds__(256) void rowbias_bwd_k(const bf16_t* __restrict__ 
   }
 }
 extern "C" int dl_rowbias_add(const void* x, const void* e, int64_t lde, void* out, int64_t B, int64_t HW, int64_t C, dl_stream_t stream) {
-  DL_CHECK_ARG(x && e && out && B > 0 && HW > 0 && C > 0 && C % 8 == 0 && lde % 8 == 0, "dl_rowbias_add: bad args (C, lde % 8)");
+  DL_CHECK_ARG(x && e && out && B > 0 && HW > 0 && C > 0 && C % 8 == 0 && lde % 8 == 0 && lde >= C &&
+                   (((uintptr_t)x | (uintptr_t)e | (uintptr_t)out) & 15) == 0,
+               "dl_rowbias_add: bad args (C, lde % 8, lde >= C, 16-byte aligned)");
   hipLaunchKernelGGL(rowbias_add_k, grid_for(B * HW * C / 8), 256, 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)e, lde,
                      (bf16_t*)out, (int)B, (int)HW, (int)(C / 8));
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
 extern "C" int dl_rowbias_bwd(const void* dy, void* de, int64_t lde, int64_t B, int64_t HW, int64_t C, dl_stream_t stream) {
-  DL_CHECK_ARG(dy && de && B > 0 && B < 65536 && HW > 0 && C > 0 && C % 8 == 0, "dl_rowbias_bwd: bad args (C % 8)");
+  DL_CHECK_ARG(dy && de && B > 0 && B < 65536 && HW > 0 && C > 0 && C % 8 == 0 && lde >= C && ((uintptr_t)dy & 15) == 0,
+               "dl_rowbias_bwd: bad args (C % 8, lde >= C, 16-byte aligned dy)");
   hipLaunchKernelGGL(rowbias_bwd_k, dim3((unsigned)((C + 63) / 64), (unsigned)B), 256, 0, (hipStream_t)stream, (const bf16_t*)dy,
                      (bf16_t*)de, lde, (int)HW, (int)C);
   DL_LAUNCH_CHECK();

@@ -12,6 +12,10 @@
 //     sinf / cosf  [0, 1000]   timestep embedding: t f with t <= 1000, f <= 1
 //     sqrtf  [2^-40, 2^40]     var + eps, mean square + eps
 //     1 / x  [2^-40, 2^40],  x / y with the same y and x = three fixed mantissas
+// The fast __expf (one v_exp_f32 of x log2 e: dgelu_f of csrc/common.h, ddt_cond_bwd_k of csrc/tokens.hip) is swept over [-88, 0] and,
+// for the bounds of tests/bf16_aux_bounds.py, over [-4, 4], [-8, 8] and [-16, 16]; beside the ulp error its ABSOLUTE error over
+// [-88, 0] (results in (0, 1]) is printed in units of 2^-24: its relative error grows with |x| (the rounded product x log2 e) and
+// passes the 8-ulp cap, the absolute one does not grow.
 // The error of a result r against the fp64 value v is |r - v| / ulp(v), ulp(v) = 2^(floor(log2 |v|) - 23), |v| clamped below at
 // 2^-126 (results under the normal range count in units of the smallest normal's ulp).
 #include <hip/hip_runtime.h>
@@ -23,8 +27,9 @@
 #include <cstring>
 #include <vector>
 
-enum Fn { FN_EXP, FN_ERF, FN_SIN, FN_COS, FN_SQRT, FN_RCP, FN_DIV, FN_COUNT };
-static const char* kNames[FN_COUNT] = {"expf", "erff", "sinf", "cosf", "sqrtf", "1.0f / x", "x / y"};
+enum Fn { FN_EXP, FN_ERF, FN_SIN, FN_COS, FN_SQRT, FN_RCP, FN_DIV, FN_FEXP, FN_FEXP4, FN_FEXP8, FN_FEXP16, FN_FEXP_ABS, FN_COUNT };
+static const char* kNames[FN_COUNT] = {"expf", "erff", "sinf", "cosf", "sqrtf", "1.0f / x", "x / y", "__expf [-88, 0]", "__expf [-4, 4]",
+                                       "__expf [-8, 8]", "__expf [-16, 16]", "__expf [-88, 0] abs / 2^-24"};
 
 __device__ double ulp_err(float r, double v) {
   double a = fabs(v);
@@ -50,6 +55,11 @@ __global__ void sweep_k(int fn, uint32_t bits0, uint32_t bits1, uint32_t stride,
       case FN_COS: e = ulp_err(cosf(x), cos((double)x)); break;
       case FN_SQRT: e = ulp_err(sqrtf(x), sqrt((double)x)); break;
       case FN_RCP: e = ulp_err(1.0f / x, 1.0 / (double)x); break;
+      case FN_FEXP:
+      case FN_FEXP4:
+      case FN_FEXP8:
+      case FN_FEXP16: e = ulp_err(__expf(x), exp((double)x)); break;
+      case FN_FEXP_ABS: e = fabs((double)__expf(x) - exp((double)x)) * 0x1p24; break;
       case FN_DIV: {
         const float n[3] = {1.2345678f, 1.9999999f, 1.0000001f};
         for (int k = 0; k < 3; ++k) {
@@ -81,6 +91,9 @@ int main(int argc, char** argv) {
       {FN_EXP, 0x1p-30f, 88.f, 0},   {FN_EXP, 0x1p-30f, 104.f, 1}, {FN_ERF, 0x1p-30f, 24.f, 0},  {FN_ERF, 0x1p-30f, 24.f, 1},
       {FN_SIN, 0x1p-30f, 1000.f, 0}, {FN_COS, 0x1p-30f, 1000.f, 0}, {FN_SQRT, 0x1p-40f, 0x1p40f, 0},
       {FN_RCP, 0x1p-40f, 0x1p40f, 0}, {FN_DIV, 0x1p-40f, 0x1p40f, 0}, {FN_DIV, 0x1p-40f, 0x1p40f, 1},
+      {FN_FEXP, 0x1p-30f, 88.f, 1}, {FN_FEXP_ABS, 0x1p-30f, 88.f, 1},
+      {FN_FEXP4, 0x1p-30f, 4.f, 0}, {FN_FEXP4, 0x1p-30f, 4.f, 1}, {FN_FEXP8, 0x1p-30f, 8.f, 0}, {FN_FEXP8, 0x1p-30f, 8.f, 1},
+      {FN_FEXP16, 0x1p-30f, 16.f, 0}, {FN_FEXP16, 0x1p-30f, 16.f, 1},
   };
   const int blocks = 2048, threads = 256, total = blocks * threads;
   double* d_w;
@@ -113,7 +126,7 @@ int main(int argc, char** argv) {
   printf("stride %u\n", stride);
   for (int f = 0; f < FN_COUNT; ++f) {
     const int chosen = (int)ceil(2.0 * best[f] - 1e-9);
-    printf("%-9s max %.4f ulp at x = %.9g (%llu arguments)  ->  allowance %d ulp%s\n", kNames[f], best[f], besta[f],
+    printf("%-28s max %.4f ulp at x = %.9g (%llu arguments)  ->  allowance %d ulp%s\n", kNames[f], best[f], besta[f],
            (unsigned long long)count[f], chosen, chosen > 8 ? "  ABOVE THE 8-ULP CAP" : "");
   }
   (void)hipFree(d_w);

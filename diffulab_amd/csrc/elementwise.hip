@@ -303,6 +303,56 @@ extern "C" int dl_euler_step_g(const float* x, const float* v, const float* v_un
   return DL_OK;
 }
 
+// variable-step Adams-Bashforth 2 on v in t (this project's).  HIST false is euler_step_k's body, expression for expression, plus the
+// store of the combined v that the next step reads as its history.
+template <bool GD, bool HIST>
+__global__ void ab2_step_k(const float* __restrict__ x, const float* __restrict__ v, const float* __restrict__ vu,
+                           const float* __restrict__ vl, float g, float t_curr, float dt, float w, float* __restrict__ xp,
+                           float* __restrict__ x0, float* __restrict__ vo, const FlowTail<GD> tail) {
+  const int64_t n = tail.n;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float vv = v[i];
+    if (vu) {
+      const float u = vu[i];
+      vv = u + g * (vv - u);
+    }
+    if constexpr (GD) {
+      if (tail.mul) vv *= tail.mul[i / tail.chw];
+    }
+    const float xi = x[i];
+    if constexpr (HIST) {
+      const float d = (1.0f + w) * vv - w * vl[i];
+      xp[i] = xi - d * dt;
+    } else {
+      xp[i] = xi - vv * dt;
+    }
+    if (x0) x0[i] = xi - vv * t_curr;
+    vo[i] = vv;
+  }
+}
+extern "C" int dl_ab2_step(const float* x, const float* v, const float* v_uncond, float guidance, const float* cfg_mul,
+                           const float* v_last, float t_curr, float dt, float w, float* x_prev, float* x0_est, float* v_out,
+                           int64_t batch, int64_t chw, dl_stream_t stream) {
+  DL_CHECK_ARG(x && v && x_prev && v_out && batch > 0 && chw > 0, "dl_ab2_step: bad args");
+  DL_CHECK_ARG(v_out != v && v_out != v_uncond && v_out != v_last && v_out != x, "dl_ab2_step: v_out aliases an input");
+  DL_CHECK_ARG(!v_last || (w == w && w - w == 0.0f), "dl_ab2_step: w %g is not finite", (double)w);
+  const int64_t n = batch * chw;
+  const FlowTail<true> on{n, cfg_mul, chw};
+  const FlowTail<false> off{n};
+#define AB2(G, H, TAIL)                                                                                                          \
+  hipLaunchKernelGGL((ab2_step_k<G, H>), ew_grid(n), 256, 0, (hipStream_t)stream, x, v, v_uncond, v_last, guidance, t_curr, dt, w, \
+                     x_prev, x0_est, v_out, TAIL)
+  if (v_last) {
+    if (cfg_mul) AB2(true, true, on); else AB2(false, true, off);
+  } else {
+    if (cfg_mul) AB2(true, false, on); else AB2(false, false, off);
+  }
+#undef AB2
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
 template <bool GD>
 __global__ void em_step_k(const float* __restrict__ x, const float* __restrict__ v, const float* __restrict__ vu,
                           float g, const float* __restrict__ noise, const float* __restrict__ xpin, float t_curr,
@@ -495,7 +545,29 @@ extern "C" int dl_ddpm_step_lv(const float* pred, const float* pred_uncond, floa
   return DL_OK;
 }
 
+// x0 of element i as the DDIM-family steps form it: CFG combine, cfg_mul, x_start_from, x0_thr, clamp_x, in that order (the same f32
+// expression X0Key evaluates for dl_x0_threshold).  Shared by ddim_step_k and dpmpp_2m_step_k.
 // HALVES: pred / pu are [B, 2 chw] and the step reads the mean half in place (learned variances, which DDIM discards: ddim.py:89)
+template <bool HALVES, bool GD>
+__device__ __forceinline__ float ddim_x0(int64_t i, int64_t chw, const float* __restrict__ pred, const float* __restrict__ pu, float g,
+                                         float x, int mean_type, float sab, float ab, float c1, float c2, int clamp_x,
+                                         const GaussTail<GD>& tail) {
+  const int64_t pi = HALVES ? i + (i / chw) * chw : i;
+  float o = pred[pi];
+  if (pu) {
+    const float u = pu[pi];
+    o = u + g * (o - u);
+  }
+  if constexpr (GD) {
+    if (tail.mul) o *= tail.mul[i / chw];
+  }
+  float x0 = x_start_from(mean_type, o, x, sab, ab, c1, c2);
+  if constexpr (GD) {
+    if (tail.thr) x0 = threshold_x0(x0, tail.thr[i / chw]);
+  }
+  if (clamp_x) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+  return x0;
+}
 template <bool HALVES, bool GD>
 __global__ void ddim_step_k(const float* __restrict__ pred, const float* __restrict__ pu, float g,
                             const float* __restrict__ xt, const float* __restrict__ noise,
@@ -510,21 +582,8 @@ __global__ void ddim_step_k(const float* __restrict__ pred, const float* __restr
     const int32_t ti = t[i / chw];
     const float sab = tab[ti], ab = tab[T + ti], abp = tab[2 * T + ti];
     const float c1 = coefs ? coefs[ti] : 1.0f, c2 = coefs ? coefs[T + ti] : 0.0f;
-    const int64_t pi = HALVES ? i + (i / chw) * chw : i;
-    float o = pred[pi];
-    if (pu) {
-      const float u = pu[pi];
-      o = u + g * (o - u);
-    }
-    if constexpr (GD) {
-      if (tail.mul) o *= tail.mul[i / chw];
-    }
     const float x = xt[i];
-    float x0 = x_start_from(mean_type, o, x, sab, ab, c1, c2);
-    if constexpr (GD) {
-      if (tail.thr) x0 = threshold_x0(x0, tail.thr[i / chw]);
-    }
-    if (clamp_x) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float x0 = ddim_x0<HALVES, GD>(i, chw, pred, pu, g, x, mean_type, sab, ab, c1, c2, clamp_x, tail);
     const float eps = ((1.0f / sab) * x - x0) / sqrtf(1.0f / ab - 1.0f);  // ddpm.py:324-326
     const float sigma = eta * sqrtf((1.0f - abp) / (1.0f - ab)) * sqrtf(1.0f - ab / abp);
     const float m = x0 * sqrtf(abp) + sqrtf(1.0f - abp - sigma * sigma) * eps;
@@ -667,6 +726,65 @@ extern "C" int dl_ddim_step_g(const float* pred, const float* pred_uncond, float
     if (gd) DDIM_G(true, true, on); else DDIM_G(true, false, off);
   }
 #undef DDIM_G
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// DPM-Solver++(2M) (Lu et al. 2022) in the data-prediction form: x_prev = a x_t + b x0_t + c x0_last, the three coefficients formed
+// on the host in fp64 (first or second order, see the header).  x0_t is ddim_x0, so dl_x0_threshold on the same arguments thresholds
+// the x0 this step uses.  A zero a drops its term (the final step: x_prev is x0_t bit for bit, whatever x_t holds); HIST false reads
+// no x0_last.
+template <bool HALVES, bool GD, bool HIST>
+__global__ void dpmpp_2m_step_k(const float* __restrict__ pred, const float* __restrict__ pu, float g,
+                                const float* __restrict__ xt, const float* __restrict__ xl, const int32_t* __restrict__ t,
+                                const float* __restrict__ tab, int32_t T, int mean_type, int clamp_x, float a, float b, float c,
+                                float* __restrict__ xp, float* __restrict__ x0o, int64_t n, const GaussTail<GD> tail) {
+  const int64_t chw = tail.chw;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int32_t ti = t[i / chw];
+    const float sab = tab[ti], ab = tab[T + ti];
+    const float x = xt[i];
+    const float x0 = ddim_x0<HALVES, GD>(i, chw, pred, pu, g, x, mean_type, sab, ab, 1.0f, 0.0f, clamp_x, tail);
+    float r = b * x0;
+    if (a != 0.0f) r += a * x;
+    if constexpr (HIST) r += c * xl[i];
+    xp[i] = r;
+    x0o[i] = x0;
+  }
+}
+extern "C" int dl_dpmpp_2m_step(const float* pred, const float* pred_uncond, float guidance, const float* cfg_mul, const float* x0_thr,
+                                const float* xt, const float* x0_last, const int32_t* t, const float* tables, int32_t T, int mean_type,
+                                int var_mode, int clamp_x, float a, float b, float c, float* x_prev, float* x0_est, int64_t batch,
+                                int64_t chw, dl_stream_t stream) {
+  DL_CHECK_ARG(pred && xt && t && tables && x_prev && x0_est && batch > 0 && chw > 0 && T > 0, "dl_dpmpp_2m_step: bad args");
+  DL_CHECK_ARG(mean_type == DL_MEAN_EPSILON || mean_type == DL_MEAN_XSTART || mean_type == DL_MEAN_V,
+               "dl_dpmpp_2m_step: mean_type %d (a posterior-mean output has no place in an ODE solver)", mean_type);
+  DL_CHECK_ARG(var_mode == DL_VAR_FIXED || var_mode == DL_VAR_LEARNED || var_mode == DL_VAR_LEARNED_RANGE,
+               "dl_dpmpp_2m_step: var_mode %d", var_mode);
+  DL_CHECK_ARG(a - a == 0.0f && b - b == 0.0f && c - c == 0.0f, "dl_dpmpp_2m_step: coefficients (%g, %g, %g) are not finite", (double)a,
+               (double)b, (double)c);
+  DL_CHECK_ARG(x0_last || c == 0.0f, "dl_dpmpp_2m_step: c != 0 needs x0_last");
+  DL_CHECK_ARG(x0_est != x0_last && x_prev != x0_last && x_prev != x0_est, "dl_dpmpp_2m_step: an output aliases x0_last or the other");
+  const int64_t n = batch * chw;
+  if (c == 0.0f) x0_last = nullptr;  // (a first-order step reads no history)
+  const bool gd = cfg_mul || x0_thr;
+  const GaussTail<true> on{chw, cfg_mul, x0_thr};
+  const GaussTail<false> off{chw};
+#define DPMPP(H, G, HIST, TAIL)                                                                                                      \
+  hipLaunchKernelGGL((dpmpp_2m_step_k<H, G, HIST>), ew_grid(n), 256, 0, (hipStream_t)stream, pred, pred_uncond, guidance, xt, x0_last, \
+                     t, tables, T, mean_type, clamp_x, a, b, c, x_prev, x0_est, n, TAIL)
+#define DPMPP_H(H)                                                              \
+  do {                                                                          \
+    if (x0_last) {                                                              \
+      if (gd) DPMPP(H, true, true, on); else DPMPP(H, false, true, off);        \
+    } else {                                                                    \
+      if (gd) DPMPP(H, true, false, on); else DPMPP(H, false, false, off);      \
+    }                                                                           \
+  } while (0)
+  if (var_mode == DL_VAR_FIXED) DPMPP_H(false); else DPMPP_H(true);
+#undef DPMPP_H
+#undef DPMPP
   DL_LAUNCH_CHECK();
   return DL_OK;
 }

@@ -17,7 +17,7 @@ from torch import Tensor
 
 from ... import ops
 from ..samplers.common import StepResult
-from ..samplers.flow import Euler, EulerMaruyama
+from ..samplers.flow import AB2, Euler, EulerMaruyama
 from ..utils import (SamplingOutput, check_guidance, flow_renoise_coefs, guidance_kwargs, in_guidance_interval, strength_to_steps,
                      to_device)
 from .diffusion import Diffusion, mse_head
@@ -44,7 +44,7 @@ class _XToV(torch.autograd.Function):
 
 
 class Flow(Diffusion):
-    sampler_registry = {"euler": Euler, "euler_maruyama": EulerMaruyama}
+    sampler_registry = {"euler": Euler, "euler_maruyama": EulerMaruyama, "ab2": AB2}  # "ab2" (second order, multistep) is this project's
 
     def __init__(self, n_steps: int = 50, sampling_method: str = "euler", schedule: str = "linear",
                  latent_diffusion: bool = False, logits_normal: bool = False, shift: float | None = None,
@@ -190,6 +190,7 @@ class Flow(Diffusion):
         stds: list[Tensor] = []
         lps: list[Tensor] = []
         pairs = zip(self.timesteps[:-1], self.timesteps[1:])
+        self.sampler.reset()
         for t_curr, t_prev in tqdm(pairs, desc="generating image", total=self.steps, disable=not use_tqdm, leave=False):
             out = self.one_step_denoise(model, model_inputs, t_curr=t_curr, t_prev=t_prev, guidance_scale=guidance_scale,
                                         sampler_args=sampler_args, **guided)
@@ -203,6 +204,7 @@ class Flow(Diffusion):
                     stds.append(out["x_prev_std"])
                 if "logprob" in out:
                     lps.append(out["logprob"])
+        self.sampler.reset()  # (a multistep sampler lets go of its image-sized history tensor)
         if clamp_x:
             model_inputs["x"] = model_inputs["x"].clamp(-1, 1)
         return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=0)  # std stacked on dim 0 (flow.py:520)
@@ -235,6 +237,7 @@ class Flow(Diffusion):
         stds: list[Tensor] = []
         lps: list[Tensor] = []
         pairs = list(zip(self.timesteps[i0:-1], self.timesteps[i0 + 1:]))
+        self.sampler.reset()
         for j, (t_curr, t_prev) in enumerate(tqdm(pairs, desc="generating image", total=k, disable=not use_tqdm, leave=False)):
             repeats = resample if j + 1 < k else 1
             for r in range(repeats):
@@ -248,6 +251,7 @@ class Flow(Diffusion):
                     model_inputs["x"] = ops.inpaint_blend(None, out["x_prev"], torch.randn_like(out["x_prev"]), None, a, s)
             if keep:
                 self._record(out, xt, x0s, means, stds, lps)
+        self.sampler.reset()  # (a multistep sampler lets go of its image-sized history tensor)
         if clamp_x:
             model_inputs["x"] = model_inputs["x"].clamp(-1, 1)
         return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=0)

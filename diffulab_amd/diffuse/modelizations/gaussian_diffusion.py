@@ -15,7 +15,7 @@ from torch import Tensor
 
 from ... import ops
 from ..samplers.common import StepResult
-from ..samplers.gaussian_diffusion import DDIM, DDPM
+from ..samplers.gaussian_diffusion import DDIM, DDPM, DPMSolverPP2M
 from ..utils import (SamplingOutput, check_guidance, f32_table, guidance_kwargs, in_guidance_interval, strength_to_steps,
                      to_device)
 from .diffusion import Diffusion, gd_head, hybrid_head, mse_head
@@ -48,13 +48,13 @@ def min_snr_weights(alphas_bar: Tensor, target: str, gamma: float = 5.0) -> Tens
 
 
 class GaussianDiffusion(Diffusion):
-    sampler_registry = {"ddpm": DDPM, "ddim": DDIM}
+    sampler_registry = {"ddpm": DDPM, "ddim": DDIM, "dpmpp_2m": DPMSolverPP2M}  # "dpmpp_2m" (second order, multistep) is this project's
 
     def __init__(self, n_steps: int = 1000, sampling_method: str = "ddpm", schedule: str = "linear",
                  latent_diffusion: bool = False, sampler_parameters: dict[str, Any] = {}, vlb_weight: float | None = None,
                  loss_target: str = "epsilon", loss_weighting: str | None = None, min_snr_gamma: float = 5.0) -> None:
-        if sampling_method not in ["ddpm", "ddim"]:
-            raise ValueError("sampling method must be one of ['ddpm', 'ddim']")
+        if sampling_method not in self.sampler_registry:
+            raise ValueError(f"sampling method must be one of {list(self.sampler_registry)}")
         if loss_target not in LOSS_TARGETS:
             raise ValueError(f"loss_target must be one of {list(LOSS_TARGETS)}")
         if loss_weighting not in LOSS_WEIGHTINGS:
@@ -96,6 +96,9 @@ class GaussianDiffusion(Diffusion):
         self.sampler.set_steps(betas)
 
     def set_steps(self, n_steps: int, schedule: str = "linear", section_counts: int | str | None = None) -> None:
+        """n_steps below the training chain respaces it.  Only "ddim" asks `space_timesteps` for the reference's ddim=True spacing,
+        which only ever accepts stride 1; "dpmpp_2m" (like "ddpm") gets ddim=False, so `set_steps(20)` on a 1000-step chain yields
+        the IDDPM-respaced 20-step chain, and the sampler's lambda table is that chain's."""
         if n_steps != self.training_steps:
             section_counts = section_counts or n_steps
         self.steps = n_steps
@@ -170,6 +173,8 @@ class GaussianDiffusion(Diffusion):
             if guidance_scale > 0:
                 extra = {"prediction_uncond": model(**{**model_inputs, "p": 1}, timesteps=t_model)["x"],
                          "guidance_scale": guidance_scale}
+        if self.sampler.multistep:  # its coefficients and its history rule are host arithmetic on the index: no device value is read
+            extra = {**extra, "step_index": t}
         return self.sampler.step(model_prediction=prediction, timesteps=timesteps, xt=model_inputs["x"], clamp_x=clamp_x,
                                  **extra, **sampler_args)
 
@@ -273,6 +278,7 @@ class GaussianDiffusion(Diffusion):
         means: list[Tensor] = []
         stds: list[Tensor] = []
         lps: list[Tensor] = []
+        self.sampler.reset()
         for t in tqdm(list(range(self.steps))[::-1], desc="generating image", total=self.steps, disable=not use_tqdm,
                       leave=False):
             out = self.one_step_denoise(model=model, model_inputs=model_inputs, t=t, clamp_x=clamp_x,
@@ -287,6 +293,7 @@ class GaussianDiffusion(Diffusion):
                     stds.append(out["x_prev_std"])
                 if "logprob" in out:
                     lps.append(out["logprob"])
+        self.sampler.reset()  # (a multistep sampler lets go of its image-sized history tensor)
         return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=1)
 
     def _denoise_from_image(self, model, model_inputs, cond, strength: float, resample: int, use_tqdm: bool, clamp_x: bool,
@@ -317,6 +324,7 @@ class GaussianDiffusion(Diffusion):
         means: list[Tensor] = []
         stds: list[Tensor] = []
         lps: list[Tensor] = []
+        self.sampler.reset()
         for t in tqdm(list(range(k))[::-1], desc="generating image", total=k, disable=not use_tqdm, leave=False):
             repeats = resample if t > 0 else 1
             for r in range(repeats):
@@ -336,4 +344,5 @@ class GaussianDiffusion(Diffusion):
                                                           (1.0 - beta) ** 0.5, beta**0.5)
             if keep:
                 self._record(out, xt, x0s, means, stds, lps)
+        self.sampler.reset()  # (a multistep sampler lets go of its image-sized history tensor)
         return self._pack(model_inputs["x"], xt, x0s, means, stds, lps, std_dim=1)

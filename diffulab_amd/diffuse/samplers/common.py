@@ -23,9 +23,14 @@ class StepResult(TypedDict):
 
 class Sampler(ABC):
     name: str
+    # a multistep sampler (this project's) keeps one tensor of the previous step; the Gaussian loop hands it the step's host index
+    multistep: bool = False
 
     def __init__(self) -> None:
         pass
+
+    def reset(self) -> None:
+        """forget the previous step (the loops call it once before they start); nothing to forget for a single-step sampler"""
 
     @abstractmethod
     def set_steps(self, *args: Any, **kwargs: Any) -> None: ...

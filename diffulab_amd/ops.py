@@ -404,6 +404,31 @@ def ddim_step_g(pred, pred_uncond, guidance, cfg_mul, x0_thr, xt, noise, t, tabl
     return xp, x0, mean, std, lp
 
 
+# second-order multistep samplers: one launch per step, the step coefficients formed on the host in double
+def ab2_step(x: Tensor, v: Tensor, v_uncond: Tensor | None, guidance: float, cfg_mul: Tensor | None, v_last: Tensor | None,
+             t_curr: float, t_prev: float, w: float = 0.0, out=None) -> tuple[Tensor, Tensor, Tensor]:
+    """-> (x_prev, x0_est, v_out); v_last None: the Euler step (w is not read).  v_out, the combined v, is the next step's v_last"""
+    B = x.shape[0]
+    assert v.numel() == x.numel() and (v_uncond is None or v_uncond.numel() == x.numel()) and (v_last is None or v_last.numel() == x.numel())
+    xp, x0, vo = (torch.empty_like(x) for _ in range(3)) if out is None else out
+    _call("dl_ab2_step", _p(x), _p(v), _p(v_uncond), float(guidance), _p(cfg_mul), _p(v_last), float(t_curr), float(t_curr - t_prev),
+          float(w), _p(xp), _p(x0), _p(vo), B, x.numel() // B, _s())
+    return xp, x0, vo
+
+
+def dpmpp_2m_step(pred, pred_uncond, guidance, cfg_mul, x0_thr, xt, x0_last, t, tables, mean_type: int, var_mode: int, clamp_x: bool,
+                  a: float, b: float, c: float, out=None) -> tuple[Tensor, Tensor]:
+    """-> (x_prev, x0_est) with x_prev = a xt + b x0 + c x0_last, x0 formed as ddim_step_g forms it (tables f32 [>= 2, T]: ddim_step's);
+    x0_last None needs c == 0; mean_type xprev is refused"""
+    B = xt.shape[0]
+    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    assert x0_last is None or x0_last.numel() == xt.numel()
+    xp, x0 = (torch.empty_like(xt) for _ in range(2)) if out is None else out
+    _call("dl_dpmpp_2m_step", _p(pred), _p(pred_uncond), float(guidance), _p(cfg_mul), _p(x0_thr), _p(xt), _p(x0_last), _p(t), _p(tables),
+          tables.shape[1], mean_type, var_mode, int(clamp_x), float(a), float(b), float(c), _p(xp), _p(x0), B, xt.numel() // B, _s())
+    return xp, x0
+
+
 def inpaint_blend(x: Tensor | None, ref: Tensor, noise: Tensor | None, mask: Tensor | None, a: float, b: float,
                   out: Tensor | None = None) -> Tensor:
     """known = a ref + b noise; with a mask ([B, 1, *spatial] or [B, C, *spatial], f32, 1 = generate) out = x where mask >= 1, known

@@ -236,6 +236,41 @@ DL_API int dl_ddim_step_g(const float* pred, const float* pred_uncond, float gui
                           const float* xt, const float* noise, const int32_t* t, const float* tables, int32_t T, int mean_type,
                           int var_mode, const float* ddpm_coefs, int clamp_x, float eta, float* x_prev, float* x0_est, float* mean,
                           float* std, float* logprob, int64_t batch, int64_t chw, dl_stream_t stream);
+/* Second-order multistep samplers, which the reference does not have (its four samplers are first order); both entry points are this
+ * project's.  Each costs one denoiser forward per step, keeps one tensor from the previous step, and takes its step coefficients as
+ * host scalars formed in double and rounded to f32.
+ *
+ * dl_ab2_step: variable-step Adams-Bashforth 2 on the rectified-flow velocity in t (Hairer, Norsett & Wanner, "Solving Ordinary
+ * Differential Equations I", sec. III.5).  With vc = cfg_mul[b] (v_uncond + g (v - v_uncond)) (v_uncond, cfg_mul may be NULL, as for
+ * dl_euler_step_g), dt = t_curr - t_prev and w = dt / (2 dt_last), dt_last the previous step's dt:
+ *   x_prev = x - dt ((1 + w) vc - w v_last)      v_last != NULL
+ *   x_prev = x - dt vc                           v_last == NULL: bit for bit dl_euler_step_g's x_prev and x0_est; w is not read
+ *   x0_est = x - vc t_curr                       (may be NULL)
+ *   v_out  = vc                                  always written: the next step's v_last.  It must not be one of the inputs.
+ * The flow path is not solved in log-SNR: log((1 - t) / t) is infinite at both ends of the grid, and first-order DPM-Solver++ on it is
+ * the Euler step anyway.
+ *
+ * dl_dpmpp_2m_step: DPM-Solver++(2M) (Lu et al., "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models",
+ * 2022, alg. 2) in the data-prediction form
+ *   x_prev = a x_t + b x0_t + c x0_last
+ * with alpha_i = sqrt(ab_i), sigma_i = sqrt(1 - ab_i), lambda_i = log(alpha_i / sigma_i) (index -1: ab = 1), h = lambda_{t-1} - lambda_t:
+ *   a = sigma_{t-1} / sigma_t
+ *   first order:   b = -alpha_{t-1} expm1(-h),                     c = 0      (the DDIM eta = 0 step)
+ *   second order:  b = -alpha_{t-1} expm1(-h) (1 + 1 / (2 r)),     c = alpha_{t-1} expm1(-h) / (2 r),   r = (lambda_t - lambda_{t+1}) / h
+ *   t == 0:        a = 0, b = 1, c = 0: x_prev is x0_t bit for bit (a zero a drops its term, so x_t is not read into x_prev)
+ * The caller takes the steps at t == 1 and t == 0 first order: the log-SNR step into index 0 is several times the steps before it and
+ * the extrapolation weight 1 / (2 r) then exceeds 1.  x0_t is formed exactly as dl_ddim_step_g forms it (CFG combine, cfg_mul, the
+ * mean_type's x0, x0_thr, clamp_x), so dl_x0_threshold on the same arguments thresholds the x0 this step uses; tables f32 [>= 2][T],
+ * rows sqrt_ab, ab (dl_ddim_step's table serves); var_mode as for dl_ddim_step_g (a learned mode reads the mean half of the [B, 2 chw]
+ * prediction in place).  DL_MEAN_XPREV is refused: a posterior-mean output has no place in an ODE solver.  x0_est (required) is x0_t
+ * after threshold and clamp, and the next step's x0_last; x0_last may be NULL when c == 0 and is not read then.  No noise is drawn. */
+DL_API int dl_ab2_step(const float* x, const float* v, const float* v_uncond, float guidance, const float* cfg_mul,
+                       const float* v_last, float t_curr, float dt, float w, float* x_prev, float* x0_est, float* v_out,
+                       int64_t batch, int64_t chw, dl_stream_t stream);
+DL_API int dl_dpmpp_2m_step(const float* pred, const float* pred_uncond, float guidance, const float* cfg_mul, const float* x0_thr,
+                            const float* xt, const float* x0_last, const int32_t* t, const float* tables, int32_t T, int mean_type,
+                            int var_mode, int clamp_x, float a, float b, float c, float* x_prev, float* x0_est, int64_t batch,
+                            int64_t chw, dl_stream_t stream);
 /* Image-to-image and inpainting, which the reference does not have: the known region of Meng et al., "SDEdit: Guided Image Synthesis
  * and Editing with Stochastic Differential Equations" (2022) and Lugmayr et al., "RePaint: Inpainting using Denoising Diffusion
  * Probabilistic Models" (2022), for the loops of diffuse/modelizations/flow.py (Flow.denoise) and gaussian_diffusion.py

@@ -1080,10 +1080,16 @@ __device__ __forceinline__ float approx_cdf(float z, float* dz) {  // 0.5 (1 + t
   if (dz) *dz = 0.5f * (1.0f - th * th) * VLB_SQRT_2_OVER_PI * (1.0f + 3.0f * 0.044715f * z * z);
   return 0.5f * (1.0f + th);
 }
-template <bool GRAD>
+// CLAMP (the evaluation kernel below): the predicted x0 is clamped to [-1, 1] before m_p is formed, and x0_pred, where given,
+// receives the x0 the term was formed from.  The training kernels take neither and keep their code.
+template <bool GRAD, bool CLAMP = false>
 __device__ __forceinline__ float vlb_elem(int mean_type, int var_mode, int32_t ti, float o, float v, float x0, float x, float sab,
-                                          float ab, float c1, float c2, float lv_q, float beta, float* dterm_dv) {
-  const float m_p = c1 * x_start_from(mean_type, o, x, sab, ab, c1, c2) + c2 * x;  // no clamp
+                                          float ab, float c1, float c2, float lv_q, float beta, float* dterm_dv,
+                                          float* x0_pred = nullptr) {
+  float xs = x_start_from(mean_type, o, x, sab, ab, c1, c2);
+  if (CLAMP) xs = fminf(fmaxf(xs, -1.0f), 1.0f);
+  if (x0_pred) *x0_pred = xs;
+  const float m_p = c1 * xs + c2 * x;  // no clamp unless CLAMP
   const float lv_p = learned_log_var(var_mode, v, lv_q, beta);
   float term, dlv;
   if (ti > 0) {  // KL(q(x_{t-1} | x_t, x_0) || p(x_{t-1} | x_t))
@@ -1354,6 +1360,142 @@ extern "C" int dl_gd_loss_bwd(const float* pred, const float* eps, const float* 
     if (weight) GD_BWD(false, true); else GD_BWD(false, false);
   }
 #undef GD_BWD
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// ---------------------------------------------------------------- variational bound per (sample, timestep): evaluation
+// calc_bpd_loop of Nichol & Dhariwal (2021): what vlb_partial_k sums over the whole batch, kept per row, for fixed variances too, next
+// to the two squared errors that loop reports.  A row's chw elements are cut into shares of MSE_ELEMS_PER_BLOCK, one workgroup each,
+// walked in the element-to-thread order of mse_partial_k; a row of one share is finished by its workgroup, a longer one leaves its
+// share sums in `partial` ([N][rows][nshare]) for rows_final_k, which adds them in share order.  No atomics: every run gives the
+// same bits.
+template <int N>
+struct RowOut {
+  float* out[N];
+  float scale[N];
+};
+template <int N>
+__device__ __forceinline__ void row_share_finish(float (&acc)[N], float (*red)[MSE_BLOCK / DL_WAVE], const RowOut<N>& ro,
+                                                 float* __restrict__ partial, int64_t rows, int64_t row, int64_t nshare,
+                                                 int64_t share) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) acc[k] = wave_sum(acc[k]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) red[k][threadIdx.x >> 6] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    const int k = threadIdx.x;
+    float s = 0.f;
+    for (int w = 0; w < MSE_BLOCK / DL_WAVE; ++w) s += red[k][w];
+    if (nshare == 1)
+      ro.out[k][row] = s * ro.scale[k];
+    else
+      partial[((int64_t)k * rows + row) * nshare + share] = s;
+  }
+}
+template <int N>
+__global__ void rows_final_k(const float* __restrict__ partial, const RowOut<N> ro, int64_t rows, int64_t nshare) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (array k, row)
+  if (idx >= N * rows) return;
+  const float* p = partial + idx * nshare;
+  float s = 0.f;
+  for (int64_t j = 0; j < nshare; ++j) s += p[j];
+  const int k = (int)(idx / rows);
+  ro.out[k][idx - k * rows] = s * ro.scale[k];
+}
+// LV: pred is [rows, 2 chw] and its variance half gives lv_p by var_mode; else pred is [rows, chw] and lv_p = tab row 5 (the sampler's
+// log_variance), handed to vlb_elem as a DL_VAR_LEARNED output.  lv_q = lvq[t] either way (the learned table's row 4 holds the same).
+template <bool LV, bool CLAMP>
+__global__ void vb_terms_k(const float* __restrict__ pred, const float* __restrict__ eps, const float* __restrict__ x0,
+                           const float* __restrict__ xt, const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T,
+                           const float* __restrict__ lvq, int mean_type, int var_mode, float* __restrict__ partial,
+                           const RowOut<3> ro, int64_t rows, int64_t chw, int64_t nshare) {
+  __shared__ float red[3][MSE_BLOCK / DL_WAVE];
+  const int64_t row = blockIdx.x / nshare, share = blockIdx.x - row * nshare;
+  const int32_t ti = t[row];
+  const float sab = tab[ti], ab = tab[T + ti], c1 = tab[2 * T + ti], c2 = tab[3 * T + ti], r5 = tab[5 * T + ti], lv_q = lvq[ti];
+  const float rsab = 1.0f / sab, rden = sqrtf(1.0f / ab - 1.0f);  // eps from x0 as ddim_step_k forms it (ddpm.py:324-326)
+  const float* pr = pred + row * (LV ? 2 : 1) * chw;
+  const int64_t ro0 = row * chw, base = share * MSE_ELEMS_PER_BLOCK;
+  float acc[3] = {0.f, 0.f, 0.f};  // bound term, (x0 - x0_pred)^2, (eps - eps_pred)^2
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int64_t i = base + (int64_t)j * MSE_BLOCK + threadIdx.x;
+    if (i < chw) {
+      const float o = pr[i], v = LV ? pr[chw + i] : r5;
+      const float xs = x0[ro0 + i], x = xt[ro0 + i];
+      float x0p;
+      acc[0] += vlb_elem<false, CLAMP>(mean_type, LV ? var_mode : DL_VAR_LEARNED, ti, o, v, xs, x, sab, ab, c1, c2, lv_q, r5, nullptr,
+                                       &x0p);
+      const float dx = xs - x0p, de = eps[ro0 + i] - (rsab * x - x0p) / rden;
+      acc[1] += dx * dx;
+      acc[2] += de * de;
+    }
+  }
+  row_share_finish<3>(acc, red, ro, partial, rows, row, nshare, share);
+}
+extern "C" int dl_vb_terms(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                           const float* tables, int32_t T, const float* lv_q, int mean_type, int var_mode, int clip_denoised,
+                           float* partial, float* vb, float* xstart_mse, float* mse, int64_t rows, int64_t chw, dl_stream_t stream) {
+  DL_CHECK_ARG(pred && eps && x0 && xt && t && tables && lv_q && rows > 0 && chw > 0 && T > 0, "dl_vb_terms: bad args");
+  DL_CHECK_ARG(vb && xstart_mse && mse, "dl_vb_terms: bad args (vb, xstart_mse, mse)");
+  DL_CHECK_ARG(mean_type >= DL_MEAN_EPSILON && mean_type <= DL_MEAN_V, "dl_vb_terms: mean_type %d", mean_type);
+  DL_CHECK_ARG(var_mode == DL_VAR_FIXED || var_mode == DL_VAR_LEARNED || var_mode == DL_VAR_LEARNED_RANGE, "dl_vb_terms: var_mode %d",
+               var_mode);
+  const int64_t nshare = dl_mse_loss_partials(chw);
+  DL_CHECK_ARG(nshare == 1 || partial, "dl_vb_terms: chw %lld needs partial (3 rows dl_mse_loss_partials(chw) floats)", (long long)chw);
+  DL_CHECK_ARG(rows <= INT32_MAX / nshare, "dl_vb_terms: rows %lld x %lld shares exceed the grid", (long long)rows, (long long)nshare);
+  const float inv = (float)(1.0 / (double)chw);
+  const RowOut<3> ro = {{vb, xstart_mse, mse}, {(float)(1.0 / ((double)chw * 0.6931471805599453)), inv, inv}};
+  const bool lv = var_mode != DL_VAR_FIXED;
+#define VB_TERMS(LV, CLAMP)                                                                                                    \
+  hipLaunchKernelGGL((vb_terms_k<LV, CLAMP>), (int)(rows * nshare), MSE_BLOCK, 0, (hipStream_t)stream, pred, eps, x0, xt, t, tables, \
+                     T, lv_q, mean_type, var_mode, partial, ro, rows, chw, nshare)
+  if (lv) {
+    if (clip_denoised) VB_TERMS(true, true); else VB_TERMS(true, false);
+  } else {
+    if (clip_denoised) VB_TERMS(false, true); else VB_TERMS(false, false);
+  }
+#undef VB_TERMS
+  if (nshare > 1)
+    hipLaunchKernelGGL(rows_final_k<3>, cdiv(3 * rows, 256), 256, 0, (hipStream_t)stream, partial, ro, rows, nshare);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+// KL(q(x_T | x0) || N(0, I)) per row in bits per dimension: the mean of 0.5 (-1 - l + exp(l) + ab x0^2), l = log(1 - ab)
+__global__ void prior_bpd_k(const float* __restrict__ x0, float ab, float l, float* __restrict__ partial, const RowOut<1> ro,
+                            int64_t rows, int64_t chw, int64_t nshare) {
+  __shared__ float red[1][MSE_BLOCK / DL_WAVE];
+  const int64_t row = blockIdx.x / nshare, share = blockIdx.x - row * nshare;
+  const int64_t ro0 = row * chw, base = share * MSE_ELEMS_PER_BLOCK;
+  const float c0 = expm1f(l) - l;  // -1 - l + exp(l) without its cancellation (l is about -4e-5 on the 1000-step linear chain)
+  float acc[1] = {0.f};
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int64_t i = base + (int64_t)j * MSE_BLOCK + threadIdx.x;
+    if (i < chw) {
+      const float x = x0[ro0 + i];
+      acc[0] += 0.5f * (c0 + ab * (x * x));
+    }
+  }
+  row_share_finish<1>(acc, red, ro, partial, rows, row, nshare, share);
+}
+extern "C" int dl_prior_bpd(const float* x0, float alphas_bar_last, float log_one_minus_ab, float* partial, float* out, int64_t batch,
+                            int64_t chw, dl_stream_t stream) {
+  DL_CHECK_ARG(x0 && out && batch > 0 && chw > 0, "dl_prior_bpd: bad args");
+  DL_CHECK_ARG(alphas_bar_last > 0.0f && alphas_bar_last < 1.0f && log_one_minus_ab < 0.0f,
+               "dl_prior_bpd: alphas_bar %g in (0, 1) and log(1 - alphas_bar) %g < 0 expected", (double)alphas_bar_last,
+               (double)log_one_minus_ab);
+  const int64_t nshare = dl_mse_loss_partials(chw);
+  DL_CHECK_ARG(nshare == 1 || partial, "dl_prior_bpd: chw %lld needs partial (batch dl_mse_loss_partials(chw) floats)", (long long)chw);
+  DL_CHECK_ARG(batch <= INT32_MAX / nshare, "dl_prior_bpd: batch %lld x %lld shares exceed the grid", (long long)batch, (long long)nshare);
+  const RowOut<1> ro = {{out}, {(float)(1.0 / ((double)chw * 0.6931471805599453))}};
+  hipLaunchKernelGGL(prior_bpd_k, (int)(batch * nshare), MSE_BLOCK, 0, (hipStream_t)stream, x0, alphas_bar_last, log_one_minus_ab,
+                     partial, ro, batch, chw, nshare);
+  if (nshare > 1) hipLaunchKernelGGL(rows_final_k<1>, cdiv(batch, 256), 256, 0, (hipStream_t)stream, partial, ro, batch, nshare);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }

@@ -48,6 +48,13 @@ class Diffuser:
         assert timesteps is not None, "timesteps must be provided for loss computation"
         return self.diffusion.compute_loss(self.denoiser, model_inputs, timesteps, noise, self.extra_losses, extra_args)
 
+    def evaluate_bpd(self, model_inputs, **kwargs: Any) -> dict[str, Tensor]:
+        """the variational bound on the negative log-likelihood of the clean data model_inputs["x"] in bits per dimension (this
+        project's; the reference has no likelihood evaluation): `GaussianDiffusion.calc_bpd_loop` on this denoiser, same keywords
+        (clip_denoised, t_chunk, noise, timesteps, use_tqdm) and same result dict.  Refused for rectified flow (no variational
+        bound) and for latent diffusion (the t = 0 term's 8-bit bins are pixel bins)."""
+        return self.diffusion.calc_bpd_loop(self.denoiser, model_inputs, **kwargs)
+
     def set_steps(self, n_steps: int, schedule: str = "linear", *args: Any, **kwargs: Any) -> None:
         self.diffusion.set_steps(n_steps, schedule=schedule, *args, **kwargs)
 

@@ -43,6 +43,11 @@ class _XToV(torch.autograd.Function):
         return ops.flow_x_to_v_bwd(dv.float().contiguous(), t), None, None
 
 
+NO_VARIATIONAL_BOUND = ("rectified flow has no variational bound: bits per dimension (calc_bpd_loop, evaluate_bpd, val_bpd_batches) "
+                        "are evaluated for model_type='gaussian_diffusion' only; the exact likelihood of a flow model is the ODE "
+                        "likelihood, which needs a divergence estimate through the network and is not built")
+
+
 class Flow(Diffusion):
     sampler_registry = {"euler": Euler, "euler_maruyama": EulerMaruyama, "ab2": AB2}  # "ab2" (second order, multistep) is this project's
 
@@ -152,6 +157,9 @@ class Flow(Diffusion):
 
     def compute_loss_grpo(self, *a: Any, **k: Any):
         raise NotImplementedError("GRPO fine-tuning (flow.py:317-380) is outside the MI355X hot-path scope (DESIGN.md)")
+
+    def calc_bpd_loop(self, *a: Any, **k: Any):
+        raise NotImplementedError(NO_VARIATIONAL_BOUND)
 
     def add_noise(self, x: Tensor, timesteps: Tensor, noise: Tensor | None = None) -> tuple[Tensor, Tensor]:
         x = x.float().contiguous()

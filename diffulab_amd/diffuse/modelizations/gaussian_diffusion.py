@@ -47,6 +47,30 @@ def min_snr_weights(alphas_bar: Tensor, target: str, gamma: float = 5.0) -> Tens
     raise ValueError(f"loss_weighting='min_snr' is defined for the targets epsilon, xstart and v, not for {target!r}")
 
 
+BPD_ROWS = 256  # rows (sample, timestep pairs) of one pass of calc_bpd_loop when t_chunk is left to it
+
+
+def plan_bpd_chunks(n_steps: int, batch: int, t_chunk: int | None = None, timesteps=None) -> list[list[int]]:
+    """the passes of `calc_bpd_loop` as lists of chain indices: the indices (all n_steps of the chain, or the subset `timesteps`)
+    from high to low, t_chunk per pass; t_chunk None takes the largest K with K * batch <= BPD_ROWS rows, at least 1.  Host
+    arithmetic only; a bad argument raises a ValueError that names it."""
+    if t_chunk is not None and (isinstance(t_chunk, bool) or int(t_chunk) != t_chunk or t_chunk < 1):
+        raise ValueError(f"t_chunk must be an integer >= 1 or None, got {t_chunk!r}")
+    if timesteps is None:
+        idx = list(range(n_steps))
+    else:
+        idx = [int(v) for v in (timesteps.tolist() if isinstance(timesteps, Tensor) else timesteps)]
+        if not idx:
+            raise ValueError("timesteps must name at least one index of the chain")
+        if min(idx) < 0 or max(idx) >= n_steps:
+            raise ValueError(f"timesteps must lie in [0, {n_steps}) on this chain, got {min(idx)} .. {max(idx)}")
+        if len(set(idx)) != len(idx):
+            raise ValueError("timesteps must not repeat an index")
+    idx = sorted(idx, reverse=True)
+    k = max(1, BPD_ROWS // max(1, int(batch))) if t_chunk is None else int(t_chunk)
+    return [idx[i:i + k] for i in range(0, len(idx), k)]
+
+
 class GaussianDiffusion(Diffusion):
     sampler_registry = {"ddpm": DDPM, "ddim": DDIM, "dpmpp_2m": DPMSolverPP2M}  # "dpmpp_2m" (second order, multistep) is this project's
 
@@ -248,6 +272,96 @@ class GaussianDiffusion(Diffusion):
             self._dev[x.device] = (f32_table(self.sqrt_alphas_bar, x.device), f32_table(self.alphas_bar, x.device))
         sab, ab = self._dev[x.device]
         return ops.ddpm_add_noise(x, noise, to_device(timesteps, x.device, torch.int32), sab, ab), noise
+
+    # ---- likelihood evaluation (this project's; the reference has none): the variational bound in bits per dimension, the headline
+    # number of Nichol & Dhariwal, "Improved Denoising Diffusion Probabilistic Models" (2021), `calc_bpd_loop` of their code base
+    def _bpd_check_halves(self, pred_shape: tuple[int, ...], x: Tensor) -> None:
+        try:  # (shapes only: a meta tensor stands in for a prediction that does not exist yet)
+            self.sampler._check_halves(torch.empty(pred_shape, device="meta"), x)
+        except AssertionError as e:
+            raise ValueError(f"model: {e}") from None
+
+    def _bpd_plan(self, model, model_inputs, t_chunk, noise, timesteps) -> list[list[int]]:
+        """every host check of `calc_bpd_loop`, before any device work; -> the passes as lists of chain indices"""
+        if self.latent_diffusion:
+            raise ValueError("latent_diffusion=True: the bound's t = 0 term is the likelihood of 8-bit bins on [-1, 1], which only mean "
+                             "something for pixel data; bits per dimension of a latent chain are not offered")
+        x = model_inputs["x"]
+        if x.dim() < 2:
+            raise ValueError(f"model_inputs['x'] must be [B, C, *spatial], got {tuple(x.shape)}")
+        chunks = plan_bpd_chunks(self.steps, x.shape[0], t_chunk, timesteps)
+        if noise is not None and tuple(noise.shape) != (x.shape[0], self.steps, *x.shape[1:]):
+            raise ValueError(f"noise must be [B, T, C, *spatial] = {(x.shape[0], self.steps, *x.shape[1:])} (one draw per sample and "
+                             f"chain index), got {tuple(noise.shape)}")
+        out_ch = getattr(model, "out_channels", None) or getattr(model, "output_channels", None)
+        if self.sampler.learned_variance and isinstance(out_ch, int):
+            self._bpd_check_halves((x.shape[0], out_ch, *x.shape[2:]), x)
+        return chunks
+
+    @torch.no_grad()
+    def calc_bpd_loop(self, model, model_inputs, clip_denoised: bool = True, t_chunk: int | None = None, noise: Tensor | None = None,
+                      timesteps=None, use_tqdm: bool = False) -> dict[str, Tensor]:
+        """The variational bound on the negative log-likelihood of the clean data model_inputs["x"] [B, C, *spatial], in bits per
+        dimension, term by term.  The chain's indices (all `self.steps` of them, or the subset `timesteps`) are walked from high to
+        low, t_chunk of them per pass: a pass noises the data to its K indices (K * B rows, a fresh draw per row, or noise[:, j] of
+        `noise` [B, T, C, *spatial] for index j), makes one conditional forward (p = 0, indices through the respacing map, every
+        other entry of model_inputs repeated K times along the batch) and one `dl_vb_terms` launch.  t_chunk None: the largest K
+        with K * B <= 256, at least 1.  Runs under no_grad (the denoiser takes its inference path); nothing is read back to the host
+        inside the loop.  Unlike `compute_loss`, model_inputs is not mutated.
+        -> "vb", "xstart_mse", "mse": f32 [B, n_t], columns in ascending index order (vb: KL(q(x_{t-1} | x_t, x_0) || p) for t > 0,
+        the discretised-Gaussian NLL for t == 0; the squared errors of the predicted x0 and of the eps derived from it);
+        "prior_bpd" f32 [B] = KL(q(x_T | x_0) || N(0, I)); "total_bpd" f32 [B] = vb.sum(1) + prior_bpd, only when every index was
+        evaluated.  clip_denoised (IDDPM's default for this loop) clamps the predicted x0 to [-1, 1] before the model mean is formed.
+        A bad argument raises a ValueError that names it before any device work."""
+        chunks = self._bpd_plan(model, model_inputs, t_chunk, noise, timesteps)
+        x0 = model_inputs["x"].float().contiguous()
+        dev, B, tail = x0.device, x0.shape[0], tuple(x0.shape[1:])
+        order = [j for c in chunks for j in c]
+        n_t = len(order)
+        t_rows = to_device(torch.tensor(order, dtype=torch.int32).repeat_interleave(B), dev, torch.int32)  # row k B + b: index k
+        t_model = self._remap(t_rows)
+        if noise is not None:
+            noise = noise.to(device=dev, dtype=torch.float32)
+            cols = torch.tensor(order, dtype=torch.int64).to(dev)
+        tab = self.sampler._tables(dev)
+        key = ("lv_q", dev)
+        if key not in self.sampler._dev_tables:
+            self.sampler._dev_tables[key] = f32_table(self.sampler.posterior_log_variance_clipped, dev)
+        lv_q = self.sampler._dev_tables[key]
+        mean_type = ops.MEAN_TYPES[self.sampler.mean_type]
+        var_mode = ops.VAR_MODES.get(self.sampler.var_type, ops.VAR_FIXED)
+        rest = {k: v for k, v in model_inputs.items() if k not in ("x", "p")}
+
+        def repeated(v, K: int):
+            if isinstance(v, Tensor) and v.dim() >= 1 and v.shape[0] == B:
+                return v.repeat(K, *([1] * (v.dim() - 1)))
+            if isinstance(v, dict):
+                return {k: repeated(u, K) for k, u in v.items()}
+            return v
+
+        per_k: dict[int, tuple[Tensor, dict[str, Any]]] = {}  # x0 and the conditioning repeated K times (two values of K at most)
+        flat = [torch.empty(n_t * B, device=dev, dtype=torch.float32) for _ in range(3)]
+        off = 0
+        for chunk in tqdm(chunks, desc="evaluating the bound", total=len(chunks), disable=not use_tqdm, leave=False):
+            K = len(chunk)
+            if K not in per_k:
+                per_k[K] = (x0.repeat(K, *([1] * len(tail))), {k: repeated(v, K) for k, v in rest.items()})
+            x0r, cond = per_k[K]
+            rows = slice(off * B, (off + K) * B)
+            eps = None if noise is None else noise.index_select(1, cols[off:off + K]).transpose(0, 1).reshape(K * B, *tail)
+            xt, eps = self.add_noise(x0r, t_rows[rows], eps)
+            prediction = model(**cond, x=xt, p=0, timesteps=t_model[rows])["x"]
+            if self.sampler.learned_variance:
+                self._bpd_check_halves(tuple(prediction.shape), xt)
+            ops.vb_terms(prediction.float().contiguous(), eps, x0r, xt, t_rows[rows], tab, lv_q, mean_type, var_mode, clip_denoised,
+                         out=tuple(a[rows] for a in flat))
+            off += K
+        out = {k: a.view(n_t, B).flip(0).t().contiguous() for k, a in zip(("vb", "xstart_mse", "mse"), flat)}
+        ab = float(self.alphas_bar[-1])
+        out["prior_bpd"] = ops.prior_bpd(x0, ab, math.log(1.0 - ab))
+        if n_t == self.steps:
+            out["total_bpd"] = out["vb"].sum(1) + out["prior_bpd"]
+        return out
 
     # The reference leaves autograd on in this loop (gaussian_diffusion.py:344-447 carries no inference_mode / no_grad, unlike
     # Flow.denoise): outside the trainer's @no_grad image logging it would record a graph through all 1000 steps.  Here the

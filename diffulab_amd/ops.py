@@ -20,7 +20,7 @@ from . import tuning
 BF16, F32 = 0, 1
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 LOSS_FLOW, LOSS_EPS = 0, 1
-MEAN_TYPES = {"epsilon": 0, "xstart": 1, "xprev": 2, "v": 3}  # "v": the gd_loss_* / *_step_v / *_step_g / x0_threshold entry points only
+MEAN_TYPES = {"epsilon": 0, "xstart": 1, "xprev": 2, "v": 3}  # "v": the gd_loss_* / vb_terms / *_step_v / *_step_g / x0_threshold entry points only
 VAR_MODES = {"learned": 0, "learned_range": 1}
 VAR_FIXED = -1
 PATCH_CPP, PATCH_PPC = 0, 1
@@ -218,6 +218,36 @@ def gd_loss_bwd(pred: Tensor, eps: Tensor | None, x0: Tensor | None, xt: Tensor 
     out = torch.empty_like(pred) if out is None else out
     _call("dl_gd_loss_bwd", _p(pred), _p(eps), _p(x0), _p(xt), _p(t), _p(tables), tables.shape[1], target, _p(weight), var_mode,
           _p(g_mse), _p(g_vb), _p(out), B, n // B, _s())
+    return out
+
+
+def vb_terms(pred: Tensor, eps: Tensor, x0: Tensor, xt: Tensor, t: Tensor, tables: Tensor, lv_q: Tensor, mean_type: int,
+             var_mode: int, clip_denoised: bool, out: tuple[Tensor, Tensor, Tensor] | None = None) -> tuple[Tensor, Tensor, Tensor]:
+    """-> (vb, xstart_mse, mse), f32 [R] each: the variational-bound term in bits / dim and the two squared errors of every row, one
+    row per (sample, timestep) pair (dl_vb_terms).  pred [R, C, ...] (VAR_FIXED) or [R, 2C, ...]; eps, x0, xt [R, C, ...]; t int32
+    [R]; tables f32 [6, T] = DDPM._tables; lv_q f32 [T] = posterior_log_variance_clipped; out: three f32 [R] windows, allocated here
+    when None"""
+    R, n = xt.shape[0], xt.numel()
+    chw = n // R
+    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * n and eps.numel() == n and x0.numel() == n and t.numel() == R
+    assert tables.shape[0] == 6 and lv_q.numel() == tables.shape[1]
+    nshare = lib().call("dl_mse_loss_partials", chw)
+    partial = torch.empty(3 * R * nshare, device=pred.device, dtype=torch.float32) if nshare > 1 else None
+    vb, xstart_mse, mse = (torch.empty(R, device=pred.device, dtype=torch.float32) for _ in range(3)) if out is None else out
+    _call("dl_vb_terms", _p(pred), _p(eps), _p(x0), _p(xt), _p(t), _p(tables), tables.shape[1], _p(lv_q), mean_type, var_mode,
+          int(bool(clip_denoised)), _p(partial), _p(vb), _p(xstart_mse), _p(mse), R, chw, _s())
+    return vb, xstart_mse, mse
+
+
+def prior_bpd(x0: Tensor, alphas_bar_last: float, log_one_minus_ab: float, out: Tensor | None = None) -> Tensor:
+    """-> f32 [B]: KL(q(x_T | x0) || N(0, I)) of every sample in bits / dim (dl_prior_bpd); the two scalars are alphas_bar[T-1] and
+    log(1 - alphas_bar[T-1]), formed in fp64 by the caller"""
+    B = x0.shape[0]
+    chw = x0.numel() // B
+    nshare = lib().call("dl_mse_loss_partials", chw)
+    partial = torch.empty(B * nshare, device=x0.device, dtype=torch.float32) if nshare > 1 else None
+    out = torch.empty(B, device=x0.device, dtype=torch.float32) if out is None else out
+    _call("dl_prior_bpd", _p(x0), float(alphas_bar_last), float(log_one_minus_ab), _p(partial), _p(out), B, chw, _s())
     return out
 
 

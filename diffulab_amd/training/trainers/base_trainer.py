@@ -21,12 +21,16 @@ from torch.optim.optimizer import Optimizer
 
 from ...datasets.base import BatchData
 from ..ema import EMA
+from ...diffuse.modelizations.flow import NO_VARIATIONAL_BOUND
 from ...diffuse.utils import to_device
 from ..utils import AverageMeter
 from .common import Trainer
 
 if TYPE_CHECKING:
     from ...diffuse import Diffuser
+
+
+BPD_KEYS = ("val/bpd", "val/prior_bpd")  # evaluated on request (train(val_bpd_batches=...)), logged, never part of the criterion
 
 
 class BaseTrainer(Trainer):
@@ -81,6 +85,17 @@ class BaseTrainer(Trainer):
         for key, val_loss in val_losses.items():
             tracker.update(val_loss.detach(), key=f"val/{key}")  # (read back when the meter is looked at, like the training losses)
 
+    @torch.no_grad()
+    def bpd_step(self, diffuser: "Diffuser", val_batch: BatchData, tracker: AverageMeter) -> None:
+        """the variational bound of one validation batch in bits per dimension (`Diffuser.evaluate_bpd`: the whole chain, fresh noise)
+        into the tracker as val/bpd and val/prior_bpd, weighted by the batch size"""
+        val_batch = self.shard_batch(val_batch)
+        model_inputs = self.move_dict_to_device(dict(val_batch["model_inputs"]))
+        out = diffuser.evaluate_bpd(model_inputs)
+        n = model_inputs["x"].shape[0]
+        tracker.update(out["total_bpd"].mean(), key="val/bpd", n=n)
+        tracker.update(out["prior_bpd"].mean(), key="val/prior_bpd", n=n)
+
     def train(
         self,
         diffuser: "Diffuser",
@@ -98,7 +113,15 @@ class BaseTrainer(Trainer):
         denoiser_ckpt: str | None = None,
         ema_ckpt: str | None = None,
         epoch_start: int = 0,
+        val_bpd_batches: int = 0,
     ) -> None:
+        """val_bpd_batches (this project's): for the first that-many validation batches of each epoch the variational bound is
+        evaluated under the same validation context (EMA weights where configured) and logged as val/bpd and val/prior_bpd.  Logged
+        only: the sum that picks the best checkpoint leaves them out.  Gaussian diffusion only; at 0 nothing changes."""
+        if val_bpd_batches < 0:
+            raise ValueError(f"val_bpd_batches must be >= 0, got {val_bpd_batches}")
+        if val_bpd_batches and diffuser.model_type == "rectified_flow":
+            raise NotImplementedError(NO_VARIATIONAL_BOUND)
         if val_step_shift is not None:
             assert diffuser.model_type == "rectified_flow", "Time-shifting during validation is only supported for flow-based models."
         p_cfg = p_classifier_free_guidance if diffuser.denoiser.classifier_free else 0
@@ -111,9 +134,11 @@ class BaseTrainer(Trainer):
             meter.reset()
             if val_dataloader is not None:
                 with self._validating(diffuser, ema) as online:
-                    for val_batch in self.even_batches(val_dataloader):
+                    for i, val_batch in enumerate(self.even_batches(val_dataloader)):
                         self.validation_step(diffuser=diffuser, val_batch=val_batch, tracker=meter)
-                    val_total = self._log_group(meter, "val/", epoch + 1)
+                        if i < val_bpd_batches:
+                            self.bpd_step(diffuser=diffuser, val_batch=val_batch, tracker=meter)
+                    val_total = self.val_total = self._log_group(meter, "val/", epoch + 1, logged_only=BPD_KEYS)
                     if log_validation_images and self.is_main_process:
                         logging.info("creating validation images")
                         self.log_images(diffuser, val_dataloader, epoch, val_steps, step_shift=val_step_shift,
@@ -160,14 +185,16 @@ class BaseTrainer(Trainer):
         if scheduler is not None and not per_batch_scheduler:
             scheduler.step()
 
-    def _log_group(self, meter: AverageMeter, prefix: str, step: int) -> float:
-        """log the rank-mean of every tracked average under ``prefix``; returns their sum (the validation criterion)"""
+    def _log_group(self, meter: AverageMeter, prefix: str, step: int, logged_only: tuple[str, ...] = ()) -> float:
+        """log the rank-mean of every tracked average under ``prefix``; returns their sum (the validation criterion) without the
+        keys in ``logged_only``"""
         total = 0.0
         for key, value in meter.avg.items():
             if key.startswith(prefix):
                 mean = self.gather_mean(value)
                 self.log({key: mean}, step=step)
-                total += mean
+                if key not in logged_only:
+                    total += mean
         return total
 
     @contextmanager

@@ -33,7 +33,7 @@ enum { DL_OK = 0, DL_ERR_INVALID = -1, DL_ERR_LAUNCH = -2, DL_ERR_UNSUPPORTED = 
 enum { DL_BF16 = 0, DL_F32 = 1 };
 enum { DL_ACT_NONE = 0, DL_ACT_SILU = 1, DL_ACT_GELU = 2 };  /* GELU: exact erf form (nn.GELU default) */
 enum { DL_LOSS_FLOW = 0, DL_LOSS_EPS = 1 };                       /* target = a - b | target = a */
-enum { DL_MEAN_EPSILON = 0, DL_MEAN_XSTART = 1, DL_MEAN_XPREV = 2, DL_MEAN_V = 3 }; /* V: dl_gd_loss_*, the _v and _g steps, dl_x0_threshold only */
+enum { DL_MEAN_EPSILON = 0, DL_MEAN_XSTART = 1, DL_MEAN_XPREV = 2, DL_MEAN_V = 3 }; /* V: dl_gd_loss_*, dl_vb_terms, the _v and _g steps, dl_x0_threshold only */
 enum { DL_VAR_LEARNED = 0, DL_VAR_LEARNED_RANGE = 1 };            /* lv = v | lv = w log beta_t + (1 - w) log post_var_t, w = (v + 1) / 2 */
 enum { DL_VAR_FIXED = -1 };                                       /* [B, chw] prediction, variances from the tables (dl_gd_loss_*, the _v steps) */
 enum { DL_PATCH_CPP = 0, DL_PATCH_PPC = 1 };                      /* feature order (c p1 p2) | (p1 p2 c) */
@@ -125,6 +125,29 @@ DL_API int dl_gd_loss_bwd(const float* pred, const float* eps, const float* x0, 
                           const float* weight /* f32 [T], per-timestep loss weight; NULL = 1 */, int var_mode,
                           const float* g_mse_dev, const float* g_vb_dev, float* dpred, int64_t batch, int64_t chw,
                           dl_stream_t stream);
+/* Evaluation of the variational bound (calc_bpd_loop of Nichol & Dhariwal 2021; the reference has no likelihood evaluation): per
+ * row r of `rows` (sample, timestep) pairs, in one pass,
+ *   vb[r]         = mean over the row's chw elements of dl_vlb_loss_fwd's term / ln 2 (KL for t[r] > 0, discretised-Gaussian NLL with
+ *                   the same tanh CDF and 1e-12 clamp for t[r] == 0), bits per dimension;
+ *   xstart_mse[r] = mean (x0 - x0_pred)^2;      mse[r] = mean (eps - eps_pred)^2, eps_pred = (xt / sqrt_ab - x0_pred) / sqrtf(1 / ab - 1).
+ * pred is [rows, chw] (DL_VAR_FIXED) or [rows, 2 chw] read in place as dl_vlb_loss_fwd reads it; eps, x0, xt [rows, chw]; tables f32
+ * [6][T], the rows of DDPM._tables.  With DL_VAR_FIXED lv_p = row 5 (log_variance: the posterior's for fixed_small, log beta with the
+ * IDDPM first entry for fixed_large); with learned variances lv_p comes from the variance half and row 5 (betas) by var_mode.
+ * lv_q f32 [T] = posterior_log_variance_clipped, separate because rows 4, 5 of a fixed-variance table hold the model's variance.
+ * mean_type: all four (DL_MEAN_V included).  clip_denoised != 0: x0_pred is clamped to [-1, 1] before m_p = coef1 x0_pred + coef2 xt
+ * is formed, and that clamped value enters xstart_mse and mse.
+ * A row is reduced in shares of 4096 elements, one workgroup each; `partial` is caller scratch of 3 * rows * dl_mse_loss_partials(chw)
+ * floats, read and written only where chw > 4096 (may be NULL otherwise).  Fixed order, no float atomics; exactly `rows` floats of
+ * each output are written, nothing image-sized. */
+DL_API int dl_vb_terms(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                       const float* tables, int32_t T, const float* lv_q, int mean_type, int var_mode, int clip_denoised,
+                       float* partial, float* vb, float* xstart_mse, float* mse, int64_t rows, int64_t chw, dl_stream_t stream);
+/* The prior term of the same bound: out[b] = KL(q(x_T | x0[b]) || N(0, I)) in bits per dimension = mean over chw of
+ * 0.5 (-1 - l + exp(l) + ab x0^2) / ln 2 with ab = alphas_bar[T-1] and l = log(1 - ab), host scalars computed in fp64.
+ * (-1 - l + exp(l) is formed once, as expm1f(l) - l: the three terms cancel to about l^2 / 2.)
+ * `partial`: batch * dl_mse_loss_partials(chw) floats, as for dl_vb_terms. */
+DL_API int dl_prior_bpd(const float* x0, float alphas_bar_last, float log_one_minus_ab, float* partial, float* out, int64_t batch,
+                        int64_t chw, dl_stream_t stream);
 /* Flow.compute_loss x-prediction branch flow.py:300-303: v = (z - xhat) / t[b] ; backward dxhat = -dv / t[b] */
 DL_API int dl_flow_x_to_v(const float* z, const float* xhat, const float* t, float* v, int64_t batch,
                           int64_t chw, dl_stream_t stream);

@@ -1082,26 +1082,29 @@ __device__ __forceinline__ float approx_cdf(float z, float* dz) {  // 0.5 (1 + t
 }
 // CLAMP (the evaluation kernel below): the predicted x0 is clamped to [-1, 1] before m_p is formed, and x0_pred, where given,
 // receives the x0 the term was formed from.  The training kernels take neither and keep their code.
-template <bool GRAD, bool CLAMP = false>
+// DMEAN (the row head's backward for loss_type "vlb", below): no stop-gradient; *dterm_do receives the term's derivative with respect
+// to the mean output o, d term / d m_p * d m_p / d o.
+template <bool GRAD, bool CLAMP = false, bool DMEAN = false>
 __device__ __forceinline__ float vlb_elem(int mean_type, int var_mode, int32_t ti, float o, float v, float x0, float x, float sab,
                                           float ab, float c1, float c2, float lv_q, float beta, float* dterm_dv,
-                                          float* x0_pred = nullptr) {
+                                          float* x0_pred = nullptr, float* dterm_do = nullptr) {
   float xs = x_start_from(mean_type, o, x, sab, ab, c1, c2);
   if (CLAMP) xs = fminf(fmaxf(xs, -1.0f), 1.0f);
   if (x0_pred) *x0_pred = xs;
   const float m_p = c1 * xs + c2 * x;  // no clamp unless CLAMP
   const float lv_p = learned_log_var(var_mode, v, lv_q, beta);
-  float term, dlv;
+  float term, dlv, dm = 0.f;  // dm = d term / d m_p (DMEAN)
   if (ti > 0) {  // KL(q(x_{t-1} | x_t, x_0) || p(x_{t-1} | x_t))
     const float d = c1 * x0 + c2 * x - m_p;
     const float r = expf(lv_q - lv_p), q = d * d * expf(-lv_p);
     term = 0.5f * (-1.0f + lv_p - lv_q + r + q);
     dlv = 0.5f * (1.0f - r - q);
+    if (DMEAN) dm = -d * expf(-lv_p);
   } else {  // -log of the discretised Gaussian likelihood of x0 (bins of width 2/255), log_scale = lv_p / 2
     const float c = x0 - m_p, s = expf(-0.5f * lv_p);
     const float zp = s * (c + 1.0f / 255.0f), zm = s * (c - 1.0f / 255.0f);
     float dP = 0.f, dQ = 0.f;
-    const float P = approx_cdf(zp, GRAD ? &dP : nullptr), Q = approx_cdf(zm, GRAD ? &dQ : nullptr);
+    const float P = approx_cdf(zp, (GRAD || DMEAN) ? &dP : nullptr), Q = approx_cdf(zm, (GRAD || DMEAN) ? &dQ : nullptr);
     // d z / d lv_p = -z / 2;  a clamped max(., 1e-12) passes no gradient (torch.clamp)
     float prob, dprob;
     if (x0 < -0.999f) prob = P, dprob = dP * (-0.5f * zp);
@@ -1109,8 +1112,19 @@ __device__ __forceinline__ float vlb_elem(int mean_type, int var_mode, int32_t t
     else prob = P - Q, dprob = dP * (-0.5f * zp) - dQ * (-0.5f * zm);
     term = -logf(fmaxf(prob, 1e-12f));
     dlv = prob > 1e-12f ? -dprob / prob : 0.0f;
+    if (DMEAN) {  // d z / d m_p = -s for both CDF arguments; the same clamp rule
+      const float dpm = x0 < -0.999f ? dP * -s : (x0 > 0.999f ? dQ * s : (dP - dQ) * -s);
+      dm = prob > 1e-12f ? -dpm / prob : 0.0f;
+    }
   }
   if (GRAD) *dterm_dv = dlv * (var_mode == DL_VAR_LEARNED ? 1.0f : 0.5f * (logf(beta) - lv_q));
+  if (DMEAN) {  // d m_p / d o = c1 d x0_pred / d o (x_start_from)
+    float dmo = c1;                                                                // xstart
+    if (mean_type == DL_MEAN_EPSILON) dmo = -c1 * (sqrtf(1.0f - ab) / sab);  // = -c1 sqrt(1 / ab - 1), as x_start_from scales o
+    else if (mean_type == DL_MEAN_XPREV) dmo = 1.0f;
+    else if (mean_type == DL_MEAN_V) dmo = -c1 * sqrtf(1.0f - ab);
+    *dterm_do = dm * dmo;
+  }
   return term;
 }
 // partial[blk] = sum (eps - o)^2 and partial[np + blk] = sum of the bound terms over the block's MSE_ELEMS_PER_BLOCK elements, in the
@@ -1228,7 +1242,8 @@ struct gd_elem {
   int64_t pi;
   float o, tgt, x0, x, sab, ab, c1, c2;
 };
-template <bool LV, bool W>
+// TI (the row head below, whose per-sample factors are looked up by timestep in every mode): ti is loaded whatever the mode reads
+template <bool LV, bool W, bool TI = false>
 __device__ __forceinline__ gd_elem gd_load(int64_t i, const float* __restrict__ pred, const float* __restrict__ eps,
                                            const float* __restrict__ x0, const float* __restrict__ xt,
                                            const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T, int target,
@@ -1237,7 +1252,7 @@ __device__ __forceinline__ gd_elem gd_load(int64_t i, const float* __restrict__ 
   const bool rows = LV || target >= DL_MEAN_XPREV;
   g.ti = 0;
   g.pi = i;
-  if (rows || W) {
+  if (rows || W || TI) {
     const int64_t b = i / chw;
     g.ti = t[b];
     if (LV) g.pi = i + b * chw;
@@ -1496,6 +1511,339 @@ extern "C" int dl_prior_bpd(const float* x0, float alphas_bar_last, float log_on
   hipLaunchKernelGGL(prior_bpd_k, (int)(batch * nshare), MSE_BLOCK, 0, (hipStream_t)stream, x0, alphas_bar_last, log_one_minus_ab,
                      partial, ro, batch, chw, nshare);
   if (nshare > 1) hipLaunchKernelGGL(rows_final_k<1>, cdiv(batch, 256), 256, 0, (hipStream_t)stream, partial, ro, batch, nshare);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// ---------------------------------------------------------------- row head: per-sample losses, L_vlb, loss-aware timestep sampling
+// Nichol & Dhariwal (2021), sec. 3.3: training on the bound itself, the timestep drawn by importance from a running second moment
+// of the per-timestep loss (`LossSecondMomentResampler` of their code base).  gd_partial_k kept per sample: a row's shares are
+// walked and reduced as vb_terms_k does it, the batch scalars are formed from the rows in ascending b by one workgroup.
+template <bool LV>
+__global__ void gd_rows_k(const float* __restrict__ pred, const float* __restrict__ eps, const float* __restrict__ x0,
+                          const float* __restrict__ xt, const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T,
+                          int target, int var_mode, float* __restrict__ partial, const RowOut<(LV ? 2 : 1)> ro, int64_t rows,
+                          int64_t chw, int64_t nshare) {
+  constexpr int N = LV ? 2 : 1;
+  __shared__ float red[N][MSE_BLOCK / DL_WAVE];
+  const int64_t row = blockIdx.x / nshare, share = blockIdx.x - row * nshare;
+  const int64_t ro0 = row * chw, base = share * MSE_ELEMS_PER_BLOCK;
+  float acc[N] = {};  // (target - o)^2, bound term
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int64_t r = base + (int64_t)j * MSE_BLOCK + threadIdx.x;
+    if (r < chw) {
+      const gd_elem g = gd_load<LV, false, true>(ro0 + r, pred, eps, x0, xt, t, tab, T, target, chw);
+      const float d = gd_sub(g.tgt, g.o);
+      acc[0] += d * d;
+      if constexpr (LV)
+        acc[1] += vlb_elem<false>(target, var_mode, g.ti, g.o, pred[g.pi + chw], g.x0, g.x, g.sab, g.ab, g.c1, g.c2, tab[4 * T + g.ti],
+                                  tab[5 * T + g.ti], nullptr);
+    }
+  }
+  row_share_finish<N>(acc, red, ro, partial, rows, row, nshare, share);
+}
+// one workgroup: finishes the rows of more than one share (share order), forms total_row and the two batch scalars (ascending b:
+// 256 rows at a time go through shared memory, thread k sums scalar k)
+template <bool LV>
+__global__ __launch_bounds__(256) void gd_rows_final_k(const float* __restrict__ partial, const int32_t* __restrict__ t,
+                                                       const float* __restrict__ weight, const float* __restrict__ imp,
+                                                       float vb_scale, int vlb, const RowOut<(LV ? 2 : 1)> ro,
+                                                       float* __restrict__ total_row, float* __restrict__ loss, int64_t rows,
+                                                       int64_t nshare, float inv_rows) {
+  constexpr int N = LV ? 2 : 1;
+  __shared__ float sm[N][256];
+  float s = 0.f;
+  for (int64_t base = 0; base < rows; base += 256) {
+    const int64_t b = base + threadIdx.x;
+    float a[2] = {0.f, 0.f};
+    if (b < rows) {
+      float r[2] = {0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        if (nshare == 1) {
+          r[k] = ro.out[k][b];
+        } else {
+          const float* p = partial + ((int64_t)k * rows + b) * nshare;
+          float q = 0.f;
+          for (int64_t j = 0; j < nshare; ++j) q += p[j];
+          r[k] = q * ro.scale[k];
+          ro.out[k][b] = r[k];
+        }
+      }
+      const int32_t ti = t[b];
+      const float wm = weight ? weight[ti] * r[0] : r[0], im = imp ? imp[ti] : 1.0f;
+      total_row[b] = vlb ? r[1] : (LV ? wm + vb_scale * r[1] : wm);
+      a[0] = im * wm;
+      a[1] = im * r[1];
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) sm[k][threadIdx.x] = a[k];
+    __syncthreads();
+    if (threadIdx.x < N) {
+      const int m = (int)(rows - base < 256 ? rows - base : 256);
+      for (int k = 0; k < m; ++k) s += sm[threadIdx.x][k];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < N) loss[threadIdx.x] = s * inv_rows;
+}
+// gd_bwd_k with the per-sample importance weight and, DMEAN, the bound's derivative into the mean output
+template <bool LV, bool W, bool DMEAN>
+__global__ void gd_rows_bwd_k(const float* __restrict__ pred, const float* __restrict__ eps, const float* __restrict__ x0,
+                              const float* __restrict__ xt, const int32_t* __restrict__ t, const float* __restrict__ tab, int32_t T,
+                              int target, const float* __restrict__ weight, const float* __restrict__ imp, int var_mode, float coef_m,
+                              float coef_v, const float* __restrict__ g_mse, const float* __restrict__ g_vb,
+                              float* __restrict__ dpred, int64_t n, int64_t chw) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (g_mse) coef_m *= *g_mse;  // as gd_bwd_k forms its coefficients
+  if (LV && g_vb) coef_v *= *g_vb;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const gd_elem g = gd_load<LV, W, true>(i, pred, eps, x0, xt, t, tab, T, target, chw);
+    float cm = W ? coef_m * weight[g.ti] : coef_m, cv = coef_v;
+    if (imp) {
+      const float im = imp[g.ti];
+      cm *= im;
+      cv *= im;
+    }
+    float dm = cm * gd_sub(g.o, g.tgt);
+    if constexpr (LV) {
+      float dv, dvo = 0.f;
+      vlb_elem<true, false, DMEAN>(target, var_mode, g.ti, g.o, pred[g.pi + chw], g.x0, g.x, g.sab, g.ab, g.c1, g.c2,
+                                   tab[4 * T + g.ti], tab[5 * T + g.ti], &dv, nullptr, &dvo);
+      dpred[g.pi + chw] = cv * dv;
+      if (DMEAN) dm += cv * dvo;
+    }
+    dpred[g.pi] = dm;
+  }
+}
+static int gd_rows_check(const char* who, int var_mode, int loss_type) {
+  DL_CHECK_ARG(loss_type == DL_LOSS_TYPE_MSE || loss_type == DL_LOSS_TYPE_VLB, "%s: loss_type %d", who, loss_type);
+  DL_CHECK_ARG(loss_type == DL_LOSS_TYPE_MSE || var_mode != DL_VAR_FIXED, "%s: DL_LOSS_TYPE_VLB needs learned variances", who);
+  return DL_OK;
+}
+extern "C" int dl_gd_loss_rows_fwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                                   const float* tables, int32_t T, int target, const float* weight, const float* imp, int var_mode,
+                                   int loss_type, float vb_scale, float* partial, float* mse_row, float* vb_row, float* total_row,
+                                   float* loss, int64_t batch, int64_t chw, dl_stream_t stream) {
+  if (int rc = gd_check("dl_gd_loss_rows_fwd", pred, eps, x0, xt, t, tables, T, target, var_mode, batch, chw)) return rc;
+  if (int rc = gd_rows_check("dl_gd_loss_rows_fwd", var_mode, loss_type)) return rc;
+  const bool lv = var_mode != DL_VAR_FIXED;
+  DL_CHECK_ARG(mse_row && total_row && loss && (vb_row || !lv), "dl_gd_loss_rows_fwd: bad args (mse_row, vb_row, total_row, loss)");
+  const int64_t nshare = dl_mse_loss_partials(chw);
+  DL_CHECK_ARG(nshare == 1 || partial, "dl_gd_loss_rows_fwd: chw %lld needs partial (2 batch dl_mse_loss_partials(chw) floats)",
+               (long long)chw);
+  DL_CHECK_ARG(batch <= INT32_MAX / nshare, "dl_gd_loss_rows_fwd: batch %lld x %lld shares exceed the grid", (long long)batch,
+               (long long)nshare);
+  const float inv = (float)(1.0 / (double)chw), inv_ln2 = (float)(1.0 / ((double)chw * 0.6931471805599453));
+  const float inv_b = (float)(1.0 / (double)batch);
+  const int vlb = loss_type == DL_LOSS_TYPE_VLB;
+  if (lv) {
+    const RowOut<2> ro = {{mse_row, vb_row}, {inv, inv_ln2}};
+    hipLaunchKernelGGL(gd_rows_k<true>, (int)(batch * nshare), MSE_BLOCK, 0, (hipStream_t)stream, pred, eps, x0, xt, t, tables, T,
+                       target, var_mode, partial, ro, batch, chw, nshare);
+    hipLaunchKernelGGL(gd_rows_final_k<true>, 1, 256, 0, (hipStream_t)stream, partial, t, weight, imp, vb_scale, vlb, ro, total_row,
+                       loss, batch, nshare, inv_b);
+  } else {
+    const RowOut<1> ro = {{mse_row}, {inv}};
+    hipLaunchKernelGGL(gd_rows_k<false>, (int)(batch * nshare), MSE_BLOCK, 0, (hipStream_t)stream, pred, eps, x0, xt, t, tables, T,
+                       target, var_mode, partial, ro, batch, chw, nshare);
+    hipLaunchKernelGGL(gd_rows_final_k<false>, 1, 256, 0, (hipStream_t)stream, partial, t, weight, imp, vb_scale, vlb, ro, total_row,
+                       loss, batch, nshare, inv_b);
+  }
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+extern "C" int dl_gd_loss_rows_bwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                                   const float* tables, int32_t T, int target, const float* weight, const float* imp, int var_mode,
+                                   int loss_type, const float* g_mse_dev, const float* g_vb_dev, float* dpred, int64_t batch,
+                                   int64_t chw, dl_stream_t stream) {
+  if (int rc = gd_check("dl_gd_loss_rows_bwd", pred, eps, x0, xt, t, tables, T, target, var_mode, batch, chw)) return rc;
+  if (int rc = gd_rows_check("dl_gd_loss_rows_bwd", var_mode, loss_type)) return rc;
+  DL_CHECK_ARG(dpred, "dl_gd_loss_rows_bwd: bad args (dpred)");
+  const int64_t n = batch * chw;
+  const bool lv = var_mode != DL_VAR_FIXED;
+  const float coef_m = (float)(2.0 / (double)n), coef_v = (float)(1.0 / ((double)n * 0.6931471805599453));
+#define GD_ROWS_BWD(LV, W, DMEAN)                                                                                                \
+  hipLaunchKernelGGL((gd_rows_bwd_k<LV, W, DMEAN>), ew_grid(n), 256, 0, (hipStream_t)stream, pred, eps, x0, xt, t, tables, T, target, \
+                     weight, imp, var_mode, coef_m, coef_v, g_mse_dev, g_vb_dev, dpred, n, chw)
+  if (loss_type == DL_LOSS_TYPE_VLB) {
+    if (weight) GD_ROWS_BWD(true, true, true); else GD_ROWS_BWD(true, false, true);
+  } else if (lv) {
+    if (weight) GD_ROWS_BWD(true, true, false); else GD_ROWS_BWD(true, false, false);
+  } else {
+    if (weight) GD_ROWS_BWD(false, true, false); else GD_ROWS_BWD(false, false, false);
+  }
+#undef GD_ROWS_BWD
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
+// the resampler's state, one launch per training step: one workgroup, thread i owns the histories of timesteps i, i + 1024, ...
+#define HIST_THREADS 1024
+#define HIST_MAX_T 4096
+#define HIST_MAX_N 65536
+__global__ __launch_bounds__(HIST_THREADS) void loss_history_update_k(const int32_t* __restrict__ t, const float* __restrict__ loss,
+                                                                       int n, float* __restrict__ hist, int32_t* __restrict__ count,
+                                                                       float* __restrict__ p, float* __restrict__ imp,
+                                                                       float* __restrict__ cdf, int T, int H, float uniform_prob) {
+  __shared__ float sp[HIST_MAX_T];
+  __shared__ float wsum[HIST_THREADS / DL_WAVE];
+  __shared__ __attribute__((aligned(16))) int32_t st[HIST_THREADS];
+  __shared__ float sl[HIST_THREADS];
+  __shared__ int not_full;
+  constexpr int OWN = HIST_MAX_T / HIST_THREADS;
+  if (threadIdx.x == 0) not_full = 0;
+  // Applying k pairs in order to a row that holds c of its H slots leaves the last min(H, c + k) entries of (old entries, new losses):
+  // drop = max(0, c + k - H) entries fall off the front.  So the pairs are walked twice, 1024 at a time through shared memory (four
+  // indices compared per read): once to count a thread's pairs, then -- after the kept old entries have moved to the front -- to put
+  // the j-th of them at slot c + j - drop.  Array order is kept (chunks ascend, a thread walks a chunk in order), and no work that
+  // waits on memory sits in the divergent branch of a match: the lanes of a wave meet their pairs at different iterations, so
+  // whatever that branch waits for is waited for one lane after the other.
+  int c[OWN], k[OWN], drop[OWN];
+#pragma unroll
+  for (int q = 0; q < OWN; ++q) {
+    const int i = threadIdx.x + q * HIST_THREADS;
+    c[q] = i < T ? min(max(count[i], 0), H) : 0;  // (a count from outside this kernel never indexes past the row)
+    k[q] = 0;
+  }
+  for (int j0 = 0; j0 < n; j0 += HIST_THREADS) {
+    __syncthreads();
+    st[threadIdx.x] = j0 + threadIdx.x < n ? t[j0 + threadIdx.x] : -1;
+    __syncthreads();
+    const int m = min(HIST_THREADS, n - j0);
+#pragma unroll
+    for (int q = 0; q < OWN; ++q) {
+      const int i = threadIdx.x + q * HIST_THREADS;
+      if (i < T)
+        for (int jj = 0; jj < m; jj += 4) {
+          const int4 v = *reinterpret_cast<const int4*>(&st[jj]);
+          k[q] += (v.x == i) + (v.y == i) + (v.z == i) + (v.w == i);
+        }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < OWN; ++q) {
+    const int i = threadIdx.x + q * HIST_THREADS;
+    drop[q] = max(0, c[q] + k[q] - H);
+    const int keep = i < T && k[q] > 0 && drop[q] > 0 ? c[q] - drop[q] : 0;  // old entries that stay, moved to slots 0 .. keep-1
+    float* h = hist + (int64_t)i * H;
+    for (int r0 = 0; r0 < keep; r0 += 8) {  // eight slots per round trip; a slot is read in the round before the one that overwrites it
+      float a[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) a[r] = r0 + r < keep ? h[r0 + r + drop[q]] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 8; ++r)
+        if (r0 + r < keep) h[r0 + r] = a[r];
+    }
+  }
+  bool any = false;
+#pragma unroll
+  for (int q = 0; q < OWN; ++q) any |= k[q] > 0;
+  for (int j0 = 0; j0 < n; j0 += HIST_THREADS) {
+    __syncthreads();
+    const bool in = j0 + threadIdx.x < n;
+    st[threadIdx.x] = in ? t[j0 + threadIdx.x] : -1;
+    sl[threadIdx.x] = in ? loss[j0 + threadIdx.x] : 0.f;
+    __syncthreads();
+    if (!any) continue;
+    const int m = min(HIST_THREADS, n - j0);
+#pragma unroll
+    for (int q = 0; q < OWN; ++q) {
+      const int i = threadIdx.x + q * HIST_THREADS;
+      if (i < T && k[q] > 0) {
+        float* h = hist + (int64_t)i * H;
+        for (int jj = 0; jj < m; jj += 4) {
+          const int4 v = *reinterpret_cast<const int4*>(&st[jj]);
+          if (v.x != i && v.y != i && v.z != i && v.w != i) continue;
+          const int e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int k4 = 0; k4 < 4; ++k4) {
+            if (e[k4] != i) continue;
+            const int pos = c[q] - drop[q];  // c counts up through the pairs: the slot of this one, negative if it falls off too
+            if (pos >= 0) h[pos] = sl[jj + k4];
+            ++c[q];
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < OWN; ++q) c[q] = min(c[q], H);
+  float local = 0.f;
+  bool nf = false;
+#pragma unroll
+  for (int q = 0; q < OWN; ++q) {
+    const int i = threadIdx.x + q * HIST_THREADS;
+    if (i < T) {
+      const float* h = hist + (int64_t)i * H;
+      count[i] = c[q];
+      nf |= c[q] != H;
+      float s = 0.f;
+      for (int slot = 0; slot < H; ++slot) s += h[slot] * h[slot];
+      const float r = sqrtf(s / (float)H);
+      sp[i] = r;
+      local += r;  // ascending i within the thread
+    }
+  }
+  __syncthreads();  // (not_full = 0 above, where n == 0 met no barrier)
+  if (nf) not_full = 1;  // (every writer stores the same value)
+  local = wave_sum(local);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = local;
+  __syncthreads();
+  float total = 0.f;
+  for (int w = 0; w < HIST_THREADS / DL_WAVE; ++w) total += wsum[w];
+  const bool warm = !not_full && total > 0.0f;
+  const float uni = 1.0f / (float)T;
+  for (int i = threadIdx.x; i < T; i += HIST_THREADS) {
+    const float pi = warm ? sp[i] / total * (1.0f - uniform_prob) + uniform_prob / (float)T : uni;
+    sp[i] = pi;
+    p[i] = pi;
+    imp[i] = 1.0f / ((float)T * pi);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {  // a serial prefix sum: ascending order, and non-decreasing whatever the rounding
+    float run = 0.f;
+    for (int i = 0; i < T; ++i) {
+      run += sp[i];
+      sp[i] = run;
+    }
+    sp[T - 1] = 1.0f;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < T; i += HIST_THREADS) cdf[i] = sp[i];
+}
+extern "C" int dl_loss_history_update(const int32_t* t, const float* loss, int64_t n, float* hist, int32_t* count, float* p,
+                                      float* imp, float* cdf, int32_t T, int32_t H, float uniform_prob, dl_stream_t stream) {
+  DL_CHECK_ARG(hist && count && p && imp && cdf && T > 0 && H > 0 && n >= 0, "dl_loss_history_update: bad args");
+  DL_CHECK_ARG(n == 0 || (t && loss), "dl_loss_history_update: bad args (t, loss with n %lld)", (long long)n);
+  DL_CHECK_ARG(uniform_prob >= 0.0f && uniform_prob <= 1.0f, "dl_loss_history_update: uniform_prob %g outside [0, 1]",
+               (double)uniform_prob);
+  if (T > HIST_MAX_T || n > HIST_MAX_N) {
+    dl_set_error("dl_loss_history_update: T %d above %d or n %lld above %d", T, HIST_MAX_T, (long long)n, HIST_MAX_N);
+    return DL_ERR_UNSUPPORTED;
+  }
+  hipLaunchKernelGGL(loss_history_update_k, 1, HIST_THREADS, 0, (hipStream_t)stream, t, loss, (int)n, hist, count, p, imp, cdf, T, H,
+                     uniform_prob);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+__global__ void draw_timesteps_k(const float* __restrict__ u, const float* __restrict__ cdf, int T, int32_t* __restrict__ out,
+                                 int64_t n) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  const float x = u[b];
+  int lo = 0, hi = T - 1;  // the first index with cdf > x lies in [lo, hi], or there is none and T - 1 is returned
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cdf[mid] > x) hi = mid; else lo = mid + 1;
+  }
+  out[b] = lo;
+}
+extern "C" int dl_draw_timesteps(const float* u, const float* cdf, int32_t T, int32_t* t_out, int64_t batch, dl_stream_t stream) {
+  DL_CHECK_ARG(u && cdf && t_out && T > 0 && batch > 0, "dl_draw_timesteps: bad args");
+  DL_CHECK_ARG(batch <= (int64_t)INT32_MAX * 256, "dl_draw_timesteps: batch %lld exceeds the grid", (long long)batch);
+  hipLaunchKernelGGL(draw_timesteps_k, cdiv(batch, 256), 256, 0, (hipStream_t)stream, u, cdf, T, t_out, batch);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }

@@ -38,6 +38,8 @@ class Diffuser:
         self.denoiser.train()
 
     def draw_timesteps(self, batch_size: int) -> Tensor:
+        if getattr(self.diffusion, "timestep_sampler_state", None) is not None:  # a loss-aware sampler draws on the denoiser's device
+            return self.diffusion.draw_timesteps(batch_size=batch_size, device=next(self.denoiser.parameters()).device)
         return self.diffusion.draw_timesteps(batch_size=batch_size)
 
     def compute_loss(self, model_inputs, timesteps: Tensor | None = None, noise: Tensor | None = None,

@@ -104,6 +104,50 @@ def gd_head(pred: Tensor, eps: Tensor | None, x0: Tensor | None, xt: Tensor | No
     return out if var_mode == ops.VAR_FIXED else (out[0], out[1])
 
 
+class _GDRowsHead(torch.autograd.Function):
+    """`_GDHead` with every sample's loss kept -- dl_gd_loss_rows_fwd / _bwd: for a per-sample importance weight `imp` (loss-aware
+    timestep sampling) and for loss_type "vlb", the variational bound trained without the stop-gradient on the predicted mean.
+    -> (loss f32 [2] = the two batch scalars, rows): only `loss` is differentiable; rows = the detached per-sample tensors."""
+
+    @staticmethod
+    def forward(ctx, pred: Tensor, eps, x0, xt, t: Tensor, tables: Tensor, weight, imp, target: int, var_mode: int, loss_type: int,
+                vb_scale: float):
+        pred = pred.float().contiguous()
+        ctx.save_for_backward(pred, eps, x0, xt, t, tables, weight, imp)
+        ctx.modes = (target, var_mode, loss_type)
+        mse_row, vb_row, total_row, loss = ops.gd_loss_rows_fwd(pred, eps, x0, xt, t, tables, target, weight, imp, var_mode, loss_type,
+                                                                vb_scale)
+        ctx.mark_non_differentiable(mse_row, total_row, *(() if vb_row is None else (vb_row,)))
+        if vb_row is None:
+            return loss[0], mse_row, total_row
+        return loss[0], loss[1], mse_row, vb_row, total_row
+
+    @staticmethod
+    def backward(ctx, g_mse: Tensor, *rest):
+        # the upstream gradients stay on the device (an unused output arrives as zeros); one kernel writes the whole dpred
+        pred, eps, x0, xt, t, tables, weight, imp = ctx.saved_tensors
+        target, var_mode, loss_type = ctx.modes
+        g_vb = None if var_mode == ops.VAR_FIXED else rest[0].float().contiguous()
+        dpred = ops.gd_loss_rows_bwd(pred, eps, x0, xt, t, tables, target, weight, imp, var_mode, loss_type,
+                                     g_mse.float().contiguous(), g_vb)
+        return (dpred,) + (None,) * 11
+
+
+def gd_rows_head(pred: Tensor, eps: Tensor | None, x0: Tensor | None, xt: Tensor | None, t: Tensor, tables: Tensor, target: int,
+                 weight: Tensor | None, imp: Tensor | None, var_mode: int, loss_type: int, vb_scale: float) -> dict[str, Tensor]:
+    """-> {"loss_mse", "loss_vb" (learned variances), "mse", "vb" (learned variances), "total"}: the two batch scalars, carrying the
+    importance weights and differentiable in pred, and the per-sample f32 [B] tensors before those weights, detached"""
+    eps, x0, xt = (None if v is None else v.float().contiguous() for v in (eps, x0, xt))
+    fixed = var_mode == ops.VAR_FIXED
+    if pred.requires_grad:
+        out = _GDRowsHead.apply(pred, eps, x0, xt, t, tables, weight, imp, target, var_mode, loss_type, vb_scale)
+    else:
+        mse_row, vb_row, total_row, loss = ops.gd_loss_rows_fwd(pred.float().contiguous(), eps, x0, xt, t, tables, target, weight, imp,
+                                                                var_mode, loss_type, vb_scale)
+        out = (loss[0], mse_row, total_row) if fixed else (loss[0], loss[1], mse_row, vb_row, total_row)
+    return dict(zip(("loss_mse", "mse", "total") if fixed else ("loss_mse", "loss_vb", "mse", "vb", "total"), out))
+
+
 class Diffusion(ABC):
     sampler_registry: dict[str, type[Sampler]]
 

@@ -18,7 +18,8 @@ from ..samplers.common import StepResult
 from ..samplers.gaussian_diffusion import DDIM, DDPM, DPMSolverPP2M
 from ..utils import (SamplingOutput, check_guidance, f32_table, guidance_kwargs, in_guidance_interval, strength_to_steps,
                      to_device)
-from .diffusion import Diffusion, gd_head, hybrid_head, mse_head
+from .diffusion import Diffusion, gd_head, gd_rows_head, hybrid_head, mse_head
+from .timestep_sampler import TIMESTEP_SAMPLERS, LossSecondMomentState
 from .utils import space_timesteps
 
 try:
@@ -30,6 +31,7 @@ except ImportError:  # pragma: no cover
 
 LOSS_TARGETS = ("epsilon", "mean_type")
 LOSS_WEIGHTINGS = (None, "min_snr")
+LOSS_TYPES = ("mse", "vlb")
 
 
 def min_snr_weights(alphas_bar: Tensor, target: str, gamma: float = 5.0) -> Tensor:
@@ -76,7 +78,9 @@ class GaussianDiffusion(Diffusion):
 
     def __init__(self, n_steps: int = 1000, sampling_method: str = "ddpm", schedule: str = "linear",
                  latent_diffusion: bool = False, sampler_parameters: dict[str, Any] = {}, vlb_weight: float | None = None,
-                 loss_target: str = "epsilon", loss_weighting: str | None = None, min_snr_gamma: float = 5.0) -> None:
+                 loss_target: str = "epsilon", loss_weighting: str | None = None, min_snr_gamma: float = 5.0,
+                 loss_type: str = "mse", timestep_sampler: str = "uniform", sampler_history: int = 10,
+                 sampler_uniform_prob: float = 0.001) -> None:
         if sampling_method not in self.sampler_registry:
             raise ValueError(f"sampling method must be one of {list(self.sampler_registry)}")
         if loss_target not in LOSS_TARGETS:
@@ -99,6 +103,13 @@ class GaussianDiffusion(Diffusion):
                              'loss_target="epsilon" the variational bound would read the output as epsilon')
         if loss_weighting == "min_snr" and self._target == "xprev":
             raise ValueError('loss_weighting="min_snr" is defined for the targets epsilon, xstart and v, not for xprev')
+        self._check_loss_type(loss_type, timestep_sampler, sampler_history, sampler_uniform_prob, loss_target, loss_weighting, mean_type,
+                              sampler_parameters.get("var_type", "fixed_small"), latent_diffusion)
+        self.loss_type, self.timestep_sampler = loss_type, timestep_sampler
+        # compute_loss goes through the row head (per-sample losses) instead of the batch-scalar heads
+        self._rows_head = loss_type == "vlb" or timestep_sampler != "uniform"
+        self.timestep_sampler_state: LossSecondMomentState | None = None  # built below, once the chain is
+        self.last_terms: dict[str, Tensor] = {}
         self.loss_weight: Tensor | None = None  # fp64 [T], rebuilt with the chain
         self._dev_weight: dict[torch.device, Tensor] = {}
         self.training_steps = n_steps
@@ -107,6 +118,35 @@ class GaussianDiffusion(Diffusion):
         self._dev: dict[torch.device, tuple[Tensor, Tensor]] = {}
         super().__init__(n_steps=self.training_steps, sampling_method=sampling_method, schedule=schedule,
                          latent_diffusion=latent_diffusion, sampler_parameters=sampler_parameters)
+        if timestep_sampler == "loss_second_moment":
+            self.timestep_sampler_state = LossSecondMomentState(self.steps, sampler_history, sampler_uniform_prob)
+
+    @staticmethod
+    def _check_loss_type(loss_type, timestep_sampler, sampler_history, sampler_uniform_prob, loss_target, loss_weighting, mean_type,
+                         var_type, latent_diffusion) -> None:
+        """the host checks of loss_type / timestep_sampler and their two parameters: a ValueError that names the argument"""
+        if loss_type not in LOSS_TYPES:
+            raise ValueError(f"loss_type must be one of {list(LOSS_TYPES)}, got {loss_type!r}")
+        if timestep_sampler not in TIMESTEP_SAMPLERS:
+            raise ValueError(f"timestep_sampler must be one of {list(TIMESTEP_SAMPLERS)}, got {timestep_sampler!r}")
+        if isinstance(sampler_history, bool) or not isinstance(sampler_history, int) or sampler_history < 1:
+            raise ValueError(f"sampler_history must be an integer >= 1, got {sampler_history!r}")
+        if isinstance(sampler_uniform_prob, bool) or not isinstance(sampler_uniform_prob, (int, float)) or not 0.0 <= sampler_uniform_prob <= 1.0:
+            raise ValueError(f"sampler_uniform_prob must lie in [0, 1], got {sampler_uniform_prob!r}")
+        learned = var_type in ops.VAR_MODES
+        if loss_type == "vlb":
+            if not learned:
+                raise ValueError(f'loss_type="vlb" needs learned variances (var_type "learned" or "learned_range"), got var_type={var_type!r}: '
+                                 "with a fixed variance the variance is not trained and L_vlb is a reweighted MSE")
+            if loss_weighting is not None:
+                raise ValueError(f'loss_weighting={loss_weighting!r} weights the MSE, which loss_type="vlb" does not form')
+            if latent_diffusion:
+                raise ValueError('latent_diffusion=True: the t = 0 term of loss_type="vlb" is the likelihood of 8-bit pixel bins on [-1, 1], '
+                                 "which means nothing for latents")
+        if (loss_type == "vlb" or timestep_sampler != "uniform") and learned and loss_target == "epsilon" and mean_type != "epsilon":
+            # one parameterisation per call of the row head: the regression target is also what the bound reads the mean output as
+            raise ValueError(f'loss_type="vlb" / a loss-aware timestep_sampler with learned variances and mean_type={mean_type!r} take '
+                             'loss_target="mean_type": with loss_target="epsilon" the bound would read the output as epsilon')
 
     def set_diffusion_parameters(self, betas: Tensor) -> None:
         self.betas = betas
@@ -139,6 +179,9 @@ class GaussianDiffusion(Diffusion):
                     prev_bar = bar
                     self.timestep_map.append(i)
             self.set_diffusion_parameters(torch.tensor(respaced))
+        state = getattr(self, "timestep_sampler_state", None)
+        if state is not None and state.n_steps != self.steps:  # the history is per index of the chain being trained
+            state.reset(self.steps)
 
     def _get_variance_schedule(self, n_steps: int, variance_schedule: str = "linear") -> Tensor:
         if variance_schedule == "linear":  # Ho et al., rescaled to any chain length
@@ -152,8 +195,17 @@ class GaussianDiffusion(Diffusion):
         vals = [min(1 - alpha_bar((i + 1) / n_steps) / alpha_bar(i / n_steps), max_beta) for i in range(n_steps)]
         return torch.tensor(vals, dtype=torch.float64, requires_grad=False)
 
-    def draw_timesteps(self, batch_size: int) -> Tensor:
-        return torch.randint(0, self.steps, (batch_size,), dtype=torch.int32)
+    def draw_timesteps(self, batch_size: int, device: torch.device | str | None = None) -> Tensor:
+        """timestep_sampler "uniform": the reference's CPU draw (`device` is ignored).  "loss_second_moment": a device int32 tensor
+        drawn from the state's distribution -- one uniform per sample from the CPU global generator (the reference's site for
+        timestep randomness), searched in the device's cumulative table by `dl_draw_timesteps`; nothing is read back."""
+        if self.timestep_sampler_state is None:
+            return torch.randint(0, self.steps, (batch_size,), dtype=torch.int32)
+        if device is None:
+            raise ValueError('device: timestep_sampler="loss_second_moment" draws on the device that holds its state; pass the '
+                             "denoiser's (Diffuser.draw_timesteps does)")
+        u = torch.rand(batch_size)
+        return self.timestep_sampler_state.draw(to_device(u, device, torch.float32))
 
     def _remap(self, timesteps: Tensor) -> Tensor:
         if self.timestep_map:
@@ -204,6 +256,8 @@ class GaussianDiffusion(Diffusion):
 
     def compute_loss(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None = None, extra_losses=[],
                      extra_args: dict[str, Any] = {}) -> dict[str, Tensor]:
+        if self._rows_head:
+            return self._compute_loss_rows(model, model_inputs, timesteps, noise, extra_losses, extra_args)
         if self._target != "epsilon" or self.loss_weight is not None:
             return self._compute_loss_gd(model, model_inputs, timesteps, noise, extra_losses, extra_args)
         if self.sampler.learned_variance:
@@ -257,6 +311,46 @@ class GaussianDiffusion(Diffusion):
             loss_dict = {"loss": mse, "vb": self.vlb_weight * vb}
         else:
             loss_dict = {"loss": gd_head(prediction, noise, x0, xt, *args, ops.VAR_FIXED)}
+        for extra_loss in extra_losses:
+            loss_dict[extra_loss.name] = extra_loss(**extra_args)
+        return loss_dict
+
+    def _compute_loss_rows(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None, extra_losses,
+                           extra_args: dict[str, Any]) -> dict[str, Tensor]:
+        """the losses of `_compute_loss_gd` through the row head (loss_type="vlb" and / or a loss-aware timestep sampler; Nichol &
+        Dhariwal 2021, sec. 3.3): every sample's loss is multiplied by imp[t_b] = 1 / (T p[t_b]) -- "loss" and "vb" alike, as IDDPM
+        weights the whole per-sample loss -- and, when the prediction requires grad, the step's (t_b, total_b) pairs enter the
+        sampler's history with one launch (all ranks' pairs under data parallel).  total_b is the sample's loss before that weight:
+        w[t_b] mse_b + vlb_weight vb_b, or vb_b alone for loss_type="vlb", which returns {"loss": the bound} with its gradient
+        flowing into the mean output too.  Under no_grad the history is not touched: a validation batch drawn from the current
+        distribution with the same weights is an unbiased estimate of the uniform loss.  The step's detached per-sample tensors stay
+        on the device as `last_terms`; no device value is read back."""
+        x0 = model_inputs["x"].float().contiguous()
+        model_inputs["x"], noise = self.add_noise(x0, timesteps, noise)
+        xt = model_inputs["x"]
+        prediction = model(**model_inputs, timesteps=self._remap(timesteps))["x"]
+        t = to_device(timesteps, xt.device, torch.int32)
+        learned = self.sampler.learned_variance
+        if learned:
+            self.sampler._check_halves(prediction, xt)
+        state = self.timestep_sampler_state
+        imp = None
+        if state is not None:
+            imp = state.on(xt.device)["imp"]
+            if prediction.requires_grad:  # the backward reads the weights of this step, the update below rewrites the table
+                imp = imp.clone()
+        out = gd_rows_head(prediction, noise, x0, xt, t, self.sampler._tables(xt.device), ops.MEAN_TYPES[self._target],
+                           self._weight(xt.device), imp, ops.VAR_MODES[self.sampler.var_type] if learned else ops.VAR_FIXED,
+                           ops.LOSS_TYPES[self.loss_type], self.vlb_weight)
+        if self.loss_type == "vlb":
+            loss_dict = {"loss": out["loss_vb"]}
+        elif learned:
+            loss_dict = {"loss": out["loss_mse"], "vb": self.vlb_weight * out["loss_vb"]}
+        else:
+            loss_dict = {"loss": out["loss_mse"]}
+        self.last_terms = {"t": t, **{k: out[k].detach() for k in ("mse", "vb", "total") if k in out}}
+        if state is not None and prediction.requires_grad:
+            state.update(t, self.last_terms["total"])
         for extra_loss in extra_losses:
             loss_dict[extra_loss.name] = extra_loss(**extra_args)
         return loss_dict

@@ -251,6 +251,68 @@ def prior_bpd(x0: Tensor, alphas_bar_last: float, log_one_minus_ab: float, out: 
     return out
 
 
+LOSS_TYPES = {"mse": 0, "vlb": 1}
+
+
+def gd_loss_rows_fwd(pred: Tensor, eps: Tensor | None, x0: Tensor | None, xt: Tensor | None, t: Tensor, tables: Tensor, target: int,
+                     weight: Tensor | None, imp: Tensor | None, var_mode: int, loss_type: int, vb_scale: float,
+                     out: tuple[Tensor, Tensor | None, Tensor, Tensor] | None = None) -> tuple[Tensor, Tensor | None, Tensor, Tensor]:
+    """the row head (dl_gd_loss_rows_fwd) -> (mse_row f32 [B], vb_row f32 [B] or None with VAR_FIXED, total_row f32 [B], loss f32
+    [2], of which VAR_FIXED writes loss[0] alone).  Arguments as `gd_loss_fwd`, plus imp f32 [T] or None (the importance weights),
+    loss_type (LOSS_TYPES) and vb_scale, the weight of the bound in total_row."""
+    fixed = var_mode == VAR_FIXED
+    B = pred.shape[0]
+    n = pred.numel() if fixed else pred.numel() // 2
+    T = tables.shape[1]
+    assert all(v is None or v.numel() == n for v in (eps, x0, xt)) and t.numel() == B
+    assert all(v is None or v.numel() == T for v in (weight, imp))
+    chw = n // B
+    nshare = lib().call("dl_mse_loss_partials", chw)
+    partial = torch.empty(2 * B * nshare, device=pred.device, dtype=torch.float32) if nshare > 1 else None
+    if out is None:
+        rows = torch.empty(3, B, device=pred.device, dtype=torch.float32)
+        out = (rows[0], None if fixed else rows[1], rows[2], torch.empty(2, device=pred.device, dtype=torch.float32))
+    mse_row, vb_row, total_row, loss = out
+    _call("dl_gd_loss_rows_fwd", _p(pred), _p(eps), _p(x0), _p(xt), _p(t), _p(tables), T, target, _p(weight), _p(imp), var_mode,
+          loss_type, float(vb_scale), _p(partial), _p(mse_row), _p(vb_row), _p(total_row), _p(loss), B, chw, _s())
+    return mse_row, vb_row, total_row, loss
+
+
+def gd_loss_rows_bwd(pred: Tensor, eps: Tensor | None, x0: Tensor | None, xt: Tensor | None, t: Tensor, tables: Tensor, target: int,
+                     weight: Tensor | None, imp: Tensor | None, var_mode: int, loss_type: int, g_mse: Tensor | None,
+                     g_vb: Tensor | None, out: Tensor | None = None) -> Tensor:
+    """dpred (the shape of pred) of g_mse loss[0] + g_vb loss[1] in one pass (dl_gd_loss_rows_bwd); with loss_type "vlb" the bound
+    sends its derivative into the mean output as well.  g_mse / g_vb: device scalars (None = 1)"""
+    B = pred.shape[0]
+    n = pred.numel() if var_mode == VAR_FIXED else pred.numel() // 2
+    T = tables.shape[1]
+    assert all(v is None or v.numel() == n for v in (eps, x0, xt)) and all(v is None or v.numel() == T for v in (weight, imp))
+    out = torch.empty_like(pred) if out is None else out
+    _call("dl_gd_loss_rows_bwd", _p(pred), _p(eps), _p(x0), _p(xt), _p(t), _p(tables), T, target, _p(weight), _p(imp), var_mode,
+          loss_type, _p(g_mse), _p(g_vb), _p(out), B, n // B, _s())
+    return out
+
+
+def loss_history_update(t: Tensor | None, loss: Tensor | None, hist: Tensor, count: Tensor, p: Tensor, imp: Tensor, cdf: Tensor,
+                        uniform_prob: float) -> None:
+    """one training step of the loss-second-moment resampler (dl_loss_history_update), in place: the pairs (t[j], loss[j]) enter
+    hist f32 [T, H] / count int32 [T] in array order, then p, imp, cdf f32 [T] are formed from the history.  t None: no pairs."""
+    T, H = hist.shape
+    n = 0 if t is None else t.numel()
+    assert hist.dtype == torch.float32 and count.dtype == torch.int32 and hist.is_contiguous()
+    assert count.numel() == T and p.numel() == T and imp.numel() == T and cdf.numel() == T
+    assert n == 0 or (t.dtype == torch.int32 and loss.dtype == torch.float32 and loss.numel() == n)
+    _call("dl_loss_history_update", _p(t), _p(loss), n, _p(hist), _p(count), _p(p), _p(imp), _p(cdf), T, H, float(uniform_prob), _s())
+
+
+def draw_timesteps(u: Tensor, cdf: Tensor, out: Tensor | None = None) -> Tensor:
+    """-> int32 [B]: the first index with cdf[i] > u[b] (dl_draw_timesteps); u f32 [B] in [0, 1), cdf f32 [T]"""
+    assert u.dtype == torch.float32 and cdf.dtype == torch.float32
+    out = torch.empty(u.numel(), device=u.device, dtype=torch.int32) if out is None else out
+    _call("dl_draw_timesteps", _p(u), _p(cdf), cdf.numel(), _p(out), u.numel(), _s())
+    return out
+
+
 def flow_x_to_v(z: Tensor, xhat: Tensor, t: Tensor) -> Tensor:
     v = torch.empty_like(z)
     B = z.shape[0]

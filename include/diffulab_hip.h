@@ -148,6 +148,49 @@ DL_API int dl_vb_terms(const float* pred, const float* eps, const float* x0, con
  * `partial`: batch * dl_mse_loss_partials(chw) floats, as for dl_vb_terms. */
 DL_API int dl_prior_bpd(const float* x0, float alphas_bar_last, float log_one_minus_ab, float* partial, float* out, int64_t batch,
                         int64_t chw, dl_stream_t stream);
+/* The row head: dl_gd_loss_fwd kept per sample, for training on the bound itself (L_vlb) and for loss-aware timestep sampling
+ * (Nichol & Dhariwal 2021, sec. 3.3; `LossSecondMomentResampler` of their code base).  Inputs as dl_gd_loss_fwd, plus
+ *   imp        f32 [T] or NULL (= 1): the importance weight 1 / (T p[t]) of a sample drawn at t;
+ *   loss_type  DL_LOSS_TYPE_MSE (dl_gd_loss_fwd's loss) or DL_LOSS_TYPE_VLB (the bound alone; learned variances only);
+ *   vb_scale   host scalar: the weight of the bound in a sample's total (vlb_weight).
+ * Per sample b:  mse_row[b] = mean over chw of (target - o)^2 (unweighted);  vb_row[b] = mean term / ln 2, bits per dimension,
+ * dl_vb_terms's vb without the clamp (learned variances only; vb_row may be NULL with DL_VAR_FIXED);
+ *   total_row[b] = w[t_b] mse_row[b] + vb_scale vb_row[b]   (w[t_b] mse_row[b] with DL_VAR_FIXED; vb_row[b] with DL_LOSS_TYPE_VLB),
+ * the sample's loss before its importance weight: what dl_loss_history_update records.  Batch scalars:
+ *   loss[0] = (1/B) sum_b imp[t_b] w[t_b] mse_row[b],   loss[1] = (1/B) sum_b imp[t_b] vb_row[b]   (learned variances only),
+ * summed in ascending b by one workgroup.  A row is reduced as dl_vb_terms reduces it: shares of 4096 elements, one workgroup
+ * each; `partial` is caller scratch of 2 * batch * dl_mse_loss_partials(chw) floats, read and written only where chw > 4096 (may be
+ * NULL otherwise).  Fixed order, no float atomics, nothing image-sized written. */
+enum { DL_LOSS_TYPE_MSE = 0, DL_LOSS_TYPE_VLB = 1 };
+DL_API int dl_gd_loss_rows_fwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                               const float* tables, int32_t T, int target, const float* weight, const float* imp, int var_mode,
+                               int loss_type, float vb_scale, float* partial, float* mse_row, float* vb_row, float* total_row,
+                               float* loss, int64_t batch, int64_t chw, dl_stream_t stream);
+/* dpred of g_mse loss[0] + g_vb loss[1] in one pass, n = batch * chw:
+ *   mean output    (*g_mse_dev) imp[t_b] w[t_b] 2 (o - target) / n   (dl_gd_loss_bwd's values bit for bit where imp is NULL), plus, with
+ *                  DL_LOSS_TYPE_VLB, (*g_vb_dev) imp[t_b] / (n ln 2) d term / d o: no stop-gradient on the predicted mean.
+ *                  d term / d o = d term / d m_p * d m_p / d o;  d term / d m_p = -(m_q - m_p) exp(-lv_p) for t > 0 and, for t == 0,
+ *                  the derivative through both CDF arguments (d z / d m_p = -exp(-lv_p / 2)), zero where the 1e-12 clamp is active;
+ *                  d m_p / d o = -coef1 sqrtf(1 - ab) / sqrt_ab (epsilon: -coef1 sqrt(1 / ab - 1)), coef1 (xstart), 1 (xprev), -coef1 sqrtf(1 - ab) (v);
+ *   variance half  as dl_gd_loss_bwd writes it, times imp[t_b].
+ * Upstream gradients are DEVICE scalars (NULL = 1). */
+DL_API int dl_gd_loss_rows_bwd(const float* pred, const float* eps, const float* x0, const float* xt, const int32_t* t,
+                               const float* tables, int32_t T, int target, const float* weight, const float* imp, int var_mode,
+                               int loss_type, const float* g_mse_dev, const float* g_vb_dev, float* dpred, int64_t batch,
+                               int64_t chw, dl_stream_t stream);
+/* The loss-second-moment resampler's state, advanced by one training step in one launch (one workgroup): the n pairs
+ * (t[j], loss[j]) are applied in array order -- a timestep with count < H appends (hist[t][count++] = loss), a full one shifts its
+ * H slots left by one and stores the loss at H - 1; one thread owns one timestep and scans the pairs, so duplicates land in order
+ * (it counts its k pairs, moves the entries that stay to the front and stores the j-th pair at slot count + j - max(0, count + k - H):
+ * the same row as pair-by-pair application); an index outside [0, T) is ignored.  Then, if every count equals H (and the sum below is positive):
+ *   r[i] = sqrtf(mean_h hist[i][h]^2) (slots summed 0 .. H-1),  p = r / sum(r) * (1 - uniform_prob) + uniform_prob / T,
+ * otherwise p = 1 / T;  imp = 1 / (T p);  cdf = the inclusive prefix sum of p in ascending index order, cdf[T-1] = 1.
+ * hist f32 [T][H], count int32 [T], p, imp, cdf f32 [T].  n may be 0 (t, loss may then be NULL): the tables are formed from the
+ * history as it is.  T > 4096 or n > 65536: DL_ERR_UNSUPPORTED, nothing launched.  Fixed order: every run gives the same bits. */
+DL_API int dl_loss_history_update(const int32_t* t, const float* loss, int64_t n, float* hist, int32_t* count, float* p,
+                                  float* imp, float* cdf, int32_t T, int32_t H, float uniform_prob, dl_stream_t stream);
+/* t_out[b] = the first index i with cdf[i] > u[b] (binary search; T - 1 if there is none): a draw from p for u uniform in [0, 1) */
+DL_API int dl_draw_timesteps(const float* u, const float* cdf, int32_t T, int32_t* t_out, int64_t batch, dl_stream_t stream);
 /* Flow.compute_loss x-prediction branch flow.py:300-303: v = (z - xhat) / t[b] ; backward dxhat = -dv / t[b] */
 DL_API int dl_flow_x_to_v(const float* z, const float* xhat, const float* t, float* v, int64_t batch,
                           int64_t chw, dl_stream_t stream);

@@ -1515,6 +1515,107 @@ extern "C" int dl_prior_bpd(const float* x0, float alphas_bar_last, float log_on
   return DL_OK;
 }
 
+// ---------------------------------------------------------------- ODE likelihood of a rectified-flow model (Flow.calc_nll_loop)
+// Instantaneous change of variables with Hutchinson's divergence estimate (Grathwohl et al. 2019, FFJORD): one launch per network
+// evaluation behind the input-gradient backward.  A row's chw elements are cut into shares and reduced as vb_terms_k reduces them;
+// one sum per row, written as out[oidx] = s * scale + add.
+__device__ __forceinline__ void row1_share_finish(float acc, float* red, float* __restrict__ partial, float* __restrict__ out,
+                                                  int64_t oidx, float scale, float add, int64_t row, int64_t nshare, int64_t share) {
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int w = 0; w < MSE_BLOCK / DL_WAVE; ++w) s += red[w];
+    if (nshare == 1)
+      out[oidx] = s * scale + add;
+    else
+      partial[row * nshare + share] = s;
+  }
+}
+__global__ void rows1_final_k(const float* __restrict__ partial, float* __restrict__ out, int64_t ld, int64_t col, float scale,
+                              float add, int64_t rows, int64_t nshare) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const float* p = partial + row * nshare;
+  float s = 0.f;
+  for (int64_t j = 0; j < nshare; ++j) s += p[j];
+  out[row * ld + col] = s * scale + add;
+}
+// STEP: x_out = x + a v (+ b v0) over the same elements (x_out may be x: every element is read before it is written, by one thread)
+template <bool STEP, bool V0>
+__global__ void hutchinson_step_k(const float* x, const float* __restrict__ v, const float* __restrict__ v0, float a, float b,
+                                  float* x_out, const float* __restrict__ g, const float* __restrict__ eps, float scale,
+                                  float* __restrict__ partial, float* __restrict__ out, int64_t ld, int64_t col, int64_t rows,
+                                  int64_t chw, int64_t nshare) {
+  __shared__ float red[MSE_BLOCK / DL_WAVE];
+  const int64_t row = blockIdx.x / nshare, share = blockIdx.x - row * nshare;
+  const int64_t ro0 = row * chw, base = share * MSE_ELEMS_PER_BLOCK;
+  float acc = 0.f;
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int64_t i = base + (int64_t)j * MSE_BLOCK + threadIdx.x;
+    if (i < chw) {
+      acc += g[ro0 + i] * eps[ro0 + i];
+      if constexpr (STEP) {
+        float y = x[ro0 + i] + a * v[ro0 + i];
+        if constexpr (V0) y += b * v0[ro0 + i];
+        x_out[ro0 + i] = y;
+      }
+    }
+  }
+  row1_share_finish(acc, red, partial, out, row * ld + col, scale, 0.f, row, nshare, share);
+}
+extern "C" int dl_hutchinson_step(const float* x, const float* v, const float* v0, float a, float b, float* x_out, const float* g,
+                                  const float* eps, float scale, float* partial, float* out, int64_t ld, int64_t col, int64_t rows,
+                                  int64_t chw, dl_stream_t stream) {
+  DL_CHECK_ARG(g && eps && out && rows > 0 && chw > 0, "dl_hutchinson_step: bad args (g, eps, out, rows, chw)");
+  DL_CHECK_ARG(ld > 0 && col >= 0 && col < ld, "dl_hutchinson_step: column %lld of a table of width %lld", (long long)col, (long long)ld);
+  DL_CHECK_ARG(!x_out || (x && v), "dl_hutchinson_step: x_out needs x and v");
+  DL_CHECK_ARG(x_out || !v0, "dl_hutchinson_step: v0 without x_out");
+  const int64_t nshare = dl_mse_loss_partials(chw);
+  DL_CHECK_ARG(nshare == 1 || partial, "dl_hutchinson_step: chw %lld needs partial (rows dl_mse_loss_partials(chw) floats)", (long long)chw);
+  DL_CHECK_ARG(rows <= INT32_MAX / nshare, "dl_hutchinson_step: rows %lld x %lld shares exceed the grid", (long long)rows, (long long)nshare);
+#define HUTCH(STEP, V0)                                                                                                          \
+  hipLaunchKernelGGL((hutchinson_step_k<STEP, V0>), (int)(rows * nshare), MSE_BLOCK, 0, (hipStream_t)stream, x, v, v0, a, b, x_out, g, \
+                     eps, scale, partial, out, ld, col, rows, chw, nshare)
+  if (!x_out) HUTCH(false, false); else if (v0) HUTCH(true, true); else HUTCH(true, false);
+#undef HUTCH
+  if (nshare > 1)
+    hipLaunchKernelGGL(rows1_final_k, cdiv(rows, 256), 256, 0, (hipStream_t)stream, partial, out, ld, col, scale, 0.f, rows, nshare);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+// -log N(x; 0, I) per dimension of every row: out[r] = 0.5 mean(x^2) + 0.5 log(2 pi), nats
+__global__ void normal_nll_rows_k(const float* __restrict__ x, float* __restrict__ partial, float* __restrict__ out, float scale,
+                                  float add, int64_t rows, int64_t chw, int64_t nshare) {
+  __shared__ float red[MSE_BLOCK / DL_WAVE];
+  const int64_t row = blockIdx.x / nshare, share = blockIdx.x - row * nshare;
+  const int64_t ro0 = row * chw, base = share * MSE_ELEMS_PER_BLOCK;
+  float acc = 0.f;
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int64_t i = base + (int64_t)j * MSE_BLOCK + threadIdx.x;
+    if (i < chw) {
+      const float xv = x[ro0 + i];
+      acc += xv * xv;
+    }
+  }
+  row1_share_finish(acc, red, partial, out, row, scale, add, row, nshare, share);
+}
+extern "C" int dl_normal_nll_rows(const float* x, float* partial, float* out, int64_t rows, int64_t chw, dl_stream_t stream) {
+  DL_CHECK_ARG(x && out && rows > 0 && chw > 0, "dl_normal_nll_rows: bad args");
+  const int64_t nshare = dl_mse_loss_partials(chw);
+  DL_CHECK_ARG(nshare == 1 || partial, "dl_normal_nll_rows: chw %lld needs partial (rows dl_mse_loss_partials(chw) floats)", (long long)chw);
+  DL_CHECK_ARG(rows <= INT32_MAX / nshare, "dl_normal_nll_rows: rows %lld x %lld shares exceed the grid", (long long)rows, (long long)nshare);
+  const float scale = (float)(0.5 / (double)chw), add = 0.9189385332046727f;  // 0.5 log(2 pi)
+  hipLaunchKernelGGL(normal_nll_rows_k, (int)(rows * nshare), MSE_BLOCK, 0, (hipStream_t)stream, x, partial, out, scale, add, rows, chw,
+                     nshare);
+  if (nshare > 1) hipLaunchKernelGGL(rows1_final_k, cdiv(rows, 256), 256, 0, (hipStream_t)stream, partial, out, (int64_t)1, (int64_t)0, scale, add, rows, nshare);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
 // ---------------------------------------------------------------- row head: per-sample losses, L_vlb, loss-aware timestep sampling
 // Nichol & Dhariwal (2021), sec. 3.3: training on the bound itself, the timestep drawn by importance from a running second moment
 // of the per-timestep loss (`LossSecondMomentResampler` of their code base).  gd_partial_k kept per sample: a row's shares are

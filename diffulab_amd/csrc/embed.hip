@@ -74,6 +74,103 @@ extern "C" int dl_unpatchify(const float* tok, float* img, int64_t B, int64_t C,
   return DL_OK;
 }
 
+// ---------------------------------------------------------------- patch-embedding data gradient: dtok [M, ld] -> dimg f32 [B,C,H,W]
+// The transpose of patchify (order CPP) behind the transpose of the patch GEMM, in one launch: dimg[b, c, gy p + p1, gx p + p2] =
+// sum_d dtok[(b, gy, gx), d] W[d, (c p + p1) p + p2].  A workgroup owns PED_TM token rows and walks D in slices of PED_DK: the token
+// slice (cast to f32) and the weight slice go through LDS, thread (tl, fl) keeps tokens tl + 16 i and features fl + 16 j of the
+// current pass of PED_FP features in registers and adds the slices in ascending d.  dtok is read once per feature pass (one pass
+// up to 64 features; groups of 16 features the pass does not have are skipped), W comes from L2.  Every image element belongs to one
+// (token, feature): plain stores, no atomics.
+#define PED_TM 64
+#define PED_DK 64
+#define PED_FP 64
+template <bool BF>
+__global__ __launch_bounds__(256) void patch_embed_dgrad_k(const void* __restrict__ dtok_, const float* __restrict__ wt,
+                                                           float* __restrict__ dimg, int64_t M, int C, int H, int W, int p, int D,
+                                                           int64_t ld) {
+  __shared__ float sd[PED_TM][PED_DK + 1];  // (+1: the four token rows a wave reads at once fall into different banks)
+  __shared__ float sw[PED_DK][PED_FP];
+  const int F = C * p * p, gh = H / p, gw = W / p;
+  const int tid = threadIdx.x, fl = tid & 15, tl = tid >> 4;
+  const int64_t m0 = (int64_t)blockIdx.x * PED_TM;
+  for (int f0 = 0; f0 < F; f0 += PED_FP) {
+    float acc[4][4] = {};
+    const int nj = (F - f0 + 15) / 16 < 4 ? (F - f0 + 15) / 16 : 4;  // feature groups of 16 this pass has (uniform: 16 features -> 1)
+    const int fw = 16 * nj;
+    for (int d0 = 0; d0 < D; d0 += PED_DK) {
+      __syncthreads();
+      for (int i = tid; i < PED_TM * PED_DK; i += 256) {
+        const int r = i / PED_DK, c = i % PED_DK;
+        const int64_t m = m0 + r;
+        const int d = d0 + c;
+        float v = 0.f;
+        if (m < M && d < D) v = BF ? bf2f(((const bf16_t*)dtok_)[m * ld + d]) : ((const float*)dtok_)[m * ld + d];
+        sd[r][c] = v;
+      }
+      for (int i = tid; i < PED_DK * fw; i += 256) {  // (columns of the groups in use only: the others are never read)
+        const int r = i / fw, c = i % fw;
+        const int d = d0 + r, f = f0 + c;
+        sw[r][c] = (d < D && f < F) ? wt[(int64_t)d * F + f] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int d = 0; d < PED_DK; ++d) {
+        float a[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = sd[tl + 16 * i][d];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (j < nj) {
+            const float b = sw[d][fl + 16 * j];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i][j] += a[i] * b;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t m = m0 + tl + 16 * i;
+      if (m >= M) continue;
+      const int wq = (int)(m % gw), hq = (int)((m / gw) % gh);
+      const int64_t b = m / ((int64_t)gw * gh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int f = f0 + fl + 16 * j;
+        if (f >= F) continue;
+        const int p2 = f % p, p1 = (f / p) % p, c = f / (p * p);
+        dimg[((b * C + c) * H + hq * p + p1) * W + wq * p + p2] = acc[i][j];
+      }
+    }
+  }
+}
+extern "C" int dl_patch_embed_dgrad(const void* dtok, int dtype, int64_t ld, const float* w, float* dimg, int64_t B, int64_t C,
+                                    int64_t H, int64_t W, int64_t p, int64_t D, dl_stream_t stream) {
+  DL_CHECK_ARG(dtok && w && dimg, "dl_patch_embed_dgrad: null operand");
+  DL_CHECK_ARG(dtype == DL_BF16 || dtype == DL_F32, "dl_patch_embed_dgrad: dtype %d", dtype);
+  DL_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && p > 0 && D > 0 && H % p == 0 && W % p == 0 && ld >= D,
+               "dl_patch_embed_dgrad: bad dims (B=%lld C=%lld H=%lld W=%lld p=%lld D=%lld ld=%lld)", (long long)B, (long long)C,
+               (long long)H, (long long)W, (long long)p, (long long)D, (long long)ld);
+  DL_CHECK_ARG(B <= INT32_MAX && C <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX && D <= INT32_MAX && ld <= INT32_MAX,
+               "dl_patch_embed_dgrad: a dimension exceeds 2^31");
+  DL_CHECK_ARG(C * H <= INT32_MAX && C * H * W <= INT32_MAX && B * (C * H * W) <= INT32_MAX,
+               "dl_patch_embed_dgrad: the image has more than 2^31 elements (B=%lld C=%lld H=%lld W=%lld)", (long long)B, (long long)C,
+               (long long)H, (long long)W);
+  const int64_t M = B * (H / p) * (W / p);  // (<= the image's elements)
+  DL_CHECK_ARG(M * ld <= INT32_MAX && D * (C * p * p) <= INT32_MAX,
+               "dl_patch_embed_dgrad: more than 2^31 elements (tokens %lld x %lld, weight %lld x %lld)", (long long)M, (long long)ld,
+               (long long)D, (long long)(C * p * p));
+  const int grid = cdiv(M, PED_TM);
+  if (dtype == DL_BF16)
+    hipLaunchKernelGGL(patch_embed_dgrad_k<true>, grid, 256, 0, (hipStream_t)stream, dtok, w, dimg, M, (int)C, (int)H, (int)W, (int)p,
+                       (int)D, ld);
+  else
+    hipLaunchKernelGGL(patch_embed_dgrad_k<false>, grid, 256, 0, (hipStream_t)stream, dtok, w, dimg, M, (int)C, (int)H, (int)W,
+                       (int)p, (int)D, ld);
+  DL_LAUNCH_CHECK();
+  return DL_OK;
+}
+
 // ---------------------------------------------------------------- sinusoidal timestep embedding
 __global__ void timestep_embedding_k(const float* __restrict__ t, bf16_t* __restrict__ out, int B, int dim,
                                      float neg_log_p_over_half) {

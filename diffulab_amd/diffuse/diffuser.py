@@ -57,6 +57,14 @@ class Diffuser:
         bound) and for latent diffusion (the t = 0 term's 8-bit bins are pixel bins)."""
         return self.diffusion.calc_bpd_loop(self.denoiser, model_inputs, **kwargs)
 
+    def evaluate_nll(self, model_inputs, **kwargs: Any) -> dict[str, Tensor]:
+        """the negative log-likelihood of the clean data model_inputs["x"] under a rectified-flow model's probability-flow ODE, in nats
+        per dimension (and, in pixel space, bits per dimension of the 8-bit data), with Hutchinson's divergence estimate (this
+        project's; the reference has no likelihood evaluation): `Flow.calc_nll_loop` on this denoiser, same keywords (method,
+        n_probes, probe, probes, dequantize, dequant_noise, use_tqdm) and same result dict.  Refused for Gaussian diffusion, whose
+        likelihood measure is the variational bound (`evaluate_bpd`)."""
+        return self.diffusion.calc_nll_loop(self.denoiser, model_inputs, **kwargs)
+
     def set_steps(self, n_steps: int, schedule: str = "linear", *args: Any, **kwargs: Any) -> None:
         self.diffusion.set_steps(n_steps, schedule=schedule, *args, **kwargs)
 

@@ -10,6 +10,8 @@ GRPO (flow.py:317-380) is out of scope (needs the VLM reward stack).
 
 from __future__ import annotations
 
+import contextlib
+import math
 from typing import Any
 
 import torch
@@ -45,7 +47,18 @@ class _XToV(torch.autograd.Function):
 
 NO_VARIATIONAL_BOUND = ("rectified flow has no variational bound: bits per dimension (calc_bpd_loop, evaluate_bpd, val_bpd_batches) "
                         "are evaluated for model_type='gaussian_diffusion' only; the exact likelihood of a flow model is the ODE "
-                        "likelihood, which needs a divergence estimate through the network and is not built")
+                        "likelihood: Diffuser.evaluate_nll / Flow.calc_nll_loop (train(val_nll_batches=...))")
+
+
+def _repeat_rows(v: Any, B: int, K: int) -> Any:
+    """a per-sample entry of model_inputs (leading dimension B; dicts of such) repeated K times along the batch"""
+    if K == 1:
+        return v
+    if isinstance(v, Tensor) and v.dim() >= 1 and v.shape[0] == B:
+        return v.repeat(K, *([1] * (v.dim() - 1)))
+    if isinstance(v, dict):
+        return {k: _repeat_rows(u, B, K) for k, u in v.items()}
+    return v
 
 
 class Flow(Diffusion):
@@ -160,6 +173,128 @@ class Flow(Diffusion):
 
     def calc_bpd_loop(self, *a: Any, **k: Any):
         raise NotImplementedError(NO_VARIATIONAL_BOUND)
+
+    # ------------------------------------------------------------------ ODE likelihood (this project's; the reference has none)
+    def _nll_plan(self, model, model_inputs, method: str, n_probes: int, probe: str, probes: Tensor | None, dequantize: bool | None,
+                  dequant_noise: Tensor | None) -> tuple[int, bool]:
+        """every check of calc_nll_loop, before any device work -> (number of probes per sample, dequantize)"""
+        from ...networks.denoisers.common import FlatArenaDenoiser
+
+        if torch.is_inference_mode_enabled():
+            raise RuntimeError("calc_nll_loop differentiates the denoiser with respect to its input: it cannot run under "
+                               "torch.inference_mode() (torch.no_grad() is fine)")
+        if self.x_prediction:
+            raise NotImplementedError("calc_nll_loop: prediction_type='x' is not evaluated: v = (z - xhat) / t is singular at the data "
+                                      "end t = 0 of the ODE")
+        if isinstance(model, FlatArenaDenoiser) and not model.input_grad_capable:
+            raise NotImplementedError(f"calc_nll_loop: diffulab_amd.{type(model).__name__} returns no gradient with respect to its input "
+                                      "(input_grad_capable is False): the divergence estimate needs one; built for MMDiT(simple_dit=True)")
+        if method not in ("euler", "heun"):
+            raise ValueError(f"method must be 'euler' or 'heun' (got {method!r})")
+        if probe not in ("rademacher", "gaussian"):
+            raise ValueError(f"probe must be 'rademacher' or 'gaussian' (got {probe!r})")
+        if isinstance(n_probes, bool) or not isinstance(n_probes, int) or n_probes < 1:
+            raise ValueError(f"n_probes must be a positive integer (got {n_probes!r})")
+        x = model_inputs["x"]
+        shape = tuple(x.shape)
+        if probes is not None:
+            if not isinstance(probes, Tensor) or probes.dim() != x.dim() + 1 or tuple(probes.shape[1:]) != shape or probes.shape[0] < 1:
+                raise ValueError(f"probes must be [K, {', '.join(map(str, shape))}] (got "
+                                 f"{tuple(probes.shape) if isinstance(probes, Tensor) else type(probes).__name__})")
+            n_probes = probes.shape[0]
+        dequantize = (not self.latent_diffusion) if dequantize is None else bool(dequantize)
+        if dequant_noise is not None:
+            if not isinstance(dequant_noise, Tensor) or tuple(dequant_noise.shape) != shape:
+                raise ValueError(f"dequant_noise must be {list(shape)} (got "
+                                 f"{list(dequant_noise.shape) if isinstance(dequant_noise, Tensor) else type(dequant_noise).__name__})")
+            if not dequantize:
+                raise ValueError("dequant_noise given with dequantize=False")
+            if bool((dequant_noise < 0).any()) or bool((dequant_noise >= 1).any()):
+                raise ValueError("dequant_noise must lie in [0, 1)")
+        return n_probes, dequantize
+
+    def calc_nll_loop(self, model, model_inputs, method: str = "heun", n_probes: int = 1, probe: str = "rademacher",
+                      probes: Tensor | None = None, dequantize: bool | None = None, dequant_noise: Tensor | None = None,
+                      use_tqdm: bool = False) -> dict[str, Tensor]:
+        """The negative log-likelihood of the clean data model_inputs["x"] [B, C, *spatial] under the model's probability-flow ODE,
+        by the instantaneous change of variables (Chen et al. 2018) with Hutchinson's divergence estimate (Grathwohl et al. 2019,
+        FFJORD).  With z_t = (1 - t) x0 + t eps data sits at t = 0 and noise at t = 1: dx/dt = v(x, t) is integrated upward over this
+        object's own grid (`self.timesteps` ascending, so `set_steps` and `shift` apply) and
+            log p0(x) = log N(x1; 0, I) + integral_0^1 div v dt.
+        div v is estimated per sample as sum(eps * J^T eps), J^T eps from `torch.autograd.grad(pred, x, eps)` through the conditional
+        forward (p = 0; every other entry of model_inputs is passed through; a FlatArenaDenoiser runs inside `input_grad_only()`, so no
+        `p.grad` is touched).  method "euler": one evaluation per step; "heun": two (x_mid = x + h v1, x_new = x + h/2 (v1 + v2)), the
+        divergence with the same trapezoid weights.  One probe per row, drawn once and held along the trajectory: `probe` "rademacher"
+        or "gaussian"; n_probes = K repeats the rows K times along the batch and averages per sample; `probes` [K, B, C, *spatial]
+        supplies them.  dequantize (default: not latent_diffusion) adds (u - 0.5) * 2 / 255, u ~ U[0, 1) or `dequant_noise`
+        [B, C, *spatial]: uniform noise over the 8-bit bins of width 2/255 that `evaluate_bpd`'s t = 0 term uses.
+        Behind each backward the loop makes one `dl_hutchinson_step` launch (state update and row sums); nothing is read back to the
+        host inside it, and model_inputs is not mutated.
+        -> f32, D_el = C * prod(spatial): "nll" [B] = -(log p0) / D_el, nats per dimension; "prior" [B] = 0.5 mean(x1^2) + 0.5 log(2 pi);
+        "div" [B] = the integrated divergence / D_el; "div_terms" [B, n_evals] = every evaluation's estimate / D_el, unweighted, averaged
+        over the probes, in evaluation order; "x1" [B, C, *spatial] = the latent at t = 1; and, unless latent_diffusion, "total_bpd" [B]
+        = nll / ln 2 + log2(127.5), bits per dimension of the 8-bit data.  A bad argument raises before any device work."""
+        from ...networks.denoisers.common import FlatArenaDenoiser
+
+        K, dequantize = self._nll_plan(model, model_inputs, method, n_probes, probe, probes, dequantize, dequant_noise)
+        with torch.no_grad():
+            x0 = model_inputs["x"].detach().float().contiguous()
+            dev, B, tail = x0.device, x0.shape[0], tuple(x0.shape[1:])
+            n_el = x0.numel() // B
+            if dequantize:
+                u = torch.rand_like(x0) if dequant_noise is None else dequant_noise.to(device=dev, dtype=torch.float32)
+                x0 = x0 + (u - 0.5) * (2.0 / 255.0)
+            R = K * B
+            x = x0.repeat(K, *([1] * len(tail))).contiguous()
+            if probes is not None:
+                eps = probes.to(device=dev, dtype=torch.float32).reshape(R, *tail).contiguous()
+            elif probe == "rademacher":
+                eps = torch.randint(0, 2, (R, *tail), device=dev).float().mul_(2.0).sub_(1.0)
+            else:
+                eps = torch.randn(R, *tail, device=dev, dtype=torch.float32)
+            rest = {k: _repeat_rows(v, B, K) for k, v in model_inputs.items() if k not in ("x", "p")}
+            grid = sorted(float(t) for t in self.timesteps)
+            heun = method == "heun"
+            n_evals = (2 if heun else 1) * (len(grid) - 1)
+            table = torch.empty(R, n_evals, device=dev, dtype=torch.float32)
+            nshare = ops.lib().call("dl_mse_loss_partials", n_el)
+            partial = torch.empty(R * nshare, device=dev, dtype=torch.float32) if nshare > 1 else None
+            x_mid = torch.empty_like(x) if heun else None
+            p0 = next(model.parameters(), None)
+            t_dev, t_dtype = (p0.device, p0.dtype) if p0 is not None else (dev, torch.float32)
+        only = model.input_grad_only if isinstance(model, FlatArenaDenoiser) else contextlib.nullcontext
+
+        def evaluate(xin: Tensor, t: float) -> tuple[Tensor, Tensor]:
+            """(v, J^T eps) at (xin, t)"""
+            with torch.enable_grad(), only():
+                xin = xin.detach().requires_grad_(True)
+                pred = model(**rest, x=xin, p=0, timesteps=torch.full((R,), t, device=t_dev, dtype=t_dtype))["x"]
+                (g,) = torch.autograd.grad(pred, xin, eps.to(pred.dtype))
+            return pred.detach().float().contiguous(), g.detach().float().contiguous()
+
+        weights: list[float] = []
+        scale = 1.0 / n_el
+        steps = list(zip(grid[:-1], grid[1:]))
+        for i, (t0, t1) in enumerate(tqdm(steps, desc="evaluating the likelihood", total=len(steps), disable=not use_tqdm, leave=False)):
+            h = t1 - t0
+            v1, g1 = evaluate(x, t0)
+            if not heun:
+                ops.hutchinson_step(g1, eps, table, i, scale, x=x, v=v1, a=h, x_out=x, partial=partial)
+                weights.append(h)
+                continue
+            ops.hutchinson_step(g1, eps, table, 2 * i, scale, x=x, v=v1, a=h, x_out=x_mid, partial=partial)
+            v2, g2 = evaluate(x_mid, t1)
+            ops.hutchinson_step(g2, eps, table, 2 * i + 1, scale, x=x, v=v2, a=0.5 * h, v0=v1, b=0.5 * h, x_out=x, partial=partial)
+            weights += [0.5 * h, 0.5 * h]
+        with torch.no_grad():
+            terms = table.view(K, B, n_evals).mean(0)
+            div = (terms * torch.tensor(weights, dtype=torch.float32).to(dev)).sum(1)
+            x1 = x[:B].clone()  # (the trajectory does not depend on the probe: every repeat of a sample ends at the same latent)
+            prior = ops.normal_nll_rows(x1)
+            out = {"nll": prior - div, "prior": prior, "div": div, "div_terms": terms, "x1": x1}
+            if not self.latent_diffusion:
+                out["total_bpd"] = out["nll"] / math.log(2.0) + math.log2(127.5)
+        return out
 
     def add_noise(self, x: Tensor, timesteps: Tensor, noise: Tensor | None = None) -> tuple[Tensor, Tensor]:
         x = x.float().contiguous()

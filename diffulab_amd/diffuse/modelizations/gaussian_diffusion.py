@@ -73,6 +73,11 @@ def plan_bpd_chunks(n_steps: int, batch: int, t_chunk: int | None = None, timest
     return [idx[i:i + k] for i in range(0, len(idx), k)]
 
 
+NO_ODE_LIKELIHOOD = ("the ODE likelihood (calc_nll_loop, evaluate_nll, val_nll_batches) is evaluated for model_type='rectified_flow' "
+                     "only; the likelihood measure of Gaussian diffusion is the variational bound: evaluate_bpd / calc_bpd_loop "
+                     "(train(val_bpd_batches=...))")
+
+
 class GaussianDiffusion(Diffusion):
     sampler_registry = {"ddpm": DDPM, "ddim": DDIM, "dpmpp_2m": DPMSolverPP2M}  # "dpmpp_2m" (second order, multistep) is this project's
 
@@ -391,6 +396,9 @@ class GaussianDiffusion(Diffusion):
         if self.sampler.learned_variance and isinstance(out_ch, int):
             self._bpd_check_halves((x.shape[0], out_ch, *x.shape[2:]), x)
         return chunks
+
+    def calc_nll_loop(self, *a: Any, **k: Any):
+        raise NotImplementedError(NO_ODE_LIKELIHOOD)
 
     @torch.no_grad()
     def calc_bpd_loop(self, model, model_inputs, clip_denoised: bool = True, t_chunk: int | None = None, noise: Tensor | None = None,

@@ -923,7 +923,7 @@ class DiTEngine:
         w = self.ws
         B, Hh, D, rot = self.geo[0], self.d.num_heads, self.d.inner_dim, sum(self.d.rope_axes_dim)
         sq, sk = self.P(nm["qk"] + ".query_norm.scale"), self.P(nm["qk"] + ".key_norm.scale")
-        dscale = self.G(nm["qk"] + ".query_norm.scale")
+        dscale = self._qk_scale_sink(nm["qk"]) if self._input_only else self.G(nm["qk"] + ".query_norm.scale")
         if ops.qk_inplace_ok(w, B, nt):  # dQ, dK, dV token-major into dqkv; the QK-norm backward transforms the q / k thirds in place
             ops.attn_bwd_tok(a["q"], a["k"], a["qkv"], a["a"], s["da"], a["lse"], g["dqkv"], B, Hh, nt, 64, 64**-0.5)
             _must(ops.qk_norm_rope_bwd_inplace(a["qkv"], sq, sk, cos, sin, a["rrms"], g["dqkv"], dscale, w["qk_part"], B, nt, Hh, 64, rot,
@@ -1122,10 +1122,20 @@ class DiTEngine:
         B, _, _, _, _, N, _, _, _ = self.geo
         return self.ws["x"][k + 1].view(B, N, self.d.inner_dim)
 
-    def backward(self, dpred: Tensor, dfeats: dict[int, Tensor] | None = None) -> None:
+    def backward(self, dpred: Tensor, dfeats: dict[int, Tensor] | None = None, need_dx: bool = False,
+                 input_only: bool = False) -> Tensor | None:
         """accumulates d(loss)/d(param) into the flat gradient arena (+=) for the last train-mode forward.
-        dfeats: {block index k: gradient of an auxiliary loss w.r.t. feature(k)} (RePA), added to the residual-stream gradient."""
+        dfeats: {block index k: gradient of an auxiliary loss w.r.t. feature(k)} (RePA), added to the residual-stream gradient.
+        need_dx: also returns d(loss)/d(x) of the input latents, f32 [B, C, H, W] (one dl_patch_embed_dgrad launch on the gradient at
+        block 0's input, behind the patch weight gradient).  input_only: the data-gradient chain alone -- no weight gradient, no
+        LayerNorm-affine fold, no conditioning path, no side stream, no reducer call; the gradient arena is not written."""
         assert self._train and self.grads is not None
+        if input_only:
+            self._input_only = True
+            try:
+                return self._backward_input_only(dpred, dfeats)
+            finally:
+                self._input_only = False
         dfeats = self._dfeat_rows(dfeats)
         d, w, sh = self.d, self.ws, self.sh
         B, _, _, gh, gw, N, M, _, _ = self.geo
@@ -1218,6 +1228,66 @@ class DiTEngine:
         self._cond_bwd(dx)
         if join_last:
             sw.join()
+        return self._input_grad(dx) if need_dx else None
+
+    # ------------------------------------------------------------------ gradient of the input latents
+    _input_only = False  # True while _backward_input_only runs: the shared backward pieces then leave the gradient arena alone
+
+    def _input_grad(self, dx: Tensor) -> Tensor:
+        """d(loss)/d(input latents) f32 [B, C, H, W] from the gradient dx of the patch-embedded tokens (block 0's input)"""
+        B, H, W = self.geo[0], self.geo[1], self.geo[2]
+        dimg = torch.empty(B, self.d.input_channels, H, W, device=self.dev, dtype=torch.float32)
+        return ops.patch_embed_dgrad(dx, self.P(self._conv_name), dimg, self.d.patch_size)
+
+    def _qk_scale_sink(self, qk: str) -> Tensor:
+        """where the QK-norm backward leaves its scale gradients ([query; key], adjacent in the arena) during an input-gradient-only
+        backward: a scratch of the same extent, never read"""
+        ent = self.layout.entries
+        (q0, qs), (k0, ks) = ent[qk + ".query_norm.scale"], ent[qk + ".key_norm.scale"]
+        n = k0 - q0 + math.prod(ks)
+        sink = getattr(self, "_qk_sink", None)
+        if sink is None or sink.numel() < n:
+            sink = self._qk_sink = self._z(n, dtype=torch.float32)
+        return sink[: math.prod(qs)]
+
+    def _backward_input_only(self, dpred: Tensor, dfeats: dict[int, Tensor] | None) -> Tensor:
+        """backward() reduced to its data-gradient chain: the Python-issued block sequence that matches the forward's saved
+        activations (row-complete GEMMs or the plain one; the native C sequence launches the same kernels as these) with the
+        weight gradients and folds of SideWork made no-ops, everything on the caller's stream.  Writes workspace buffers only."""
+        dfeats = self._dfeat_rows(dfeats)
+        d, w, sh = self.d, self.ws, self.sh
+        B, _, _, gh, gw, N, M, _, _ = self.geo
+        D, L = d.inner_dim, d.depth
+        cos, sin = self._rope[(gh, gw)]
+        mod, dmod, xs = w["mod"], w["dmod32"], w["x"]
+        dmod[:B].zero_()
+        s = {k: w[k] for k in ("dxa", "dxb", "dxm", "da", "dh", "dq", "dk", "dv")}
+        fused = self._row_gemms(M, N)
+        ops.patchify(dpred, w["dO"], d.patch_size, ops.PATCH_PPC)
+        if not fused:
+            ops.gemm_nt(w["dO"], sh["last_layer.linear.weight|t"], w["dxm"], M=M, N=D, K=self._ko)
+        mo, ml = L * 6 * D, (L - 1) * 6 * D
+        dx = w["dxa"]
+        if fused:
+            _must(ops.ln_modulate_gemm_bwd(w["dO"], sh["last_layer.linear.weight|t"], xs[L], None, None, mod[:, mo : mo + D], N,
+                                            w["meanf"], w["rstdf"], dfeats.get(L - 1), dx, dmod[:, mo : mo + D],
+                                            dmod[:, mo + D : mo + 2 * D], None, gate_t=w["layers"][L - 1]["t2"],
+                                            gate=mod[:, ml + 5 * D : ml + 6 * D], dt=w["wg"][L - 1]["dt2"],
+                                            dgate=dmod[:, ml + 5 * D : ml + 6 * D], K=self._ko))
+        else:
+            Modulation(mod, dmod, mo, D, N).ln_bwd(w["dxm"], xs[L], None, None, 0, w["meanf"], w["rstdf"], dfeats.get(L - 1), dx, None,
+                                                   gate=(w["layers"][L - 1]["t2"], ml + 5 * D, w["wg"][L - 1]["dt2"]))
+        sw = _NoSideWork()
+        for i in reversed(range(L)):
+            dres = dfeats.get(i - 1)
+            if fused:  # (the LayerNorm-affine partials it writes into ws["dwb"] are overwritten, never added to, by a later backward)
+                dx = self._block_bwd_row_gemms(i, dx, dres, s, sw, False)
+            else:
+                prev = (w["layers"][i - 1]["t2"], (i - 1) * 6 * D + 5 * D, w["wg"][i - 1]["dt2"]) if i > 0 else None
+                m = Modulation(mod, dmod, i * 6 * D, D, N, part=(None, None), groups=B)
+                dx = self._dit_block_bwd(w["layers"][i], w["wg"][i], f"layers.{i}.", xs[i], dx, prev, dres, s, m, N, cos, sin, sw,
+                                         kb=w.get("kb"), dao=w.get("dao"))
+        return self._input_grad(dx)
 
     def _block_bwd_row_gemms(self, i: int, dx: Tensor, dres: Tensor | None, s: dict, sw: "SideWork", fold: bool) -> Tensor:
         """backward of block i of _forward_row_gemms: the sequence of _dit_block_bwd with each LayerNorm-modulate backward as the
@@ -1360,6 +1430,22 @@ class _StrictWgradGroups(ops.WgradGroups):
         probs = self.pending.pop(key, [])
         if probs:
             self.launch(lambda: _must(ops.gemm_tn_group(probs, self.slab, max_wgs=self.max_wgs)))
+
+
+class _NoSideWork:
+    """SideWork of an input-gradient-only backward: nothing off the data-gradient chain is launched"""
+
+    def wgrad(self, dy: Tensor, x: Tensor, name: str) -> None:
+        pass
+
+    def fold(self, partial: Tensor | None, name: str, groups: int) -> None:
+        pass
+
+    def flush(self) -> None:
+        pass
+
+    def join(self) -> None:
+        pass
 
 
 class SideWork:

@@ -275,8 +275,9 @@ class DiTEngineF32:
         mod, dmod, N = mods if mods is not None else (w["mod"], w["dmod"], N)
         scr = w["scr"]
         ops.f32_patchify(dpred, w["dO"], d.patch_size, ops.PATCH_PPC)
-        ops.f32_linear_wgrad(w["dO"], w["xf"], self.GW("last_layer.linear.weight"), scratch=scr)
-        ops.colsum(w["dO"], self.G("last_layer.linear.bias"), M, w["dO"].shape[1], scratch=scr)
+        if not self._input_only:
+            ops.f32_linear_wgrad(w["dO"], w["xf"], self.GW("last_layer.linear.weight"), scratch=scr)
+            ops.colsum(w["dO"], self.G("last_layer.linear.bias"), M, w["dO"].shape[1], scratch=scr)
         ops.f32_linear_dgrad(w["dO"], self.W("last_layer.linear.weight"), s["dxm"])
         ops.f32_ln_modulate_bwd(s["dxm"], x_last, None, None, mod[:, mo : mo + D], N, w["meanf"], w["rstdf"], dres, s["dxa"],
                                 dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], None, **gate_fused)
@@ -293,27 +294,32 @@ class DiTEngineF32:
         P, Wt, G, GW = self.P, self.W, self.G, self.GW
         mod, dmod, rpm = mods if mods is not None else (w["mod"], w["dmod"], nt)
         groups = B * nt // rpm
-        dwb = w["dwb"] if groups == B else w["dwbt"]  # partial [groups, 2, D] sums of the affine LayerNorm gradients
+        io = self._input_only  # the data-gradient chain alone: no weight gradient, no fold, no partial sums of the affine gradients
+        dwb = None if io else w["dwb"] if groups == B else w["dwbt"]  # partial [groups, 2, D] sums of the affine LayerNorm gradients
         scr = w["scr"]
         gh, gw = self.geo[3], self.geo[4]
         cos, sin = self._rope[(gh, gw)]
         rot = sum(d.rope_axes_dim)
         scale = dh**-0.5
         # MLP branch (mmdit.py:260-264, 305-308)
-        ops.f32_linear_wgrad(s["dt2"], a["h"], GW(pre + "mlp_input.2.weight"), scratch=scr)
+        if not io:
+            ops.f32_linear_wgrad(s["dt2"], a["h"], GW(pre + "mlp_input.2.weight"), scratch=scr)
         ops.f32_linear_dgrad(s["dt2"], Wt(pre + "mlp_input.2.weight"), s["dh"])
         ops.f32_swiglu_bwd(s["dh"], a["u"], s["du"])
-        ops.f32_linear_wgrad(s["du"], a["xm2"], GW(pre + "mlp_input.0.weight"), scratch=scr)
+        if not io:
+            ops.f32_linear_wgrad(s["du"], a["xm2"], GW(pre + "mlp_input.0.weight"), scratch=scr)
         ops.f32_linear_dgrad(s["du"], Wt(pre + "mlp_input.0.weight"), s["dxm"])
         dx_alt = self._other(s, dx)
         ops.f32_ln_modulate_bwd(s["dxm"], a["x1"], P(pre + "norm_2.weight"), P(pre + "norm_2.bias"), mod[:, mo + 3 * D : mo + 4 * D],
                                 rpm, a["mean2"], a["rstd2"], dx, dx_alt, dmod[:, mo + 3 * D : mo + 4 * D],
                                 dmod[:, mo + 4 * D : mo + 5 * D], dwb, gate_t=a["t1"], gate=mod[:, mo + 2 * D : mo + 3 * D],
                                 dt=s["dt1"], dgate=dmod[:, mo + 2 * D : mo + 3 * D])
-        self._fold_groups(dwb, G(pre + "norm_2.weight"), groups, 2 * D)  # [w; b] adjacent; fixed-order fold
+        if not io:
+            self._fold_groups(dwb, G(pre + "norm_2.weight"), groups, 2 * D)  # [w; b] adjacent; fixed-order fold
         dx = dx_alt
         # attention branch (mmdit.py:75-104)
-        ops.f32_linear_wgrad(s["dt1"], a["a"], GW(pre + "attention.proj_out.weight"), scratch=scr)
+        if not io:
+            ops.f32_linear_wgrad(s["dt1"], a["a"], GW(pre + "attention.proj_out.weight"), scratch=scr)
         ops.f32_linear_dgrad(s["dt1"], Wt(pre + "attention.proj_out.weight"), s["da"])
         hb = dict(batch=(B, Hh))
         # dP = dO V^T
@@ -331,8 +337,9 @@ class DiTEngineF32:
         ops.f32_qk_norm_rope_bwd(s["dqk"], a["qkv"], P(pre + "attention.qk_norm.query_norm.scale"),
                                  P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["rrms"], s["dqkv"], w["dqs"], B, nt, Hh, dh,
                                  rot, pos=pos)
-        ops.reduce_rows_batched_f32(w["dqs"], 0, G(pre + "attention.qk_norm.query_norm.scale"), 0, 1, B, 2 * D)  # [q; k] adjacent
-        ops.f32_linear_wgrad(s["dqkv"], a["xm1"], GW(pre + "attention.qkv.weight"), scratch=scr)
+        if not io:
+            ops.reduce_rows_batched_f32(w["dqs"], 0, G(pre + "attention.qk_norm.query_norm.scale"), 0, 1, B, 2 * D)  # [q; k] adjacent
+            ops.f32_linear_wgrad(s["dqkv"], a["xm1"], GW(pre + "attention.qkv.weight"), scratch=scr)
         ops.f32_linear_dgrad(s["dqkv"], Wt(pre + "attention.qkv.weight"), s["dxm"])
         if dxin_aux is not None:
             ops.f32_add(dx, dxin_aux, dx)
@@ -340,7 +347,8 @@ class DiTEngineF32:
         ops.f32_ln_modulate_bwd(s["dxm"], xin, P(pre + "norm_1.weight"), P(pre + "norm_1.bias"), mod[:, mo : mo + D], rpm,
                                 a["mean1"], a["rstd1"], dx, dx_alt, dmod[:, mo : mo + D], dmod[:, mo + D : mo + 2 * D], dwb,
                                 **gate_fused)
-        self._fold_groups(dwb, G(pre + "norm_1.weight"), groups, 2 * D)
+        if not io:
+            self._fold_groups(dwb, G(pre + "norm_1.weight"), groups, 2 * D)
         return dx_alt
 
     def _prev_gate(self, a_prev: dict, mp: int, s: dict, mods: tuple | None = None) -> dict:
@@ -384,9 +392,33 @@ class DiTEngineF32:
             self.reducer.ready(0, self.layout.size)
             self.reducer.finish()
 
-    def backward(self, dpred: Tensor, dfeats: dict[int, Tensor] | None = None) -> None:
-        """accumulates d(loss)/d(param) into the flat gradient arena (+=) for the last train-mode forward"""
+    _input_only = False  # True during an input-gradient-only backward: the backward pieces then leave the gradient arena alone
+
+    def _input_grad(self, dx0: Tensor) -> Tensor:
+        """d(loss)/d(input latents) f32 [B, C, H, W] from the gradient dx0 of the patch-embedded tokens"""
+        B, H, W = self.geo[0], self.geo[1], self.geo[2]
+        dimg = torch.empty(B, self.d.input_channels, H, W, device=self.dev, dtype=torch.float32)
+        return ops.patch_embed_dgrad(dx0, self.P(self._conv_name), dimg, self.d.patch_size)
+
+    def backward(self, dpred: Tensor, dfeats: dict[int, Tensor] | None = None, need_dx: bool = False,
+                 input_only: bool = False) -> Tensor | None:
+        """accumulates d(loss)/d(param) into the flat gradient arena (+=) for the last train-mode forward.  need_dx: also returns
+        d(loss)/d(x) of the input latents, f32 [B, C, H, W] (one dl_patch_embed_dgrad launch behind the patch weight gradient).
+        input_only: the data-gradient chain alone (no weight gradient, fold, column sum, conditioning path or reducer call): the
+        gradient arena is not written."""
         assert self._train and self.grads is not None
+        if input_only:
+            self._input_only = True
+            try:
+                return self._input_grad(self._backward_chain(dpred, dfeats))
+            finally:
+                self._input_only = False
+        dx = self._backward_chain(dpred, dfeats)
+        self._stem_cond_bwd(dx)
+        return self._input_grad(dx) if need_dx else None
+
+    def _backward_chain(self, dpred: Tensor, dfeats: dict[int, Tensor] | None) -> Tensor:
+        """head and blocks of the backward; returns the gradient at block 0's input (the patch-embedded tokens)"""
         d, w = self.d, self.ws
         B, N, M = self.geo[0], self.geo[5], self.geo[6]
         D, L = d.inner_dim, d.depth
@@ -397,4 +429,4 @@ class DiTEngineF32:
             fused = self._prev_gate(w["layers"][i - 1], (i - 1) * 6 * D, s) if i > 0 else {}
             # (dfeats[i - 1]: auxiliary-loss gradient on the output of block i-1 = this block's input)
             dx = self._blk_bwd(w["layers"][i], f"layers.{i}.", i * 6 * D, xs[i], s, dx, B, N, None, fused, dfeats.get(i - 1))
-        self._stem_cond_bwd(dx)
+        return dx

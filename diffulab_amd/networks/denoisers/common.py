@@ -2,6 +2,7 @@
 
 from __future__ import annotations
 
+import contextlib
 import copy
 import logging
 from abc import ABC, abstractmethod
@@ -54,6 +55,11 @@ class EngineFn(torch.autograd.Function):
         ctx.module, ctx.taps = module, tuple(taps)
         ctx.set_materialize_grads(False)
         ctx.serial = module._next_serial()
+        # the gradient of the input latents is formed only where it is asked for; the backward leaves the parameter gradients alone
+        # when no parameter wants one, or when the forward ran inside `input_grad_only()`
+        ctx.need_dx = bool(module.input_grad_capable and ctx.needs_input_grad[1])
+        ctx.input_only = ctx.need_dx and (bool(module.__dict__.get("_input_grad_only"))
+                                          or not any(q.requires_grad for q in module.parameters()))
         pred = module._engine.forward(x, t, y_eff, train=True).clone()
         ctx.pred_shape = pred.shape
         if not taps:
@@ -71,9 +77,13 @@ class EngineFn(torch.autograd.Function):
                 raise RuntimeError(f"{type(m).__name__}: backward through a forward that is no longer the module's latest "
                                    "train-mode forward (two grad-enabled forwards before one backward are not supported: "
                                    "call backward after each forward, or concatenate the batches)")
-            m._prepare_grads()
+            if not ctx.input_only:
+                m._prepare_grads()
             if dpred is None:
                 dpred = torch.zeros(ctx.pred_shape, device=m._engine.dev)
+            if ctx.need_dx:
+                dx = m._engine.backward(dpred.contiguous().float(), grads, need_dx=True, input_only=ctx.input_only)
+                return None, dx, None, None, None, None
             m._engine.backward(dpred.contiguous().float(), grads)
         return None, None, None, None, None, None
 
@@ -297,6 +307,22 @@ class FlatArenaDenoiser(Denoiser):
         if self.pooled_embedding:
             eng.pooled = tensors[2]
 
+    # ---- gradient of the denoiser's input.  input_grad_capable: the engine's backward can return d(loss)/d(x) of the input latents
+    #      (MMDiT simple_dit=True, both precision regimes); elsewhere an x that requires grad gets none, as before.
+    input_grad_capable = False
+
+    @contextlib.contextmanager
+    def input_grad_only(self):
+        """forwards made inside are differentiated with respect to their INPUT alone: their backward runs the data-gradient chain
+        only and leaves the gradient arena and every ``p.grad`` untouched, whatever the parameters' ``requires_grad`` -- e.g. a
+        likelihood evaluation (``Diffuser.evaluate_nll``) during validation inside a training run"""
+        prev = self.__dict__.get("_input_grad_only", False)
+        object.__setattr__(self, "_input_grad_only", True)
+        try:
+            yield self
+        finally:
+            object.__setattr__(self, "_input_grad_only", prev)
+
     # ---- classifier-free guidance: the conditional and the label-dropped forward of a sampler step as ONE forward
     cfg_pair_capable = False  # True where `p` reaches nothing but the label drop (class-conditional MMDiT / DDT / UNetModel)
 
@@ -342,7 +368,8 @@ class FlatArenaDenoiser(Denoiser):
         """prediction (and, with taps, the tapped block outputs)"""
         eng = self.engine
         eng.param_version = self._param_version()
-        need_grad = torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters())
+        need_grad = torch.is_grad_enabled() and (any(q.requires_grad for q in self.parameters())
+                                                 or (self.input_grad_capable and x.requires_grad))
         if need_grad:
             return EngineFn.apply(self, x, t, y_eff, self._anchor, tuple(taps))
         if taps:  # validation with an auxiliary loss on intermediate features: run the keep-everything sequence eagerly

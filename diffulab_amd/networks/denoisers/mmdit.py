@@ -243,6 +243,10 @@ class MMDiT(FlatArenaDenoiser):
     def precisions(self) -> tuple[str, ...]:  # the fp32-class regime is built for the class-conditional DiT (engine_f32.py)
         return ("bf16", "fp32") if self.simple_dit and self._fp32_width_ok() else ("bf16",)
 
+    @property
+    def input_grad_capable(self) -> bool:  # DiTEngine / DiTEngineF32 return the gradient of the input latents; the joint forms do not
+        return bool(self.simple_dit)
+
     def _make_engine(self, device: torch.device) -> DiTEngine:
         if self.simple_dit:
             if self.precision == "fp32":

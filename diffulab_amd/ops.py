@@ -251,6 +251,39 @@ def prior_bpd(x0: Tensor, alphas_bar_last: float, log_one_minus_ab: float, out: 
     return out
 
 
+def hutchinson_step(g: Tensor, eps: Tensor, out: Tensor, col: int, scale: float, x: Tensor | None = None, v: Tensor | None = None,
+                    a: float = 0.0, v0: Tensor | None = None, b: float = 0.0, x_out: Tensor | None = None,
+                    partial: Tensor | None = None) -> Tensor:
+    """one evaluation of the ODE likelihood behind its input-gradient backward (dl_hutchinson_step): out[r, col] = scale *
+    sum(g[r] * eps[r]) of the f32 table out [R, n]; with x_out also x_out = x + a v (+ b v0).  g, eps, x, v, v0, x_out: contiguous f32
+    [R, ...]; partial: the scratch of R * dl_mse_loss_partials(chw) floats rows of more than 4096 elements need, allocated here when
+    None"""
+    R = g.shape[0]
+    chw = g.numel() // R
+    assert out.dim() == 2 and out.shape[0] == R and out.stride(1) == 1 and out.dtype == torch.float32 and 0 <= col < out.shape[1]
+    assert all(q is None or (q.dtype == torch.float32 and q.is_contiguous() and q.numel() == R * chw) for q in (g, eps, x, v, v0, x_out))
+    nshare = lib().call("dl_mse_loss_partials", chw)
+    if partial is None and nshare > 1:
+        partial = torch.empty(R * nshare, device=g.device, dtype=torch.float32)
+    assert partial is None or partial.numel() >= R * nshare
+    _call("dl_hutchinson_step", _p(x), _p(v), _p(v0), float(a), float(b), _p(x_out), _p(g), _p(eps), float(scale), _p(partial), _p(out),
+          out.stride(0), col, R, chw, _s())
+    return out
+
+
+def normal_nll_rows(x: Tensor, out: Tensor | None = None) -> Tensor:
+    """-> f32 [R]: 0.5 mean(x[r]^2) + 0.5 log(2 pi), the negative log-density of every row under N(0, I) in nats per dimension
+    (dl_normal_nll_rows); x contiguous f32 [R, ...]"""
+    R = x.shape[0]
+    chw = x.numel() // R
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    nshare = lib().call("dl_mse_loss_partials", chw)
+    partial = torch.empty(R * nshare, device=x.device, dtype=torch.float32) if nshare > 1 else None
+    out = torch.empty(R, device=x.device, dtype=torch.float32) if out is None else out
+    _call("dl_normal_nll_rows", _p(x), _p(partial), _p(out), R, chw, _s())
+    return out
+
+
 LOSS_TYPES = {"mse": 0, "vlb": 1}
 
 
@@ -1000,6 +1033,19 @@ def patchify(x, tok, p, order):
 def unpatchify(tok, img, p):
     B, C, H, W = img.shape
     _call("dl_unpatchify", _p(tok), _p(img), B, C, H, W, p, tok.stride(0), _s())
+
+
+def patch_embed_dgrad(dtok, w, dimg, p):
+    """dimg f32 [B, C, H, W] = gradient of the image behind the patch embedding (patchify, order CPP, then tokens = patches @ w^T)
+    from the gradient dtok [M, D] (bf16 or f32 rows, any row stride) of its tokens; w: the f32 parameter [D, C, p, p] (contiguous)"""
+    B, C, H, W = dimg.shape
+    D = w.shape[0]
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.numel() == D * C * p * p and dimg.dtype == torch.float32
+    assert dimg.is_contiguous() and dtok.stride(1) == 1 and dtok.shape[1] >= D and dtok.dtype in (torch.bfloat16, torch.float32)
+    assert dtok.shape[0] >= B * (H // p) * (W // p)
+    _call("dl_patch_embed_dgrad", _p(dtok), BF16 if dtok.dtype == torch.bfloat16 else F32, dtok.stride(0), _p(w), _p(dimg), B, C, H, W,
+          p, D, _s())
+    return dimg
 
 
 def timestep_embedding(t, out, max_period=10000.0):

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import logging
 from contextlib import contextmanager
-from typing import TYPE_CHECKING, Iterable
+from typing import TYPE_CHECKING, Any, Iterable
 
 import torch
 from torch.optim.lr_scheduler import LRScheduler
@@ -22,6 +22,7 @@ from torch.optim.optimizer import Optimizer
 from ...datasets.base import BatchData
 from ..ema import EMA
 from ...diffuse.modelizations.flow import NO_VARIATIONAL_BOUND
+from ...diffuse.modelizations.gaussian_diffusion import NO_ODE_LIKELIHOOD
 from ...diffuse.utils import to_device
 from ..utils import AverageMeter
 from .common import Trainer
@@ -31,6 +32,7 @@ if TYPE_CHECKING:
 
 
 BPD_KEYS = ("val/bpd", "val/prior_bpd")  # evaluated on request (train(val_bpd_batches=...)), logged, never part of the criterion
+NLL_KEYS = ("val/nll",)  # the ODE likelihood of a flow model (train(val_nll_batches=...)): logged only as well; its val/bpd is in BPD_KEYS
 
 
 class BaseTrainer(Trainer):
@@ -96,6 +98,18 @@ class BaseTrainer(Trainer):
         tracker.update(out["total_bpd"].mean(), key="val/bpd", n=n)
         tracker.update(out["prior_bpd"].mean(), key="val/prior_bpd", n=n)
 
+    def nll_step(self, diffuser: "Diffuser", val_batch: BatchData, tracker: AverageMeter, nll_args: dict[str, Any] = {}) -> None:
+        """the ODE likelihood of one validation batch (`Diffuser.evaluate_nll`: the diffuser's own grid, fresh probes) into the tracker
+        as val/nll (nats per dimension) and, in pixel space, val/bpd, weighted by the batch size.  The evaluation differentiates the
+        denoiser with respect to its input inside `input_grad_only()`: no parameter gradient is touched."""
+        val_batch = self.shard_batch(val_batch)
+        model_inputs = self.move_dict_to_device(dict(val_batch["model_inputs"]))
+        out = diffuser.evaluate_nll(model_inputs, **nll_args)
+        n = model_inputs["x"].shape[0]
+        tracker.update(out["nll"].mean(), key="val/nll", n=n)
+        if "total_bpd" in out:
+            tracker.update(out["total_bpd"].mean(), key="val/bpd", n=n)
+
     def train(
         self,
         diffuser: "Diffuser",
@@ -114,6 +128,8 @@ class BaseTrainer(Trainer):
         ema_ckpt: str | None = None,
         epoch_start: int = 0,
         val_bpd_batches: int = 0,
+        val_nll_batches: int = 0,
+        val_nll_args: dict[str, Any] = {},
     ) -> None:
         """val_bpd_batches (this project's): for the first that-many validation batches of each epoch the variational bound is
         evaluated under the same validation context (EMA weights where configured) and logged as val/bpd and val/prior_bpd.  Logged
@@ -122,6 +138,12 @@ class BaseTrainer(Trainer):
             raise ValueError(f"val_bpd_batches must be >= 0, got {val_bpd_batches}")
         if val_bpd_batches and diffuser.model_type == "rectified_flow":
             raise NotImplementedError(NO_VARIATIONAL_BOUND)
+        # val_nll_batches / val_nll_args (this project's): the same for the ODE likelihood of a rectified-flow model (`evaluate_nll` with
+        # the keywords val_nll_args), logged as val/nll and, in pixel space, val/bpd; logged only; refused for Gaussian diffusion
+        if val_nll_batches < 0:
+            raise ValueError(f"val_nll_batches must be >= 0, got {val_nll_batches}")
+        if val_nll_batches and diffuser.model_type != "rectified_flow":
+            raise NotImplementedError(NO_ODE_LIKELIHOOD)
         if val_step_shift is not None:
             assert diffuser.model_type == "rectified_flow", "Time-shifting during validation is only supported for flow-based models."
         p_cfg = p_classifier_free_guidance if diffuser.denoiser.classifier_free else 0
@@ -138,7 +160,9 @@ class BaseTrainer(Trainer):
                         self.validation_step(diffuser=diffuser, val_batch=val_batch, tracker=meter)
                         if i < val_bpd_batches:
                             self.bpd_step(diffuser=diffuser, val_batch=val_batch, tracker=meter)
-                    val_total = self.val_total = self._log_group(meter, "val/", epoch + 1, logged_only=BPD_KEYS)
+                        if i < val_nll_batches:
+                            self.nll_step(diffuser=diffuser, val_batch=val_batch, tracker=meter, nll_args=val_nll_args)
+                    val_total = self.val_total = self._log_group(meter, "val/", epoch + 1, logged_only=BPD_KEYS + NLL_KEYS)
                     if log_validation_images and self.is_main_process:
                         logging.info("creating validation images")
                         self.log_images(diffuser, val_dataloader, epoch, val_steps, step_shift=val_step_shift,

@@ -148,6 +148,18 @@ DL_API int dl_vb_terms(const float* pred, const float* eps, const float* x0, con
  * `partial`: batch * dl_mse_loss_partials(chw) floats, as for dl_vb_terms. */
 DL_API int dl_prior_bpd(const float* x0, float alphas_bar_last, float log_one_minus_ab, float* partial, float* out, int64_t batch,
                         int64_t chw, dl_stream_t stream);
+/* ODE likelihood of a rectified-flow model (instantaneous change of variables with Hutchinson's divergence estimate, Grathwohl et
+ * al. 2019; the reference has no likelihood evaluation): what one network evaluation of the solver leaves to do, in one launch.
+ *   x_out = x + a v + b v0                        (f32 [rows, chw]; v0 NULL: no b term; x_out NULL: no update, x / v not read;
+ *                                                  x_out may be x)
+ *   out[r * ld + col] = scale * sum_chw(g * eps)  (g = J^T eps from the input-gradient backward, eps the row's probe)
+ * Rows are reduced as dl_vb_terms reduces them: shares of 4096 elements, one workgroup each; `partial` is caller scratch of
+ * rows * dl_mse_loss_partials(chw) floats, used only where chw > 4096 (may be NULL otherwise).  Fixed order, no float atomics. */
+DL_API int dl_hutchinson_step(const float* x, const float* v, const float* v0, float a, float b, float* x_out, const float* g,
+                              const float* eps, float scale, float* partial, float* out, int64_t ld, int64_t col, int64_t rows,
+                              int64_t chw, dl_stream_t stream);
+/* out[r] = 0.5 mean_chw(x^2) + 0.5 log(2 pi): -log N(x; 0, I) per dimension of every row, nats.  Reduction and `partial` as above. */
+DL_API int dl_normal_nll_rows(const float* x, float* partial, float* out, int64_t rows, int64_t chw, dl_stream_t stream);
 /* The row head: dl_gd_loss_fwd kept per sample, for training on the bound itself (L_vlb) and for loss-aware timestep sampling
  * (Nichol & Dhariwal 2021, sec. 3.3; `LossSecondMomentResampler` of their code base).  Inputs as dl_gd_loss_fwd, plus
  *   imp        f32 [T] or NULL (= 1): the importance weight 1 / (T p[t]) of a sample drawn at t;
@@ -619,6 +631,14 @@ DL_API int dl_patchify(const float* x, void* tok, int64_t B, int64_t C, int64_t 
 /* unpatchify mmdit.py:778-787: tok f32 [B*gh*gw, ld] (p1 p2 c) -> img f32 [B,C,H,W] */
 DL_API int dl_unpatchify(const float* tok, float* img, int64_t B, int64_t C, int64_t H, int64_t W, int64_t p,
                          int64_t ld, dl_stream_t stream);
+/* data gradient of the patch embedding (conv_proj, mmdit.py:757-765): the transpose of dl_patchify (order DL_PATCH_CPP) behind the
+ * transpose of the patch GEMM, in one launch:
+ *   dimg[b, c, gy p + p1, gx p + p2] = sum_d dtok[(b, gy, gx), d] * w[d, (c p + p1) p + p2]
+ * dtok [B*gh*gw, ld] bf16 or f32 (dtype DL_BF16 / DL_F32, ld >= D); w f32 [D, C*p*p], the parameter itself; dimg f32 [B,C,H,W].
+ * f32 accumulation in ascending d; every image element is written once with a plain store (no atomics, no zero-fill: the same
+ * bits every run).  Refused: H or W not a multiple of p, ld < D, an unknown dtype, tensors of more than 2^31 elements. */
+DL_API int dl_patch_embed_dgrad(const void* dtok, int dtype, int64_t ld, const float* w, float* dimg, int64_t B, int64_t C,
+                                int64_t H, int64_t W, int64_t p, int64_t D, dl_stream_t stream);
 /* timestep_embedding nn.py:106-114: out[b,:] = [cos(t f_i) | sin(t f_i)], bf16 [B, dim] (dim even) */
 DL_API int dl_timestep_embedding(const float* t, void* out, int64_t B, int64_t dim, float max_period,
                                  dl_stream_t stream);

@@ -156,3 +156,10 @@ struct DlWgCapScope {
   ~DlWgCapScope() { dl_set_wg_cap(saved); }
 };
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// grid of an element-wise grid-stride kernel over nvec vectors
+static inline int ew_grid(int64_t nvec, int threads = 256) {
+  int64_t g = (nvec + threads - 1) / threads;
+  if (g > 2048) g = 2048;  // 256 CUs x 8 blocks, grid-stride beyond that
+  if (g < 1) g = 1;
+  return (int)g;
+}

@@ -259,38 +259,6 @@ class GaussianDiffusion(Diffusion):
         return self.sampler.step(model_prediction=prediction, timesteps=timesteps, xt=model_inputs["x"], clamp_x=clamp_x,
                                  **extra, **sampler_args)
 
-    def compute_loss(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None = None, extra_losses=[],
-                     extra_args: dict[str, Any] = {}) -> dict[str, Tensor]:
-        if self._rows_head:
-            return self._compute_loss_rows(model, model_inputs, timesteps, noise, extra_losses, extra_args)
-        if self._target != "epsilon" or self.loss_weight is not None:
-            return self._compute_loss_gd(model, model_inputs, timesteps, noise, extra_losses, extra_args)
-        if self.sampler.learned_variance:
-            return self._compute_loss_learned_variance(model, model_inputs, timesteps, noise, extra_losses, extra_args)
-        model_inputs["x"], noise = self.add_noise(model_inputs["x"], timesteps, noise)
-        prediction = model(**model_inputs, timesteps=self._remap(timesteps))["x"]
-        loss_dict = {"loss": mse_head(prediction, noise, None, ops.LOSS_EPS)}
-        for extra_loss in extra_losses:
-            loss_dict[extra_loss.name] = extra_loss(**extra_args)
-        return loss_dict
-
-    def _compute_loss_learned_variance(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None, extra_losses,
-                                       extra_args: dict[str, Any]) -> dict[str, Tensor]:
-        """L_hybrid of Nichol & Dhariwal (2021), eq. 16, for a [B, 2C, ...] denoiser (the reference leaves it as a TODO,
-        gaussian_diffusion.py:267): "loss" = the usual MSE on the mean half, "vb" = vlb_weight * the variational bound in bits per
-        dimension, which trains the variance half only.  The trainer sums the dict and logs each entry."""
-        x0 = model_inputs["x"].float().contiguous()  # kept: add_noise's result replaces model_inputs["x"]
-        model_inputs["x"], noise = self.add_noise(x0, timesteps, noise)
-        xt = model_inputs["x"]
-        prediction = model(**model_inputs, timesteps=self._remap(timesteps))["x"]
-        self.sampler._check_halves(prediction, xt)
-        mse, vb = hybrid_head(prediction, noise, x0, xt, to_device(timesteps, xt.device, torch.int32), self.sampler._tables(xt.device),
-                              ops.MEAN_TYPES[self.sampler.mean_type], ops.VAR_MODES[self.sampler.var_type])
-        loss_dict = {"loss": mse, "vb": self.vlb_weight * vb}
-        for extra_loss in extra_losses:
-            loss_dict[extra_loss.name] = extra_loss(**extra_args)
-        return loss_dict
-
     def _weight(self, device: torch.device) -> Tensor | None:
         if self.loss_weight is None:
             return None
@@ -298,31 +266,49 @@ class GaussianDiffusion(Diffusion):
             self._dev_weight[device] = f32_table(self.loss_weight, device)
         return self._dev_weight[device]
 
-    def _compute_loss_gd(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None, extra_losses,
-                         extra_args: dict[str, Any]) -> dict[str, Tensor]:
-        """the loss of the parameterisation the sampler reads (loss_target="mean_type": x0, the posterior mean or v as the regression
-        target, formed inside the kernel) and / or a per-timestep weight on it.  Same keys as the other two paths: "loss", and "vb" for
-        a learned-variance model, whose bound derives its frozen mean from the same parameterisation and carries no weight.  (The
-        constructor refuses the one form in which that parameterisation would differ from the sampler's mean_type.)"""
-        x0 = model_inputs["x"].float().contiguous()
+    def compute_loss(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None = None, extra_losses=[],
+                     extra_args: dict[str, Any] = {}) -> dict[str, Tensor]:
+        """One of four heads, with the same keys from each: "loss", and "vb" for a learned-variance model.
+        - the row head (`_rows_losses`): loss_type="vlb" and / or a loss-aware timestep sampler;
+        - `gd_head`: the loss of the parameterisation the sampler reads (loss_target="mean_type": x0, the posterior mean or v as the
+          regression target, formed inside the kernel) and / or a per-timestep weight on it.  The bound of a learned-variance model
+          derives its frozen mean from the same parameterisation and carries no weight.  (The constructor refuses the one form in
+          which that parameterisation would differ from the sampler's mean_type.)
+        - `hybrid_head`: L_hybrid of Nichol & Dhariwal (2021), eq. 16, for a [B, 2C, ...] denoiser (the reference leaves it as a TODO,
+          gaussian_diffusion.py:267): "loss" = the usual MSE on the mean half, "vb" = vlb_weight * the variational bound in bits per
+          dimension, which trains the variance half only.  The trainer sums the dict and logs each entry.
+        - `mse_head`: the reference's loss, which reads neither x0 nor xt, so no copy of x0 is kept."""
+        learned = self.sampler.learned_variance
+        gd = self._target != "epsilon" or self.loss_weight is not None
+        plain = not (self._rows_head or gd or learned)
+        x0 = model_inputs["x"]
+        if not plain:
+            x0 = x0.float().contiguous()  # kept: add_noise's result replaces model_inputs["x"]
         model_inputs["x"], noise = self.add_noise(x0, timesteps, noise)
         xt = model_inputs["x"]
         prediction = model(**model_inputs, timesteps=self._remap(timesteps))["x"]
-        t = to_device(timesteps, xt.device, torch.int32)
-        args = (t, self.sampler._tables(xt.device), ops.MEAN_TYPES[self._target], self._weight(xt.device))
-        if self.sampler.learned_variance:
+        if not plain:
+            t = to_device(timesteps, xt.device, torch.int32)
+        if learned:
             self.sampler._check_halves(prediction, xt)
-            mse, vb = gd_head(prediction, noise, x0, xt, *args, ops.VAR_MODES[self.sampler.var_type])
+        if self._rows_head:
+            loss_dict = self._rows_losses(prediction, noise, x0, xt, t)
+        elif gd:
+            out = gd_head(prediction, noise, x0, xt, t, self.sampler._tables(xt.device), ops.MEAN_TYPES[self._target],
+                          self._weight(xt.device), ops.VAR_MODES[self.sampler.var_type] if learned else ops.VAR_FIXED)
+            loss_dict = {"loss": out[0], "vb": self.vlb_weight * out[1]} if learned else {"loss": out}
+        elif learned:
+            mse, vb = hybrid_head(prediction, noise, x0, xt, t, self.sampler._tables(xt.device), ops.MEAN_TYPES[self.sampler.mean_type],
+                                  ops.VAR_MODES[self.sampler.var_type])
             loss_dict = {"loss": mse, "vb": self.vlb_weight * vb}
         else:
-            loss_dict = {"loss": gd_head(prediction, noise, x0, xt, *args, ops.VAR_FIXED)}
+            loss_dict = {"loss": mse_head(prediction, noise, None, ops.LOSS_EPS)}
         for extra_loss in extra_losses:
             loss_dict[extra_loss.name] = extra_loss(**extra_args)
         return loss_dict
 
-    def _compute_loss_rows(self, model, model_inputs, timesteps: Tensor, noise: Tensor | None, extra_losses,
-                           extra_args: dict[str, Any]) -> dict[str, Tensor]:
-        """the losses of `_compute_loss_gd` through the row head (loss_type="vlb" and / or a loss-aware timestep sampler; Nichol &
+    def _rows_losses(self, prediction: Tensor, noise: Tensor, x0: Tensor, xt: Tensor, t: Tensor) -> dict[str, Tensor]:
+        """the losses of `gd_head` through the row head (loss_type="vlb" and / or a loss-aware timestep sampler; Nichol &
         Dhariwal 2021, sec. 3.3): every sample's loss is multiplied by imp[t_b] = 1 / (T p[t_b]) -- "loss" and "vb" alike, as IDDPM
         weights the whole per-sample loss -- and, when the prediction requires grad, the step's (t_b, total_b) pairs enter the
         sampler's history with one launch (all ranks' pairs under data parallel).  total_b is the sample's loss before that weight:
@@ -330,14 +316,7 @@ class GaussianDiffusion(Diffusion):
         flowing into the mean output too.  Under no_grad the history is not touched: a validation batch drawn from the current
         distribution with the same weights is an unbiased estimate of the uniform loss.  The step's detached per-sample tensors stay
         on the device as `last_terms`; no device value is read back."""
-        x0 = model_inputs["x"].float().contiguous()
-        model_inputs["x"], noise = self.add_noise(x0, timesteps, noise)
-        xt = model_inputs["x"]
-        prediction = model(**model_inputs, timesteps=self._remap(timesteps))["x"]
-        t = to_device(timesteps, xt.device, torch.int32)
         learned = self.sampler.learned_variance
-        if learned:
-            self.sampler._check_halves(prediction, xt)
         state = self.timestep_sampler_state
         imp = None
         if state is not None:
@@ -356,8 +335,6 @@ class GaussianDiffusion(Diffusion):
         self.last_terms = {"t": t, **{k: out[k].detach() for k in ("mse", "vb", "total") if k in out}}
         if state is not None and prediction.requires_grad:
             state.update(t, self.last_terms["total"])
-        for extra_loss in extra_losses:
-            loss_dict[extra_loss.name] = extra_loss(**extra_args)
         return loss_dict
 
     def add_noise(self, x: Tensor, timesteps: Tensor, noise: Tensor | None = None) -> tuple[Tensor, Tensor]:

@@ -30,22 +30,17 @@ class DDIM(DDPM):
         if self.learned_variance:  # the 2C prediction's variance half is discarded (ddim.py:89); the mean half is read in place
             self._check_halves(model_prediction, xt)
         noise = torch.randn_like(xt)  # ddim.py:63
-        pred = model_prediction.float().contiguous()
-        pu = None if prediction_uncond is None else prediction_uncond.float().contiguous()
+        pred, pu, x, t, mul, thr = self._guided(model_prediction, prediction_uncond, guidance_scale, xt, timesteps, tab, coefs,
+                                                guidance_rescale, dynamic_threshold, threshold_max)
+        mean_type, var_mode = _MEAN.index(self.mean_type), ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED)
         if guidance_rescale > 0 or dynamic_threshold is not None:  # this project's: see `DDPM._guided`
-            pred, pu, x, t, mul, thr = self._guided(model_prediction, prediction_uncond, guidance_scale, xt, timesteps, tab, coefs,
-                                                    guidance_rescale, dynamic_threshold, threshold_max)
-            xp, x0, mean, std, lp = ops.ddim_step_g(pred, pu, guidance_scale, mul, thr, x, noise, t, tab, coefs,
-                                                    _MEAN.index(self.mean_type), ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED),
+            xp, x0, mean, std, lp = ops.ddim_step_g(pred, pu, guidance_scale, mul, thr, x, noise, t, tab, coefs, mean_type, var_mode,
                                                     clamp_x, eta)
         elif self.mean_type == "v":
-            xp, x0, mean, std, lp = ops.ddim_step_v(pred, pu, guidance_scale, xt.float().contiguous(), noise,
-                                                    timesteps.to(torch.int32).contiguous(), tab,
-                                                    ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED), clamp_x, eta)
+            xp, x0, mean, std, lp = ops.ddim_step_v(pred, pu, guidance_scale, x, noise, t, tab, var_mode, clamp_x, eta)
         else:
-            xp, x0, mean, std, lp = ops.ddim_step(pred, pu, guidance_scale, xt.float().contiguous(), noise,
-                                                  timesteps.to(torch.int32).contiguous(), tab, coefs, _MEAN.index(self.mean_type),
-                                                  clamp_x, eta, halves=self.learned_variance)
+            xp, x0, mean, std, lp = ops.ddim_step(pred, pu, guidance_scale, x, noise, t, tab, coefs, mean_type, clamp_x, eta,
+                                                  halves=self.learned_variance)
         out = StepResult(x_prev=xp, estimated_x0=x0, x_prev_mean=mean)
         if eta > 0:
             out["x_prev_std"] = std

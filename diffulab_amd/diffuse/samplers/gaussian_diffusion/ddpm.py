@@ -76,7 +76,8 @@ class DDPM(GaussianSampler):
     def _guided(self, model_prediction: Tensor, prediction_uncond: Tensor | None, guidance_scale: float, xt: Tensor,
                 timesteps: Tensor, tab: Tensor, coefs: Tensor, guidance_rescale: float, dynamic_threshold: float | None,
                 threshold_max: float | None):
-        """the per-sample device scalars of a guided step, two launches that materialise nothing the size of the image:
+        """the arguments of a step in the form the kernels read, and the per-sample device scalars of a guided one (None at the
+        defaults, which launch nothing), two launches that materialise nothing the size of the image:
         cfg_mul, the CFG-rescale factor (Lin et al. 2023) of the combined prediction's mean half -- only where the step is guided;
         x0_thr, the dynamic threshold (Saharia et al. 2022) of the x0 the step kernel will form from the same arguments.
         -> (pred, pred_uncond, xt, t) in the form the kernels read, cfg_mul or None, x0_thr or None"""
@@ -98,32 +99,19 @@ class DDPM(GaussianSampler):
         """guidance_rescale / dynamic_threshold / threshold_max (this project's): see `_guided`.  At their defaults the call below is
         what it was."""
         noise = torch.randn_like(xt)  # ddpm.py:302 (drawn for every t, masked at t == 0)
-        if guidance_rescale > 0 or dynamic_threshold is not None:
-            if self.learned_variance:
-                self._check_halves(model_prediction, xt)
-            tab = self._tables(xt.device)
-            pred, pu, x, t, mul, thr = self._guided(model_prediction, prediction_uncond, guidance_scale, xt, timesteps, tab, tab[2:4],
-                                                    guidance_rescale, dynamic_threshold, threshold_max)
-            xp, x0, mean, std, lp = ops.ddpm_step_g(pred, pu, guidance_scale, mul, thr, x, noise, t, tab, _MEAN.index(self.mean_type),
-                                                    ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED), clamp_x)
-            return StepResult(x_prev=xp, estimated_x0=x0, x_prev_mean=mean, x_prev_std=std, logprob=lp)
-        if self.mean_type == "v":  # one entry point for [B, C] and [B, 2C] predictions; `_tables` follows var_type
-            if self.learned_variance:
-                self._check_halves(model_prediction, xt)
-            xp, x0, mean, std, lp = ops.ddpm_step_v(
-                model_prediction.float().contiguous(), None if prediction_uncond is None else prediction_uncond.float().contiguous(),
-                guidance_scale, xt.float().contiguous(), noise, timesteps.to(torch.int32).contiguous(), self._tables(xt.device),
-                ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED), clamp_x)
-            return StepResult(x_prev=xp, estimated_x0=x0, x_prev_mean=mean, x_prev_std=std, logprob=lp)
         if self.learned_variance:  # `_tables` rows 4, 5 are then (posterior_log_variance_clipped, betas)
             self._check_halves(model_prediction, xt)
-            xp, x0, mean, std, lp = ops.ddpm_step_lv(
-                model_prediction.float().contiguous(), None if prediction_uncond is None else prediction_uncond.float().contiguous(),
-                guidance_scale, xt.float().contiguous(), noise, timesteps.to(torch.int32).contiguous(), self._tables(xt.device),
-                _MEAN.index(self.mean_type), ops.VAR_MODES[self.var_type], clamp_x)
-            return StepResult(x_prev=xp, estimated_x0=x0, x_prev_mean=mean, x_prev_std=std, logprob=lp)
-        xp, x0, mean, std, lp = ops.ddpm_step(
-            model_prediction.float().contiguous(), None if prediction_uncond is None else prediction_uncond.float().contiguous(),
-            guidance_scale, xt.float().contiguous(), noise, timesteps.to(torch.int32).contiguous(), self._tables(xt.device),
-            _MEAN.index(self.mean_type), clamp_x)
+        tab = self._tables(xt.device)
+        pred, pu, x, t, mul, thr = self._guided(model_prediction, prediction_uncond, guidance_scale, xt, timesteps, tab, tab[2:4],
+                                                guidance_rescale, dynamic_threshold, threshold_max)
+        mean_type, var_mode = _MEAN.index(self.mean_type), ops.VAR_MODES.get(self.var_type, ops.VAR_FIXED)
+        if guidance_rescale > 0 or dynamic_threshold is not None:
+            out = ops.ddpm_step_g(pred, pu, guidance_scale, mul, thr, x, noise, t, tab, mean_type, var_mode, clamp_x)
+        elif self.mean_type == "v":  # one entry point for [B, C] and [B, 2C] predictions; `_tables` follows var_type
+            out = ops.ddpm_step_v(pred, pu, guidance_scale, x, noise, t, tab, var_mode, clamp_x)
+        elif self.learned_variance:
+            out = ops.ddpm_step_lv(pred, pu, guidance_scale, x, noise, t, tab, mean_type, var_mode, clamp_x)
+        else:
+            out = ops.ddpm_step(pred, pu, guidance_scale, x, noise, t, tab, mean_type, clamp_x)
+        xp, x0, mean, std, lp = out
         return StepResult(x_prev=xp, estimated_x0=x0, x_prev_mean=mean, x_prev_std=std, logprob=lp)

@@ -379,9 +379,23 @@ def euler_maruyama_step(x, v, v_uncond, guidance, noise, x_prev_in, t_curr, t_pr
     return xp, mean, x0, lp, std
 
 
+def _check_pred(pred, pred_uncond, xt, halves: bool) -> None:
+    """a Gaussian step's pred / pred_uncond are [B, C, ...] or, halves, the [B, 2C, ...] prediction of a learned-variance model"""
+    assert pred.numel() == (2 if halves else 1) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+
+
+def _step_out(xt, out, eta: float | None = None):
+    """(x_prev, x0, mean, std, logprob) of a Gaussian step: `out` where given, else allocated here; DDIM (eta given) has std and
+    logprob only when eta > 0"""
+    if out is not None:
+        return out
+    n = 5 if eta is None or eta > 0 else 3
+    return (*(torch.empty_like(xt) for _ in range(n)), *(None,) * (5 - n))
+
+
 def ddpm_step(pred, pred_uncond, guidance, xt, noise, t, tables, mean_type: int, clamp_x: bool):
     B = xt.shape[0]
-    xp, x0, mean, std, lp = (torch.empty_like(xt) for _ in range(5))
+    xp, x0, mean, std, lp = _step_out(xt, None)
     _call("dl_ddpm_step", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables),
           tables.shape[1], mean_type, int(clamp_x), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
     return xp, x0, mean, std, lp
@@ -391,8 +405,8 @@ def ddpm_step_lv(pred, pred_uncond, guidance, xt, noise, t, tables, mean_type: i
     """learned variances: pred / pred_uncond are [B, 2C, ...], read in place; tables f32 [6, T] with rows 4, 5 =
     posterior_log_variance_clipped, betas; out: the five [B, C, ...] outputs, allocated here when None"""
     B = xt.shape[0]
-    assert pred.numel() == 2 * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
-    xp, x0, mean, std, lp = (torch.empty_like(xt) for _ in range(5)) if out is None else out
+    _check_pred(pred, pred_uncond, xt, True)
+    xp, x0, mean, std, lp = _step_out(xt, out)
     _call("dl_ddpm_step_lv", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables),
           tables.shape[1], mean_type, var_mode, int(clamp_x), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
     return xp, x0, mean, std, lp
@@ -402,13 +416,8 @@ def ddim_step(pred, pred_uncond, guidance, xt, noise, t, tables, coefs, mean_typ
               halves: bool = False, out=None):
     """halves: pred / pred_uncond are the [B, 2C, ...] prediction of a learned-variance model; its mean half is read in place"""
     B = xt.shape[0]
-    assert pred.numel() == (2 if halves else 1) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
-    if out is not None:
-        xp, x0, mean, std, lp = out
-    else:
-        xp, x0, mean = (torch.empty_like(xt) for _ in range(3))
-        std = torch.empty_like(xt) if eta > 0 else None
-        lp = torch.empty_like(xt) if eta > 0 else None
+    _check_pred(pred, pred_uncond, xt, halves)
+    xp, x0, mean, std, lp = _step_out(xt, out, eta)
     _call("dl_ddim_step_lv" if halves else "dl_ddim_step", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables),
           tables.shape[1], mean_type, _p(coefs), int(clamp_x), float(eta), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B,
           xt.numel() // B, _s())
@@ -418,8 +427,8 @@ def ddim_step(pred, pred_uncond, guidance, xt, noise, t, tables, coefs, mean_typ
 def ddpm_step_v(pred, pred_uncond, guidance, xt, noise, t, tables, var_mode: int, clamp_x: bool, out=None):
     """v-prediction: pred / pred_uncond [B, C, ...] and ddpm_step's tables (VAR_FIXED), or [B, 2C, ...] and ddpm_step_lv's"""
     B = xt.shape[0]
-    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
-    xp, x0, mean, std, lp = (torch.empty_like(xt) for _ in range(5)) if out is None else out
+    _check_pred(pred, pred_uncond, xt, var_mode != VAR_FIXED)
+    xp, x0, mean, std, lp = _step_out(xt, out)
     _call("dl_ddpm_step_v", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables), tables.shape[1],
           var_mode, int(clamp_x), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
     return xp, x0, mean, std, lp
@@ -428,13 +437,8 @@ def ddpm_step_v(pred, pred_uncond, guidance, xt, noise, t, tables, var_mode: int
 def ddim_step_v(pred, pred_uncond, guidance, xt, noise, t, tables, var_mode: int, clamp_x: bool, eta: float, out=None):
     """v-prediction: pred / pred_uncond [B, C, ...] (VAR_FIXED) or [B, 2C, ...], whose mean half is read in place; tables f32 [3, T]"""
     B = xt.shape[0]
-    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
-    if out is not None:
-        xp, x0, mean, std, lp = out
-    else:
-        xp, x0, mean = (torch.empty_like(xt) for _ in range(3))
-        std = torch.empty_like(xt) if eta > 0 else None
-        lp = torch.empty_like(xt) if eta > 0 else None
+    _check_pred(pred, pred_uncond, xt, var_mode != VAR_FIXED)
+    xp, x0, mean, std, lp = _step_out(xt, out, eta)
     _call("dl_ddim_step_v", _p(pred), _p(pred_uncond), float(guidance), _p(xt), _p(noise), _p(t), _p(tables), tables.shape[1],
           var_mode, int(clamp_x), float(eta), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
     return xp, x0, mean, std, lp
@@ -471,7 +475,7 @@ def x0_threshold(pred, pred_uncond, guidance, cfg_mul, xt, t, tables, coefs, mea
     form it from the same arguments (dl_x0_threshold); tables: the step's own (rows 0, 1 are read); coefs f32 [2, T]: the posterior-mean
     coefficients, needed for mean_type xprev only"""
     B = xt.shape[0]
-    assert pred.numel() == (2 if halves else 1) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    _check_pred(pred, pred_uncond, xt, halves)
     s = torch.empty(B, device=xt.device, dtype=torch.float32)
     lohi = torch.empty(B, 2, device=xt.device, dtype=torch.float32) if want_lohi else None
     _call("dl_x0_threshold", _p(pred), _p(pred_uncond), float(guidance), _p(cfg_mul), _p(xt), _p(t), _p(tables), tables.shape[1],
@@ -505,8 +509,8 @@ def ddpm_step_g(pred, pred_uncond, guidance, cfg_mul, x0_thr, xt, noise, t, tabl
     """any mean_type (v included) and var_mode: VAR_FIXED with pred [B, C, ...] and ddpm_step's tables, or a learned mode with
     [B, 2C, ...] and ddpm_step_lv's; cfg_mul / x0_thr f32 [B] or None"""
     B = xt.shape[0]
-    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
-    xp, x0, mean, std, lp = (torch.empty_like(xt) for _ in range(5)) if out is None else out
+    _check_pred(pred, pred_uncond, xt, var_mode != VAR_FIXED)
+    xp, x0, mean, std, lp = _step_out(xt, out)
     _call("dl_ddpm_step_g", _p(pred), _p(pred_uncond), float(guidance), _p(cfg_mul), _p(x0_thr), _p(xt), _p(noise), _p(t), _p(tables),
           tables.shape[1], mean_type, var_mode, int(clamp_x), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B, xt.numel() // B, _s())
     return xp, x0, mean, std, lp
@@ -516,13 +520,8 @@ def ddim_step_g(pred, pred_uncond, guidance, cfg_mul, x0_thr, xt, noise, t, tabl
                 clamp_x: bool, eta: float, out=None):
     """as ddpm_step_g, with ddim_step's tables f32 [3, T] and coefs (needed for mean_type xprev only)"""
     B = xt.shape[0]
-    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
-    if out is not None:
-        xp, x0, mean, std, lp = out
-    else:
-        xp, x0, mean = (torch.empty_like(xt) for _ in range(3))
-        std = torch.empty_like(xt) if eta > 0 else None
-        lp = torch.empty_like(xt) if eta > 0 else None
+    _check_pred(pred, pred_uncond, xt, var_mode != VAR_FIXED)
+    xp, x0, mean, std, lp = _step_out(xt, out, eta)
     _call("dl_ddim_step_g", _p(pred), _p(pred_uncond), float(guidance), _p(cfg_mul), _p(x0_thr), _p(xt), _p(noise), _p(t), _p(tables),
           tables.shape[1], mean_type, var_mode, _p(coefs), int(clamp_x), float(eta), _p(xp), _p(x0), _p(mean), _p(std), _p(lp), B,
           xt.numel() // B, _s())
@@ -546,7 +545,7 @@ def dpmpp_2m_step(pred, pred_uncond, guidance, cfg_mul, x0_thr, xt, x0_last, t, 
     """-> (x_prev, x0_est) with x_prev = a xt + b x0 + c x0_last, x0 formed as ddim_step_g forms it (tables f32 [>= 2, T]: ddim_step's);
     x0_last None needs c == 0; mean_type xprev is refused"""
     B = xt.shape[0]
-    assert pred.numel() == (1 if var_mode == VAR_FIXED else 2) * xt.numel() and (pred_uncond is None or pred_uncond.numel() == pred.numel())
+    _check_pred(pred, pred_uncond, xt, var_mode != VAR_FIXED)
     assert x0_last is None or x0_last.numel() == xt.numel()
     xp, x0 = (torch.empty_like(xt) for _ in range(2)) if out is None else out
     _call("dl_dpmpp_2m_step", _p(pred), _p(pred_uncond), float(guidance), _p(cfg_mul), _p(x0_thr), _p(xt), _p(x0_last), _p(t), _p(tables),

@@ -72,7 +72,7 @@ def step_times(B, late=False):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the selection
-STAGE = 8192  # SEL_STAGE of csrc/elementwise.hip: rows up to here keep their keys in LDS, longer rows recompute them in every pass
+STAGE = 8192  # SEL_STAGE of csrc/sampler.hip: rows up to here keep their keys in LDS, longer rows recompute them in every pass
 SELECT_N = [1, 2, 105, 255, 256, 257, 1028, 4099, STAGE, STAGE + 1]
 
 

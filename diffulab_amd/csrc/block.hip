@@ -49,6 +49,20 @@ extern "C" int dl_memset_zero(void* p, int64_t bytes, dl_stream_t stream) {
     if (rc__ != DL_OK) return rc__; \
   } while (0)
 
+// MLP-up GEMM + SwiGLU: the activation-stationary kernel (csrc/gemm_stationary.hip) where it serves the shape and only h is stored
+// (inference, and training blocks whose backward recomputes u), else the persistent tiles of dl_gemm_nt_swiglu (bit-identical
+// outputs); DL_ERR_UNSUPPORTED when neither does.  With u stored as well the launch is bound by its 600 MB of stores and the
+// stationary form was not reliably faster: that case keeps the tiles.
+static int mlp_up_swiglu(const dl_dit_block_t* b, int train, dl_stream_t stream) {
+  const int64_t D = b->D, F = b->F, M = b->B * b->N;
+  void* u = train ? P(U) : nullptr;
+  if (!u) {
+    const int rc = dl_gemm_nt_swiglu_stationary(P(XM2), D, P(W_UP_PERM), b->ldw_d, u, 2 * F, P(H), F, M, F, D, 0, stream);
+    if (rc != DL_ERR_UNSUPPORTED) return rc;
+  }
+  return dl_gemm_nt_swiglu(P(XM2), D, P(W_UP_PERM), b->ldw_d, u, 2 * F, P(H), F, M, F, D, stream);
+}
+
 extern "C" int dl_dit_block_fwd(const dl_dit_block_t* b, int train, dl_stream_t stream) {
   DL_CHECK_ARG(b, "dl_dit_block_fwd: null block");
   const int64_t B = b->B, N = b->N, D = b->D, H = b->H, F = b->F, M = B * N, dh = D / H;
@@ -62,7 +76,10 @@ extern "C" int dl_dit_block_fwd(const dl_dit_block_t* b, int train, dl_stream_t 
     DL_CHECK_ARG(P(V) == nullptr && P(NEXT_X) && P(NEXT_XM) && P(NEXT_SCALE) && P(NEXT_SHIFT) && P(NEXT_MEAN) && P(NEXT_RSTD),
                  "dl_dit_block_fwd: row_gemms needs V in place and the DL_BLK_NEXT_* slots");
     if (P(SSQ)) {  // QK-norm statistics leave with the qkv GEMM, the norm + RoPE are applied as the attention stages q and k
-      RUN(dl_gemm_nt_ssq(P(XM1), D, P(W_QKV), b->ldw_d, P(QKV), 3 * D, M, 3 * D, D, (float*)P(SSQ), 2, stream));
+      // (activation panel in registers for a short contraction, csrc/gemm_stationary.hip; every other shape: the 256 x 384 tiles)
+      int rq = dl_gemm_nt_ssq_stationary(P(XM1), D, P(W_QKV), b->ldw_d, P(QKV), 3 * D, M, 3 * D, D, (float*)P(SSQ), 2, 0, stream);
+      if (rq == DL_ERR_UNSUPPORTED) rq = dl_gemm_nt_ssq(P(XM1), D, P(W_QKV), b->ldw_d, P(QKV), 3 * D, M, 3 * D, D, (float*)P(SSQ), 2, stream);
+      if (rq != DL_OK) return rq;
       // (inference: the normalised q, k and rrms feed only the backward -- not written)
       RUN(dl_attn_fwd_qkn(P(QKV), (const float*)P(SSQ), (const float*)P(QN_SCALE), (const float*)P(KN_SCALE), (const float*)P(ROPE_COS),
                           (const float*)P(ROPE_SIN), 1e-6f, b->rot, train ? P(Q) : nullptr, train ? P(K) : nullptr,
@@ -82,7 +99,7 @@ extern "C" int dl_dit_block_fwd(const dl_dit_block_t* b, int train, dl_stream_t 
     RUN(dl_ln_modulate_gemm_fwd(P(A), D, P(W_PROJ), b->ldw_d, M, D, P(X_IN), P(GATE1), b->ld_mod, (const float*)P(LN2_W),
                                 (const float*)P(LN2_B), P(SCALE2), P(SHIFT2), b->ld_mod, N, b->eps, P(T1), P(X1), P(XM2), (float*)P(MEAN2),
                                 (float*)P(RSTD2), D, stream));
-    RUN(dl_gemm_nt_swiglu(P(XM2), D, P(W_UP_PERM), b->ldw_d, train ? P(U) : nullptr, 2 * F, P(H), F, M, F, D, stream));
+    RUN(mlp_up_swiglu(b, train, stream));
     RUN(dl_ln_modulate_gemm_fwd(P(H), F, P(W_DOWN), b->ldw_f, M, F, P(X1), P(GATE2), b->ld_mod, (const float*)P(NEXT_LN_W),
                                 (const float*)P(NEXT_LN_B), P(NEXT_SCALE), P(NEXT_SHIFT), b->ld_mod, N, b->next_eps, P(T2), P(NEXT_X),
                                 P(NEXT_XM), (float*)P(NEXT_MEAN), (float*)P(NEXT_RSTD), D, stream));
@@ -106,7 +123,7 @@ extern "C" int dl_dit_block_fwd(const dl_dit_block_t* b, int train, dl_stream_t 
   RUN(dl_ln_modulate_fwd(P(X_IN), (const float*)P(LN2_W), (const float*)P(LN2_B), P(SCALE2), P(SHIFT2), b->ld_mod, N, b->eps, P(XM2),
                          (float*)P(MEAN2), (float*)P(RSTD2), P(T1), P(GATE1), b->ld_mod, P(X1), M, D, stream));
   // (U == NULL in a training block: the backward recomputes the pre-activations, dl_mlp_dswiglu_recompute)
-  int rc = dl_gemm_nt_swiglu(P(XM2), D, P(W_UP_PERM), b->ldw_d, train ? P(U) : nullptr, 2 * F, P(H), F, M, F, D, stream);
+  int rc = mlp_up_swiglu(b, train, stream);
   if (rc == DL_ERR_UNSUPPORTED) {  // small / ragged shapes: the unfused pair
     DL_CHECK_ARG(P(U), "dl_dit_block_fwd: this shape has no fused MLP-up kernel and needs the U buffer");
     RUN(dl_gemm_nt(P(XM2), D, P(W_UP), b->ldw_d, P(U), 2 * F, M, 2 * F, D, nullptr, DL_ACT_NONE, DL_BF16, nullptr, nullptr, 0, nullptr, 0, 1,

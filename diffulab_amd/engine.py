@@ -840,7 +840,8 @@ class DiTEngine:
         ops.gemm_nt(a["a"], sh[nm["proj"] + ".weight|f"], a["t1"])
         ops.ln_modulate_fwd(xin, self.P(nm["n2"] + ".weight"), self.P(nm["n2"] + ".bias"), m.col(3), m.col(4), m.rows, 1e-5, a["xm2"],
                             a["mean2"], a["rstd2"], t=a["t1"], gate=m.col(2), x_out=a["x1"])
-        if not ops.gemm_nt_swiglu(a["xm2"], sh[nm["up"] + ".weight|g"], a["u"] if self._train else None, a["h"]):
+        u = a["u"] if self._train else None  # (stationary: the h-only launch takes the panel-in-registers kernel, csrc/gemm_stationary.hip)
+        if not ops.gemm_nt_swiglu(a["xm2"], sh[nm["up"] + ".weight|g"], u, a["h"], stationary=u is None):
             assert a["u"] is not None, "the recompute mode is only chosen for shapes the fused MLP-up kernel serves"
             ops.gemm_nt(a["xm2"], sh[nm["up"] + ".weight|f"], a["u"])  # small / ragged shapes: unfused pair
             ops.swiglu_fwd(a["u"], a["h"])
@@ -987,7 +988,7 @@ class DiTEngine:
             a, xin, pre, mo = lay(i), xbuf(i), f"layers.{i}.", i * 6 * D
             if "ssq_all" in w:
                 ssq = w["ssq_all"][i]
-                _must(ops.gemm_nt_ssq(a["xm1"], sh[pre + "attention.qkv.weight|f"], a["qkv"], ssq))
+                _must(ops.gemm_nt_ssq(a["xm1"], sh[pre + "attention.qkv.weight|f"], a["qkv"], ssq, stationary=True))
                 ops.attn_fwd_qkn(a["qkv"], ssq, self.P(pre + "attention.qk_norm.query_norm.scale"),
                                  self.P(pre + "attention.qk_norm.key_norm.scale"), cos, sin, a["q"] if train else None,
                                  a["k"] if train else None, a["rrms"] if train else None, a["a"], a["lse"], B, Hh, N, 64, rot, 64**-0.5)
@@ -1006,7 +1007,8 @@ class DiTEngine:
             _must(ops.ln_modulate_gemm_fwd(a["a"], sh[pre + "attention.proj_out.weight|f"], xin, mod[:, mo + 2 * D : mo + 3 * D],
                                             self.P(pre + "norm_2.weight"), self.P(pre + "norm_2.bias"), mod[:, mo + 3 * D : mo + 4 * D],
                                             mod[:, mo + 4 * D : mo + 5 * D], N, 1e-5, a["t1"], a["x1"], a["xm2"], a["mean2"], a["rstd2"]))
-            if not ops.gemm_nt_swiglu(a["xm2"], sh[pre + "mlp_input.0.weight|g"], a["u"] if train else None, a["h"]):
+            u = a["u"] if train else None
+            if not ops.gemm_nt_swiglu(a["xm2"], sh[pre + "mlp_input.0.weight|g"], u, a["h"], stationary=u is None):
                 raise RuntimeError("the row-complete path needs the fused MLP-up kernel")
             if i + 1 < L:
                 nx, mn, nxt = lay(i + 1), (i + 1) * 6 * D, f"layers.{i + 1}."

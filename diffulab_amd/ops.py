@@ -617,11 +617,15 @@ def gemm_nt_pair(problems: list[tuple]) -> None:
     _call("dl_gemm_nt_pair", ctypes.addressof(arr), len(problems), _s())
 
 
-def gemm_nt_swiglu(x: Tensor, w_perm: Tensor, u: Tensor | None, h: Tensor) -> bool:
+def gemm_nt_swiglu(x: Tensor, w_perm: Tensor, u: Tensor | None, h: Tensor, stationary: bool = False, max_workgroups: int = 0) -> bool:
     """fused MLP-up GEMM + SwiGLU; u=None skips the pre-activation store (inference).  False when the shape has no fused
-    kernel (caller falls back to gemm_nt + swiglu_fwd)"""
-    rc = lib().cdll.dl_gemm_nt_swiglu(_p(x), x.stride(0), _p(w_perm), w_perm.stride(0), _p(u), u.stride(0) if u is not None else 0, _p(h),
-                                      h.stride(0), x.shape[0], h.shape[1], x.shape[1], _s())
+    kernel (caller falls back to gemm_nt + swiglu_fwd).  stationary: try dl_gemm_nt_swiglu_stationary first (activation panel in
+    registers, K <= 512; bit-identical outputs; max_workgroups as in the header) and keep the persistent tiles for shapes it refuses"""
+    args = (_p(x), x.stride(0), _p(w_perm), w_perm.stride(0), _p(u), u.stride(0) if u is not None else 0, _p(h), h.stride(0), x.shape[0],
+            h.shape[1], x.shape[1])
+    rc = lib().cdll.dl_gemm_nt_swiglu_stationary(*args, int(max_workgroups), _s()) if stationary else -3
+    if rc == -3:
+        rc = lib().cdll.dl_gemm_nt_swiglu(*args, _s())
     if rc == -3:
         return False
     if rc != 0:
@@ -964,12 +968,15 @@ def attn_fwd_qkv(q, k, qkv, out, lse, B, H, N, dh, scale):
           float(scale), _s())
 
 
-def gemm_nt_ssq(a, w_sh, out, ssq) -> bool:
+def gemm_nt_ssq(a, w_sh, out, ssq, stationary: bool = False, max_workgroups: int = 0) -> bool:
     """out[M, N] = a w_sh^T (bf16, persistent 256 x 384 tiles) + ssq[M, T] += row sums of squares of the first T = ssq.shape[1] 384-wide
     column tiles (ssq f32, zeroed by the caller): the qkv GEMM that also leaves the QK-RMSNorm statistics.  False: no such kernel for
     the shape (the caller keeps gemm_nt + qk_norm_rope_fwd)"""
-    return _maybe("dl_gemm_nt_ssq", _p(a), a.stride(0), _p(w_sh), w_sh.stride(0), _p(out), out.stride(0), a.shape[0], w_sh.shape[0],
-                  a.shape[1], _p(ssq), ssq.shape[1], _s())
+    args = (_p(a), a.stride(0), _p(w_sh), w_sh.stride(0), _p(out), out.stride(0), a.shape[0], w_sh.shape[0], a.shape[1], _p(ssq), ssq.shape[1])
+    # stationary: dl_gemm_nt_ssq_stationary first (activation panel in registers, K <= 512: the same `out` and ssq bits, ssq written with plain stores)
+    if stationary and _maybe("dl_gemm_nt_ssq_stationary", *args, int(max_workgroups), _s()):
+        return True
+    return _maybe("dl_gemm_nt_ssq", *args, _s())
 
 
 def attn_fwd_qkn(qkv, ssq, scale_q, scale_k, cos, sin, q, k, rrms, out, lse, B, H, N, dh, rot, scale, eps=1e-6):

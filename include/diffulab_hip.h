@@ -403,6 +403,15 @@ DL_API int dl_gemm_nt_pair(const dl_nt_problem_t* problems, int n, dl_stream_t s
  * dl_gemm_nt + dl_swiglu_fwd. */
 DL_API int dl_gemm_nt_swiglu(const void* X, int64_t ldx, const void* Wp, int64_t ldw, void* U, int64_t ldu, void* H,
                              int64_t ldh, int64_t M, int64_t F, int64_t K, dl_stream_t stream);
+/* dl_gemm_nt_swiglu with the ACTIVATION PANEL IN REGISTERS (csrc/gemm_stationary.hip): same operands, same contract, U, H bit-identical
+ * to dl_gemm_nt_swiglu on every shape both take.  For a short contraction and a wide output (the DiT MLP-up linear: K = 384, 2F = 3072):
+ * a workgroup holds 256 activation rows as MFMA fragments for its whole panel and streams only the weight through LDS.
+ * K % 64 == 0 and K <= 512, M % 256 == 0, F % 64 == 0 -- otherwise DL_ERR_UNSUPPORTED, nothing written.  max_workgroups == 0: one
+ * workgroup per CU (of the budget of dl_dit_block_t::max_workgroups inside a block call) and DL_ERR_UNSUPPORTED unless the M / 256
+ * panels fill at least 0.7 of their rounds on those workgroups; max_workgroups > 0: that many workgroups (at most the budget), each
+ * looping over its panels, whatever the fill. */
+DL_API int dl_gemm_nt_swiglu_stationary(const void* X, int64_t ldx, const void* Wp, int64_t ldw, void* U, int64_t ldu, void* H,
+                                        int64_t ldh, int64_t M, int64_t F, int64_t K, int max_workgroups, dl_stream_t stream);
 /* PackedSwiGLU MLP backward WITHOUT saved pre-activations (nn.py:478-486, mmdit.py:260-264): dU = [dH x3 silu'(x1) | dH silu(x1)]
  * with u = [x1 | x3] = X Wp^T RECOMPUTED per 256 x 128-unit tile (rounded to bf16 as the forward would have stored it) and
  * dH = dT W2t^T, neither of them written to memory.  X = the MLP input (modulated LayerNorm output) [M, K1], Wp = the row-permuted
@@ -616,6 +625,13 @@ DL_API int dl_attn_bwd_tok(const void* q, const void* k, const void* qkv, const 
  * (inputs of the backward kernels; all three NULL = inference, nothing of it is written).  N % 64 == 0 up to 256, dh = 64. */
 DL_API int dl_gemm_nt_ssq(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N,
                           int64_t K, float* ssq, int64_t ssq_tiles, dl_stream_t stream);
+/* dl_gemm_nt_ssq with the activation panel in registers (csrc/gemm_stationary.hip; shapes and max_workgroups as
+ * dl_gemm_nt_swiglu_stationary with N % 128 == 0 in place of F % 64 == 0): C bit-identical to dl_gemm_nt_ssq.  A wave owns whole rows, so
+ * ssq[m, t] is WRITTEN with a plain store (no atomics; the caller's zero fill is not needed, and harmless), summed in the grouping of
+ * dl_gemm_nt_ssq (two 192-column sums per tile, added last): bit-identical to it as well, and bit-reproducible run to run.  A last
+ * statistics tile narrower than 384 columns (N % 384 != 0) sums the columns that exist. */
+DL_API int dl_gemm_nt_ssq_stationary(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N,
+                                     int64_t K, float* ssq, int64_t ssq_tiles, int max_workgroups, dl_stream_t stream);
 DL_API int dl_attn_fwd_qkn(const void* qkv, const float* ssq, const float* scale_q, const float* scale_k, const float* cos,
                            const float* sin, float eps, int64_t rot, void* q_out, void* k_out, float* rrms, void* out, float* lse,
                            int64_t B, int64_t H, int64_t N, int64_t dh, float scale, dl_stream_t stream);

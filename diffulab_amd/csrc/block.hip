@@ -75,6 +75,11 @@ extern "C" int dl_dit_block_fwd(const dl_dit_block_t* b, int train, dl_stream_t 
     // GEMM the gated residual of the MLP branch and the LayerNorm that follows the block.
     DL_CHECK_ARG(P(V) == nullptr && P(NEXT_X) && P(NEXT_XM) && P(NEXT_SCALE) && P(NEXT_SHIFT) && P(NEXT_MEAN) && P(NEXT_RSTD),
                  "dl_dit_block_fwd: row_gemms needs V in place and the DL_BLK_NEXT_* slots");
+    if ((b->row_gemms & 8) && P(SSQ)) {
+      // the five launches below as ONE, every workgroup carrying whole samples through the block (csrc/block_fused.hip): same bits
+      const int rc = dl_dit_block_fwd_chain(b, train, stream);
+      if (rc != DL_ERR_UNSUPPORTED) return rc;
+    }
     if (P(SSQ)) {  // QK-norm statistics leave with the qkv GEMM, the norm + RoPE are applied as the attention stages q and k
       // (activation panel in registers for a short contraction, csrc/gemm_stationary.hip; every other shape: the 256 x 384 tiles)
       int rq = dl_gemm_nt_ssq_stationary(P(XM1), D, P(W_QKV), b->ldw_d, P(QKV), 3 * D, M, 3 * D, D, (float*)P(SSQ), 2, 0, stream);

@@ -743,7 +743,9 @@ class DiTEngine:
             # bit 1: QK-norm + RoPE in the qkv epilogue (measured slightly slower inside the step: opt-in); bit 2: the LayerNorm-affine
             # partials of all blocks are folded by ONE launch at the end of the backward (not with a gradient reducer attached: it
             # wants every block's range final as soon as the block is done)
-            blk.row_gemms = 1 | (2 if tuning.on("DL_ROW_GEMM_QK") else 0) | (4 if self.reducer is None else 0)
+            # bit 3: the forward as one per-sample chain launch where the library serves the block that way (csrc/block_fused.hip)
+            blk.row_gemms = (1 | (2 if tuning.on("DL_ROW_GEMM_QK") else 0) | (4 if self.reducer is None else 0)
+                             | (8 if tuning.on("DL_BLOCK_CHAIN") else 0))
         if train and self.grads is not None:
             g, dmod = w["wg"][i], w["dmod32"]
             blk.ld_dmod = dmod.stride(0)

@@ -957,6 +957,12 @@ def dit_block_fwd(blk, train: bool) -> None:
     _call("dl_dit_block_fwd", ctypes.addressof(blk), int(train), _s())
 
 
+def dit_block_fwd_chain(blk, train: bool) -> bool:
+    """the row-complete block forward as ONE per-sample chain launch (csrc/block_fused.hip; dl_dit_block_fwd takes it by itself when
+    bit 3 of blk.row_gemms is set); False when the library does not serve the block that way"""
+    return _maybe("dl_dit_block_fwd_chain", ctypes.addressof(blk), int(train), _s())
+
+
 def dit_block_bwd(blk, main_stream: int, side_stream: int, side_wgs: int) -> None:
     _call("dl_dit_block_bwd", ctypes.addressof(blk), main_stream, side_stream, int(side_wgs))
 

@@ -1179,7 +1179,9 @@ typedef struct dl_dit_block_t {
                                   * N == 256): LN1 is NOT run by dl_dit_block_fwd (XM1 / MEAN1 / RSTD1 come from the previous block's
                                   * MLP-down epilogue or the patch embedding) and the MLP branch's gated residual IS applied (NEXT_X);
                                   * bit 1: QK-norm + RoPE in the qkv GEMM's epilogue; bit 2: dl_dit_block_bwd leaves the LayerNorm-affine
-                                  * partials DWB1 / DWB2 unfolded (the caller folds all blocks at once: dl_reduce_rows_batched_f32) */
+                                  * partials DWB1 / DWB2 unfolded (the caller folds all blocks at once: dl_reduce_rows_batched_f32);
+                                  * bit 3: dl_dit_block_fwd runs the forward as one per-sample chain launch where
+                                  * dl_dit_block_fwd_chain serves the block (same bits; clear = the separate launches) */
   int64_t tn_slab_floats;        /* size of DL_BLK_TN_SLAB; with a slab the block's four weight gradients are ONE atomics-free launch
                                   * (dl_gemm_tn_group) issued on `side` once dqkv exists */
   int32_t max_workgroups;        /* > 0: workgroup budget of the block's persistent main-chain kernels (one workgroup per CU by default).
@@ -1190,6 +1192,11 @@ typedef struct dl_dit_block_t {
 /* forward of one block; train != 0 keeps the MLP pre-activations U for the backward.  The MLP branch's gated residual
  * (x1 + gate2 * t2) is NOT applied: it is the next block's (or the final LayerNorm's) pending triple. */
 DL_API int dl_dit_block_fwd(const dl_dit_block_t* blk, int train, dl_stream_t stream);
+/* the row_gemms forward of one block as ONE launch (csrc/block_fused.hip): every workgroup carries whole samples through the block's
+ * phases with workgroup-local synchronisation only; outputs are bit-identical to dl_dit_block_fwd's separate launches.
+ * DL_ERR_UNSUPPORTED unless row_gemms bit 0 is set, SSQ is given, V is in place, N == 256, D == 384, head_dim == 64 and F % 64 == 0.
+ * dl_dit_block_fwd calls it when row_gemms bit 3 is set and issues the separate launches when it declines. */
+DL_API int dl_dit_block_fwd_chain(const dl_dit_block_t* blk, int train, dl_stream_t stream);
 /* backward of one block on `main`; the weight-gradient GEMMs and LayerNorm-affine folds are issued on `side` behind events
  * (join `side` before the gradients are consumed; side_stream == main_stream issues everything inline on one stream);
  * side_workgroups caps the persistent wgrad workgroups (0 = one per CU) */

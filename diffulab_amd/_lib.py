@@ -25,7 +25,7 @@ _CTYPES = {
 }
 
 
-_VALUE_RETURNING = {"dl_version", "dl_mse_loss_partials", "dl_grad_sumsq"}  # every other int-returning entry point returns a status
+_VALUE_RETURNING = {"dl_version", "dl_mse_loss_partials", "dl_grad_sumsq", "dl_muon_orthogonalize"}  # every other int-returning entry point returns a status
 
 
 def _ctype_of(decl: str):

@@ -20,6 +20,7 @@ _ALIASES = {
     "diffulab.networks.UNetModel": "diffulab_amd.networks.denoisers.UNetModel",
     "torch.optim.AdamW": "diffulab_amd.training.FusedAdamW",  # same update rule, one launch over the flat arena
     "torch.optim.SGD": "diffulab_amd.training.FusedSGD",  # likewise
+    "torch.optim.Muon": "diffulab_amd.training.FusedMuon",  # Muon on the hidden matrices, AdamW on the rest: grouped launches over the arena
 }
 
 

@@ -9,8 +9,10 @@ There is no fallback path: a missing library or a CPU tensor raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -1240,6 +1242,123 @@ def scale_inplace(g, coef):
         raise RuntimeError("scale_inplace needs a contiguous f32 tensor")
     _call("dl_scale_inplace", _p(g), g.numel(), _p(coef), _s())
     return g
+
+
+# ------------------------------------------------------------------ Muon (csrc/muon.hip)
+MUON_MAT_FIELDS, MUON_CHUNK_FIELDS, MUON_CHUNK = 10, 3, 2048  # DL_MUON_* of include/diffulab_hip.h
+MUON_TILE = 64
+
+
+def muon_ratio(rows: int, cols: int, adjust_lr_fn: str | None) -> float:
+    """torch.optim._muon._adjust_lr's factor"""
+    if adjust_lr_fn is None or adjust_lr_fn == "original":
+        return math.sqrt(max(1, rows / cols))
+    if adjust_lr_fn == "match_rms_adamw":
+        return 0.2 * math.sqrt(max(rows, cols))
+    raise ValueError(f"Adjust learning rate function {adjust_lr_fn} is not supported")
+
+
+class MuonPlan:
+    """The two tables of `dl_muon_*` for one flat f32 buffer of `n` elements (host copy and device copy of each) and the device
+    workspaces they index: X (two bf16 copies of every Muon matrix), A and P (min(rows, cols)^2 bf16 each), one partial sum per
+    chunk, one norm per matrix.
+
+    `matrices`: [(offset, rows, cols, ratio)] sorted by offset; everything outside them is auxiliary (AdamW).  `phase`: the
+    buffer's address in floats modulo 4 -- chunk boundaries are put on 16-byte boundaries of the buffer where a range allows, so
+    that the pre pass can use float4 there."""
+
+    def __init__(self, n: int, matrices: list[tuple[int, int, int, float]], phase: int, device) -> None:
+        self.n, self.n_mat = int(n), len(matrices)
+        mats = np.zeros((self.n_mat + 1, MUON_MAT_FIELDS), dtype=np.int64)
+        chunks: list[np.ndarray] = []
+        n_chunks = 0
+
+        def add_range(s: int, e: int, mat: int) -> int:
+            nonlocal n_chunks
+            if e <= s:
+                return 0
+            first = min(e - s, MUON_CHUNK - ((s + phase) % 4))
+            starts = np.concatenate([[s], np.arange(s + first, e, MUON_CHUNK, dtype=np.int64)]) if s + first < e else np.array([s], dtype=np.int64)
+            ends = np.minimum(np.concatenate([starts[1:], [e]]), e)
+            chunks.append(np.stack([starts, ends - starts, np.full_like(starts, mat)], axis=1))
+            n_chunks += len(starts)
+            return len(starts)
+
+        at = x_off = a_off = sq = ap = 0
+        for i, (off, rows, cols, ratio) in enumerate(matrices):
+            if off < at:
+                raise ValueError("MuonPlan: the matrices must be sorted by offset and must not overlap")
+            add_range(at, off, -1)
+            short = min(rows, cols)
+            c0 = n_chunks
+            nc = add_range(off, off + rows * cols, i)
+            mats[i] = [off, rows, cols, int(np.float32(ratio).view(np.uint32)), x_off, a_off, sq, ap, c0, nc]
+            x_off += rows * cols
+            a_off += short * short
+            sq += (short // MUON_TILE) ** 2
+            ap += (rows // MUON_TILE) * (cols // MUON_TILE)
+            at = off + rows * cols
+        add_range(at, self.n, -1)
+        mats[self.n_mat, 6:8] = [sq, ap]
+        self.mats_host = torch.from_numpy(mats)
+        self.chunks_host = torch.from_numpy(np.ascontiguousarray(np.concatenate(chunks, axis=0)))
+        self.n_chunks = n_chunks
+        self.has_aux = bool((self.chunks_host[:, 2] < 0).any())
+        self.mats_dev, self.chunks_dev = self.mats_host.to(device), self.chunks_host.to(device)
+        self.x_cap, self.a_cap = x_off, a_off
+        self.xws = self.aws = self.partials = self.norms = None
+        if self.n_mat:
+            self.xws = torch.zeros(2 * x_off, dtype=torch.bfloat16, device=device)
+            self.aws = torch.zeros(2 * a_off, dtype=torch.bfloat16, device=device)
+            self.partials = torch.zeros(n_chunks, dtype=torch.float32, device=device)
+            self.norms = torch.zeros(self.n_mat, dtype=torch.float32, device=device)
+
+    def result(self, i: int, ns_steps: int) -> Tensor:
+        """O of matrix i after `muon_orthogonalize(..., ns_steps)`: a bf16 [rows, cols] view of the X copy that holds it"""
+        off, rows, cols = (int(v) for v in self.mats_host[i, [4, 1, 2]])
+        lo = (ns_steps & 1) * self.x_cap + off
+        return self.xws[lo : lo + rows * cols].view(rows, cols)
+
+
+def _muon_check(plan: MuonPlan, *bufs) -> None:
+    for t in bufs:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != plan.n):
+            raise RuntimeError(f"muon ops need contiguous f32 tensors of the plan's {plan.n} elements")
+
+
+def muon_pre(plan: MuonPlan, p, g, m, v, lr, beta1, beta2, eps, wd, step, momentum, nesterov=True, grad_scale=1.0, coef=None):
+    """one launch over the whole buffer: AdamW (`adamw_step`'s update, bit for bit) outside the plan's matrices; inside them the
+    momentum buffer `m`, bf16(U) into the plan's X workspace and the per-chunk sums of squares.  `coef` as in `sgd_step`."""
+    _muon_check(plan, p, g, m, v)
+    _call("dl_muon_pre", _p(p), _p(g), _p(m), _p(v), plan.n, plan.chunks_host.data_ptr(), _p(plan.chunks_dev), plan.n_chunks,
+          plan.mats_host.data_ptr(), _p(plan.mats_dev), plan.n_mat, _p(plan.xws), plan.x_cap, _p(plan.partials), plan.n_chunks,
+          float(lr), float(beta1), float(beta2), float(eps), float(wd), float(1.0 - beta1**step), float(1.0 - beta2**step),
+          float(momentum), float(grad_scale), _p(coef), int(bool(nesterov)), _s())
+
+
+def muon_orthogonalize(plan: MuonPlan, eps, ns_coefficients, ns_steps) -> int:
+    """every matrix of the plan: X = bf16(U) / max(||bf16(U)||_F, eps), then `ns_steps` quintic Newton-Schulz iterations, in
+    2 + 3 * ns_steps launches whatever the number of matrices; returns the launches issued.  The result: `plan.result(i, ns_steps)`."""
+    global _LIB
+    if _LIB is None:
+        _LIB = lib()
+    a, b, c = ns_coefficients
+    args = (plan.mats_host.data_ptr(), _p(plan.mats_dev), plan.n_mat, _p(plan.partials), _p(plan.norms), _p(plan.xws), plan.x_cap,
+            _p(plan.aws), plan.a_cap, float(eps), float(a), float(b), float(c), int(ns_steps), _s())
+    k = _LIB.call("dl_muon_orthogonalize", *args)
+    if k <= 0:
+        raise RuntimeError(f"dl_muon_orthogonalize failed ({k}): {_LIB.cdll.dl_last_error().decode()}")
+    if _REC is not None:
+        _REC.calls.append((_negative_is_failure(_LIB._fns["dl_muon_orthogonalize"][0]), args))
+    return k
+
+
+def muon_post(plan: MuonPlan, p, lr, wd, ns_steps):
+    """one launch: p = p * (1 - lr * wd) - lr * ratio * O on the plan's matrices (O: the result of `muon_orthogonalize`)"""
+    _muon_check(plan, p)
+    xo = plan.xws[(ns_steps & 1) * plan.x_cap :]
+    _call("dl_muon_post", _p(p), plan.n, plan.mats_host.data_ptr(), _p(plan.mats_dev), plan.n_mat, _p(xo), plan.x_cap, float(lr),
+          float(wd), _s())
 
 
 def cast_weight(src, dst, dst_t):

@@ -6,8 +6,9 @@ Drop-in `torch.optim.Optimizer` (same hyper-parameters / update rule as `torch.o
 arena (what `MMDiT.flatten_parameters` sets up) the whole model is updated by a single kernel; otherwise it
 launches the same HIP kernel once per tensor.
 
-`FusedSGD` is the same for `torch.optim.SGD` (`configs/optimizer/sgd.yaml`): ONE `dl_sgd_step` launch.  Both derive from
-`FusedArenaOptimizer`, which owns what is not the update rule: finding the arena, `zero_grad` as one memset, the clipping pass,
+`FusedSGD` is the same for `torch.optim.SGD` (`configs/optimizer/sgd.yaml`): ONE `dl_sgd_step` launch.  `FusedMuon` is
+`torch.optim.Muon` (`configs/optimizer/muon.yaml`) on the hidden matrices and AdamW on the rest: 19 launches, whatever the number of
+matrices.  All derive from `FusedArenaOptimizer`, which owns what is not the update rule: finding the arena, `zero_grad` as one memset, the clipping pass,
 `grad_scale` and the device scalars of a captured step.
 """
 
@@ -429,5 +430,139 @@ class FusedSGD(FusedArenaOptimizer):
                     if mb is not None and "buf" not in st:
                         st["buf"] = mb.to(device=p.device, dtype=torch.float32).contiguous()
                 self._update(p.data, p.grad, st, group, hyper, coef)
+            bump_param_epoch()
+        return loss
+
+
+class FusedMuon(FusedArenaOptimizer):
+    """``torch.optim.Muon``'s update (``configs/optimizer/muon.yaml``: momentum, then ``ns_steps`` quintic Newton-Schulz iterations
+    per weight matrix in bf16) for the hidden matrices of a model and ``torch.optim.AdamW``'s for everything else, over the flat
+    parameter arena.  Unlike torch's class it takes a whole model (a module or all of its parameters).
+
+    A parameter takes the Muon rule iff it is 2-D and both dimensions are multiples of 64 -- in the transformer engines exactly the
+    hidden matrices; biases, gains, embedding tables with ``n_classes + 1`` rows, ``conv_proj.weight`` and a 16-row output head take
+    AdamW with ``aux_lr`` (``None``: ``lr``), ``aux_betas``, ``aux_eps``, ``aux_weight_decay``.  A param group with ``use_muon: False``
+    keeps all its tensors on the auxiliary rule; ``use_muon: True`` insists and raises on a tensor that does not qualify.
+
+    Launches of one ``step()`` per arena (and per tensor outside it), whatever the number of matrices: ``1 + (2 + 3 * ns_steps) + 1``
+    = 19 at the default five iterations -- the elementwise pre pass (AdamW on auxiliary ranges; momentum, bf16 staging and partial
+    sums of squares on Muon ranges), the fold of the norms, the scaling, three grouped GEMM launches per iteration (Gram, polynomial,
+    apply) and the post pass -- or one (the pre pass) when nothing qualifies, plus with ``max_grad_norm`` one sum of squares per
+    buffer and the fold of `FusedArenaOptimizer`.  The momentum rule is the one torch's class executes (``buf.lerp_(grad, 1 -
+    momentum)``; ``grad.lerp(buf, momentum)`` with Nesterov), which is its docstring's ``B = momentum * B + g`` up to the factor
+    ``1 - momentum`` the normalisation removes.
+
+    State: ``m`` (arena-sized f32: AdamW's first moment on auxiliary ranges, the Muon momentum buffer on Muon ranges), ``v`` (AdamW's
+    second moment; arena-sized, unused on Muon ranges, absent for a loose Muon matrix) and ``step`` under the group's first arena
+    parameter, the same three per tensor outside the arena.  The matrix table, the chunk table and the bf16 workspaces (two copies
+    of X, A and P) are not state: they are built once per arena and rebuilt only when the arena scan runs again.  ``grad_scale``,
+    ``last_grad_norm`` and ``zero_grad`` are `FusedArenaOptimizer`'s; captured steps are not supported."""
+
+    def __init__(self, params, lr: float = 1e-3, weight_decay: float = 0.1, momentum: float = 0.95, nesterov: bool = True,
+                 ns_coefficients: tuple[float, float, float] = (3.4445, -4.7750, 2.0315), eps: float = 1e-7, ns_steps: int = 5,
+                 adjust_lr_fn: str | None = None, aux_lr: float | None = None, aux_betas: tuple[float, float] = (0.9, 0.999),
+                 aux_eps: float = 1e-8, aux_weight_decay: float = 1e-2, max_grad_norm: float | None = None) -> None:
+        if isinstance(lr, Tensor) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if not 0.0 <= lr:
+            raise ValueError(f"Learning rate should be >= 0 but is: {lr}")
+        if not 0.0 <= momentum:
+            raise ValueError(f"momentum should be >= 0 but is: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"weight decay should be >= 0 but is: {weight_decay}")
+        if adjust_lr_fn is not None and adjust_lr_fn not in ["original", "match_rms_adamw"]:
+            raise ValueError(f"Adjust learning rate function {adjust_lr_fn} is not supported")
+        # (torch raises these two from the first step(), inside _zeropower_via_newtonschulz)
+        if ns_steps >= 100:
+            raise ValueError("Number of steps must be less than 100 for computational efficiency")
+        if len(ns_coefficients) != 3:
+            raise ValueError("Coefficients must be a tuple of exactly 3 values")
+        if ns_steps < 0:
+            raise ValueError(f"ns_steps should be >= 0 but is: {ns_steps}")
+        if aux_lr is not None and not 0.0 <= aux_lr:
+            raise ValueError(f"Learning rate should be >= 0 but is: {aux_lr}")
+        if isinstance(params, torch.nn.Module):
+            params = params.parameters()
+        super().__init__(params, dict(lr=float(lr), weight_decay=weight_decay, momentum=momentum, nesterov=nesterov,
+                                      ns_coefficients=tuple(ns_coefficients), eps=eps, ns_steps=ns_steps, adjust_lr_fn=adjust_lr_fn,
+                                      aux_lr=aux_lr, aux_betas=tuple(aux_betas), aux_eps=aux_eps, aux_weight_decay=aux_weight_decay,
+                                      use_muon=None), max_grad_norm)
+        self._plans: dict = {}
+        for group in self.param_groups:
+            if group["use_muon"]:
+                for p in group["params"]:
+                    if not self.qualifies(p):
+                        raise ValueError(f"use_muon=True on a parameter of shape {tuple(p.shape)}: the Muon rule takes 2-D tensors whose "
+                                         "dimensions are both multiples of 64")
+
+    @staticmethod
+    def qualifies(p: Tensor) -> bool:
+        return p.ndim == 2 and p.shape[0] % ops.MUON_TILE == 0 and p.shape[1] % ops.MUON_TILE == 0
+
+    def is_muon(self, p: Tensor, group: dict) -> bool:
+        """does `p` (a parameter of `group`) take the Muon rule?"""
+        return group.get("use_muon") is not False and self.qualifies(p)
+
+    def begin_graph_mode(self) -> None:
+        raise NotImplementedError("FusedMuon has no captured-step form: its launch count depends on ns_steps and its scalars travel "
+                                  "by value")
+
+    def _flat_scan(self, group):
+        self._plans.pop(("arena", id(group)), None)  # (the arena scan runs again: its tables are rebuilt with it)
+        return super()._flat_scan(group)
+
+    def _plan(self, key, buf: Tensor, matrices) -> "ops.MuonPlan":
+        sig = (buf.data_ptr(), buf.numel(), buf.device)
+        hit = self._plans.get(key)
+        if hit is None or hit[0] != sig:
+            hit = self._plans[key] = (sig, ops.MuonPlan(buf.numel(), matrices(), (buf.data_ptr() // 4) % 4, buf.device))
+        return hit[1]
+
+    def _update(self, p: Tensor, g: Tensor, st: dict, group: dict, plan, coef: Tensor | None) -> None:
+        if not st:
+            st["step"], st["m"] = 0, torch.zeros_like(p)
+            if plan.has_aux:
+                st["v"] = torch.zeros_like(p)
+        if st["m"].numel() != p.numel() or (plan.has_aux and "v" not in st):
+            raise RuntimeError(f"optimizer state does not match its parameters: moments of {st['m'].numel()} elements for {p.numel()}")
+        for k in ("m", "v"):
+            if k in st and st[k].device != p.device:  # state loaded before the model moved
+                st[k] = st[k].to(p.device)
+        st["step"] = int(st["step"]) + 1
+        b1, b2 = group["aux_betas"]
+        ops.muon_pre(plan, p, g, st["m"], st.get("v"), group["lr"] if group["aux_lr"] is None else group["aux_lr"], b1, b2,
+                     group["aux_eps"], group["aux_weight_decay"], st["step"], group["momentum"], group["nesterov"], self.grad_scale, coef)
+        if plan.n_mat:
+            ops.muon_orthogonalize(plan, group["eps"], group["ns_coefficients"], group["ns_steps"])
+            ops.muon_post(plan, p, group["lr"], group["weight_decay"], group["ns_steps"])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        coef = self._clip_pass() if self.max_grad_norm is not None else None
+        for group in self.param_groups:
+            flat = self._flat(group)
+            rest = group["params"]
+            if flat is not None:
+                pb, gb, rest = flat
+                skip = {id(p) for p in rest}
+
+                def arena_matrices():
+                    base = pb.storage_offset()
+                    found = [(p.data.storage_offset() - base, p.shape[0], p.shape[1], ops.muon_ratio(*p.shape, group["adjust_lr_fn"]))
+                             for p in group["params"] if id(p) not in skip and p.requires_grad and self.is_muon(p, group)]
+                    return sorted(found)
+
+                # (keyed on the group's first arena parameter, for the reason FusedAdamW.step gives)
+                self._update(pb, gb, self.state[self._arena_key(group, rest)], group, self._plan(("arena", id(group)), pb, arena_matrices),
+                             coef)
+                bump_param_epoch()  # raw-pointer writes bump no torch version counter: tell the engines
+            for p in rest:
+                if p.grad is None:
+                    continue
+                muon = self.is_muon(p, group)
+                plan = self._plan(("tensor", id(p)), p.data, lambda: (
+                    [(0, p.shape[0], p.shape[1], ops.muon_ratio(*p.shape, group["adjust_lr_fn"]))] if muon else []))
+                self._update(p.data, p.grad, self.state[p], group, plan, coef)
             bump_param_epoch()
         return loss

@@ -804,6 +804,43 @@ DL_API int dl_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr
  * repeats grad_scale in hyper[7], where dl_clip_coef reads it. */
 DL_API int dl_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const float* hyper, const float* coef, int flags,
                            dl_stream_t stream);
+/* Muon (torch.optim.Muon's single-tensor math) for every qualifying weight matrix of a flat f32 buffer, AdamW (dl_adamw_step's
+ * update, bit for bit) for everything else.  The number of launches does not depend on the number of matrices: two tables, each
+ * given as a HOST copy (validated before any launch) and an identical DEVICE copy (read by the kernels), describe the work.
+ *
+ * Matrix table: (n_mat + 1) rows of DL_MUON_MAT_FIELDS int64, sorted by offset, not overlapping:
+ *   {element offset in the buffer, rows, cols, ratio (f32 bits in the low word: the learning-rate adjustment), element offset in
+ *    the X workspace (multiple of 8), element offset in the A workspace (multiple of 8, min(rows, cols)^2 elements), first square
+ *    tile = sum over earlier matrices of (min / 64)^2, first flat tile = sum of (rows / 64) * (cols / 64), first chunk, chunks};
+ *   row n_mat carries the two tile totals.  rows and cols: multiples of 64, min <= 4096, max <= 32768, else DL_ERR_UNSUPPORTED.
+ * Chunk table: n_chunks rows of DL_MUON_CHUNK_FIELDS int64 {start, length (1 .. DL_MUON_CHUNK), matrix index or -1}; the chunks
+ *   tile [0, n) in order and none straddles a matrix boundary.  One workgroup per chunk.
+ *
+ * dl_muon_pre (1 launch), with gr = g * grad_scale [* *coef, `coef` = &out[1] of dl_clip_coef]:
+ *   chunks with matrix -1: dl_adamw_step's update of p, m, v (same expressions; m is AdamW's first moment there);
+ *   Muon chunks: m = lerp(m, gr, 1 - momentum) ; U = nesterov ? lerp(gr, m, momentum) : m  (torch's buf.lerp_ / grad.lerp), bf16(U)
+ *     to xws at the matrix's X offset, and the chunk's sum of squares of bf16(U) to partials[chunk] (fixed order, no atomics).
+ *   p is not written on Muon chunks, g never; v may be NULL when no chunk is auxiliary.  Any 4-byte aligned p, g, m, v: float4
+ *   where a chunk's addresses allow, one element at a time otherwise, with the same bits.
+ * dl_muon_orthogonalize (2 + 3 * ns_steps launches; RETURNS that count, or a negative status): folds each matrix's partials in
+ *   f64 in slot order into norms[i] = max(||bf16(U)||_F, eps), scales X = bf16(X / norm) in place, then ns_steps times
+ *   A = X X^T, P = b A + c A A, X' = a X + P X (bf16 MFMA, f32 accumulation, every result stored as bf16; tall matrices run the
+ *   same iteration as A = X^T X, X' = a X + X P, without a transpose).  xws: 2 * x_cap bf16 (the result O is copy ns_steps & 1,
+ *   in the parameter's own orientation), aws: 2 * a_cap bf16 (A and P), norms: n_mat f32.  ns_steps outside [0, 100) is refused.
+ * dl_muon_post (1 launch): p = p * (1 - lr * weight_decay) - lr * ratio * O on the matrices' ranges, plain f32 stores; `xo` is the
+ *   X copy that holds O.
+ * Refused with DL_ERR_INVALID before any launch: NULL pointers, tables that do not tile the buffer or do not fit the workspaces. */
+enum { DL_MUON_MAT_FIELDS = 10, DL_MUON_CHUNK_FIELDS = 3, DL_MUON_CHUNK = 2048 };
+DL_API int dl_muon_pre(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* chunks_host,
+                       const int64_t* chunks_dev, int64_t n_chunks, const int64_t* mats_host, const int64_t* mats_dev,
+                       int64_t n_mat, void* xws, int64_t x_cap, float* partials, int64_t partials_cap, float lr, float beta1,
+                       float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float momentum,
+                       float grad_scale, const float* coef, int nesterov, dl_stream_t stream);
+DL_API int dl_muon_orthogonalize(const int64_t* mats_host, const int64_t* mats_dev, int64_t n_mat, const float* partials,
+                                 float* norms, void* xws, int64_t x_cap, void* aws, int64_t a_cap, float eps, float a, float b,
+                                 float c, int ns_steps, dl_stream_t stream);
+DL_API int dl_muon_post(float* p, int64_t n, const int64_t* mats_host, const int64_t* mats_dev, int64_t n_mat, const void* xo,
+                        int64_t x_cap, float lr, float weight_decay, dl_stream_t stream);
 /* bf16 shadow of an f32 [R,C] weight: dst [R, ld_dst] (cols >= C zeroed up to ld_dst) and/or the transpose
  * dstT [C, ld_t] (cols >= R zeroed up to ld_t).  Either destination may be NULL. */
 DL_API int dl_cast_weight(const float* src, int64_t R, int64_t C, void* dst, int64_t ld_dst, void* dstT,

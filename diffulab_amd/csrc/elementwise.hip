@@ -18,6 +18,8 @@ extern "C" const char* dl_last_error(void) { return g_err; }
 static thread_local int g_wg_cap = 0;
 void dl_set_wg_cap(int cap) { g_wg_cap = cap > 0 ? cap : 0; }
 int dl_get_wg_cap() { return g_wg_cap; }
+// LAB switch (not in the header): the cap a data-parallel host sets through dl_dit_block_t::max_workgroups, for the tests
+extern "C" __attribute__((visibility("default"))) void dl_lab_set_wg_cap(int cap) { dl_set_wg_cap(cap); }
 int dl_wg_budget(int n_cu) {
   int n = (g_wg_cap > 0 && g_wg_cap < n_cu) ? g_wg_cap : n_cu;
   return n < 8 ? 8 : n;

@@ -38,7 +38,7 @@ PATHS = ["DL_PATH_NONE",
          "CONV_BIG_256_SPLITK", "CONV_BIG_128_SPLITK", "CONV_SMALL_RING2", "CONV_SMALL_RING4", "CONV_SPLITK_RING2", "CONV_SPLITK_RING4"]
 
 # the library's lab switches (not in the header) and their defaults
-LAB_DEFAULTS = {"nt_deep": 1, "conv_big": 1, "conv_halo": 1, "conv_halo_nst": 4, "conv_split128": 1}
+LAB_DEFAULTS = {"nt_deep": 1, "conv_big": 1, "conv_halo": 1, "conv_halo_nst": 4, "conv_split128": 1, "wg_cap": 0}
 
 # output tile of each path, for the failure messages
 TILE = {"NT_BIG_384": (256, 384), "NT_BIG_256": (256, 256), "NT_BIG_192": (256, 192), "NT_BIG_128": (256, 128),
@@ -107,6 +107,9 @@ def _cases():
     cs.append(Case("swiglu", "NT_BIG_192", (2048, 768, 384)))
     cs.append(Case("swiglu", "NT_BIG_192", (2048, 768, 384), extra={"noU": 1}))
     cs.append(Case("swiglu", "NT_BIG_128", (512, 2048, 256)))
+    # ---- under a data-parallel host's workgroup cap (8 workgroups): every workgroup walks many tiles, launch_big staggers their starts
+    cs.append(Case("nt", "NT_BIG_192", (3072, 3072, 192), lab={"wg_cap": 8}))
+    cs.append(Case("swiglu", "NT_BIG_192", (2048, 768, 384), lab={"wg_cap": 8}))
     # ---- dl_gemm_nt_pair (M, N0, N1, K0, K1) on column windows, with bias / residual
     cs.append(Case("pair", "NT_PAIR_RING2", (1000, 136, 264, 64, 192), epi="bias_resid"))
     cs.append(Case("pair", "NT_PAIR_RING2", (129, 72, 130, 192, 320), epi="plain"))

@@ -47,6 +47,36 @@ __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 __device__ __forceinline__ bf16_t f2bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
+
+// ---------------------------------------------------------------- AdamW, one element
+// torch.optim.AdamW's rule for one element.  ONE body for every caller (adamw_k's float4 lanes and its n % 4 tail, adamw_dev_k,
+// the auxiliary ranges of muon_pre_k; scalars from the launch or from device memory), with contraction off and each fused
+// multiply-add explicit, as sgd_elem: left to the compiler, the float4 loop, the tail and the device-scalar kernel each fused m',
+// v' and the parameter update differently and came out an ulp apart.  The roundings are those of adamw_k's float4 loop, which has
+// always updated all but the last n % 4 elements of a buffer, so an aligned buffer's update keeps its bits.
+struct AdamwScalars {
+  float b1, b2, eps, inv_bc1_lr, inv_sqrt_bc2, gs;  // gs: grad_scale [* *coef]
+  float decay, omb1, omb2;                          // 1 - lr * weight_decay (one fma), 1 - beta1, 1 - beta2
+};
+__device__ __forceinline__ AdamwScalars adamw_scalars(float lr, float b1, float b2, float eps, float wd, float inv_bc1_lr,
+                                                      float inv_sqrt_bc2, float gs) {
+#pragma clang fp contract(off)
+  AdamwScalars s;
+  s.b1 = b1, s.b2 = b2, s.eps = eps, s.inv_bc1_lr = inv_bc1_lr, s.inv_sqrt_bc2 = inv_sqrt_bc2, s.gs = gs;
+  s.decay = __builtin_fmaf(-lr, wd, 1.0f), s.omb1 = 1.0f - b1, s.omb2 = 1.0f - b2;
+  return s;
+}
+__device__ __forceinline__ void adamw_elem(float& p, const float g, float& m, float& v, const AdamwScalars& s) {
+#pragma clang fp contract(off)
+  const float gr = g * s.gs;
+  const float mj = __builtin_fmaf(s.omb1, gr, s.b1 * m);
+  const float vj = __builtin_fmaf(gr, s.omb2 * gr, s.b2 * v);
+  const float denom = __builtin_fmaf(sqrtf(vj), s.inv_sqrt_bc2, s.eps);
+  p = __builtin_fmaf(s.decay, p, -(s.inv_bc1_lr * (mj / denom)));
+  m = mj;
+  v = vj;
+}
+
 __device__ __forceinline__ void unpack8(const u32x4_t& p, float (&f)[8]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {

@@ -84,7 +84,13 @@ extern "C" int dl_stream_destroy(void* stream) {
 }
 
 // ---------------------------------------------------------------- noising
-// z = (1-t) x + t eps; chw % 4 == 0 fast path works on float4, else scalar
+// z = (1-t) x + t eps; chw % 4 == 0 fast path works on float4, else scalar.  One element goes through flow_noise_elem in both forms,
+// with contraction off and the fused multiply-add explicit (the rounding the float4 form has always had): left to the compiler,
+// the scalar form's loop was unrolled by two with the pair fused and the odd trip not, so z depended on the form and on the trip.
+__device__ __forceinline__ float flow_noise_elem(const float x, const float e, const float tt) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(1.0f - tt, x, tt * e);
+}
 template <bool VEC>
 __global__ void flow_add_noise_k(const float* __restrict__ x, const float* __restrict__ e,
                                  const float* __restrict__ t, float* __restrict__ z, int64_t n, int64_t chw) {
@@ -92,20 +98,17 @@ __global__ void flow_add_noise_k(const float* __restrict__ x, const float* __res
   if (VEC) {
     const int64_t nv = n >> 2, cv = chw >> 2;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
-      const float tt = t[i / cv], at = 1.0f - tt;
+      const float tt = t[i / cv];
       const float4 a = ((const float4*)x)[i], b = ((const float4*)e)[i];
       float4 o;
-      o.x = at * a.x + tt * b.x;
-      o.y = at * a.y + tt * b.y;
-      o.z = at * a.z + tt * b.z;
-      o.w = at * a.w + tt * b.w;
+      o.x = flow_noise_elem(a.x, b.x, tt);
+      o.y = flow_noise_elem(a.y, b.y, tt);
+      o.z = flow_noise_elem(a.z, b.z, tt);
+      o.w = flow_noise_elem(a.w, b.w, tt);
       ((float4*)z)[i] = o;
     }
   } else {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-      const float tt = t[i / chw];
-      z[i] = (1.0f - tt) * x[i] + tt * e[i];
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) z[i] = flow_noise_elem(x[i], e[i], t[i / chw]);
   }
 }
 extern "C" int dl_flow_add_noise(const float* x, const float* noise, const float* t, float* z, int64_t batch,
@@ -123,12 +126,13 @@ extern "C" int dl_flow_add_noise(const float* x, const float* noise, const float
 __global__ void ddpm_add_noise_k(const float* __restrict__ x, const float* __restrict__ e,
                                  const int32_t* __restrict__ t, const float* __restrict__ sqrt_ab,
                                  const float* __restrict__ ab, float* __restrict__ o, int64_t n, int64_t chw) {
+#pragma clang fp contract(off)
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int32_t ti = t[i / chw];
     const float ca = sqrt_ab[ti];
     const float cb = sqrtf(1.0f - ab[ti]);  // gd.py:340: sqrt evaluated in fp32 after the .float() gather
-    o[i] = ca * x[i] + cb * e[i];
+    o[i] = ca * x[i] + cb * e[i];           // (contraction off: two products and a sum on every trip of the loop)
   }
 }
 extern "C" int dl_ddpm_add_noise(const float* x, const float* noise, const int32_t* t, const float* sqrt_ab,
@@ -141,32 +145,24 @@ extern "C" int dl_ddpm_add_noise(const float* x, const float* noise, const int32
 }
 
 // ---------------------------------------------------------------- optimizer / casts
+// One element: adamw_elem (common.h), the same body in the float4 loop, in the n % 4 tail and in adamw_dev_k, so an element's result
+// does not depend on where in a buffer it lies or on which entry point updates it (tests/test_step_paths_gpu.py holds that bit for bit).
 // CLIP: the gradient scale is grad_scale * *coef, the clipping coefficient dl_clip_coef left in device memory (clip.hip); formed once
 // per thread, so with *coef == 1 the update is bit-identical to the plain one
 template <bool CLIP>
 __global__ void adamw_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                         float* __restrict__ v, int64_t n4, int64_t n, float lr, float b1, float b2, float eps,
                         float wd, float inv_bc1_lr, float inv_sqrt_bc2, float grad_scale, const float* __restrict__ coef) {
-  const float gs = CLIP ? grad_scale * *coef : grad_scale;
+#pragma clang fp contract(off)
+  const AdamwScalars s = adamw_scalars(lr, b1, b2, eps, wd, inv_bc1_lr, inv_sqrt_bc2, CLIP ? grad_scale * *coef : grad_scale);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 pp = ((float4*)p)[i], gg = ((const float4*)g)[i], mm = ((float4*)m)[i], vv = ((float4*)v)[i];
-    float* P = (float*)&pp;
-    float* G = (float*)&gg;
-    float* Mm = (float*)&mm;
-    float* V = (float*)&vv;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gr = G[j] * gs;
-      float pj = P[j] * (1.0f - lr * wd);
-      const float mj = b1 * Mm[j] + (1.0f - b1) * gr;
-      const float vj = b2 * V[j] + (1.0f - b2) * gr * gr;
-      const float denom = sqrtf(vj) * inv_sqrt_bc2 + eps;
-      pj -= inv_bc1_lr * (mj / denom);
-      P[j] = pj;
-      Mm[j] = mj;
-      V[j] = vj;
-    }
+    float4 pp = ((float4*)p)[i], mm = ((float4*)m)[i], vv = ((float4*)v)[i];
+    const float4 gg = ((const float4*)g)[i];
+    adamw_elem(pp.x, gg.x, mm.x, vv.x, s);
+    adamw_elem(pp.y, gg.y, mm.y, vv.y, s);
+    adamw_elem(pp.z, gg.z, mm.z, vv.z, s);
+    adamw_elem(pp.w, gg.w, mm.w, vv.w, s);
     ((float4*)p)[i] = pp;
     ((float4*)m)[i] = mm;
     ((float4*)v)[i] = vv;
@@ -176,11 +172,8 @@ __global__ void adamw_k(float* __restrict__ p, const float* __restrict__ g, floa
   const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gi < n - tail0) {
     const int64_t i = tail0 + gi;
-    const float gr = g[i] * gs;
-    float pj = p[i] * (1.0f - lr * wd);
-    const float mj = b1 * m[i] + (1.0f - b1) * gr;
-    const float vj = b2 * v[i] + (1.0f - b2) * gr * gr;
-    pj -= inv_bc1_lr * (mj / (sqrtf(vj) * inv_sqrt_bc2 + eps));
+    float pj = p[i], mj = m[i], vj = v[i];
+    adamw_elem(pj, g[i], mj, vj, s);
     p[i] = pj;
     m[i] = mj;
     v[i] = vj;
@@ -214,22 +207,17 @@ extern "C" int dl_adamw_step_clip(float* p, const float* g, float* m, float* v, 
 // same update with the scalars read from device memory (hyper = {lr, beta1, beta2, eps, weight_decay, lr / bias_corr1,
 // 1 / sqrt(bias_corr2), grad_scale}): the launch carries no per-step value, so a captured hipGraph of the training step can be
 // replayed while the host refreshes the 32 bytes before each replay (training/graph_step.py)
-// The roundings are written out (contraction off, each fused multiply-add explicit) in the form the plain kernel has always compiled
-// to: left to the compiler, the CLIP instantiation fused v's update differently and came out an ulp apart at *coef == 1.
 template <bool CLIP>
 __global__ void adamw_dev_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             int64_t n, const float* __restrict__ hyper, const float* __restrict__ coef) {
 #pragma clang fp contract(off)
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], inv_bc1_lr = hyper[5],
-              inv_sqrt_bc2 = hyper[6], gs = CLIP ? hyper[7] * *coef : hyper[7];
-  const float decay = __builtin_fmaf(-lr, wd, 1.0f), omb1 = 1.0f - b1, omb2 = 1.0f - b2;
+  const AdamwScalars s = adamw_scalars(hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[6],
+                                       CLIP ? hyper[7] * *coef : hyper[7]);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gr = g[i] * gs;
-    const float mj = __builtin_fmaf(b1, m[i], omb1 * gr);
-    const float vj = __builtin_fmaf(gr, omb2 * gr, b2 * v[i]);
-    const float denom = __builtin_fmaf(sqrtf(vj), inv_sqrt_bc2, eps);
-    p[i] = decay * p[i] - inv_bc1_lr * (mj / denom);
+    float pj = p[i], mj = m[i], vj = v[i];
+    adamw_elem(pj, g[i], mj, vj, s);
+    p[i] = pj;
     m[i] = mj;
     v[i] = vj;
   }
@@ -250,7 +238,7 @@ extern "C" int dl_adamw_step_dev_clip(float* p, const float* g, float* m, float*
 
 // torch.optim.SGD's single-tensor rule for one element.  ONE body for every caller (vector lanes, scalar head / tail, the odd-phase
 // loop; scalars from the launch or from device memory; with or without the clipping coefficient), with contraction off and each
-// fused multiply-add explicit, as in adamw_dev_k and for its reason: all of them round identically, which the tests hold bit for bit.
+// fused multiply-add explicit, as in adamw_elem (common.h) and for its reason: all of them round identically, which the tests hold bit for bit.
 struct SgdScalars {
   float neg_lr, mom, omd, wd, gs;  // -lr, momentum, 1 - dampening, weight_decay, grad_scale [* *coef]
   int flags;

@@ -94,27 +94,9 @@ struct MuPre {
   float w1, mom, gs;                                    // 1 - momentum (rounded from f64, as torch passes it to lerp_), momentum
   int nesterov;
 };
-// dl_adamw_step's update of one element, bit for bit.  adamw_k (elementwise.hip) leaves the contraction of its expressions to the
-// compiler, which fuses them one way in the float4 loop and another way in the loop over the last n % 4 elements; the roundings of
-// both are written out here (contraction off, each fused multiply-add explicit), so that the result does not depend on how THIS
-// kernel is compiled or on which of its loops an element falls into.  TAIL: the element is one of the buffer's last n % 4.
-__device__ __forceinline__ void mu_adamw_elem(float& p, const float g, float& m, float& v, const MuPre& s, const bool tail) {
-#pragma clang fp contract(off)
-  const float gr = g * s.gs;
-  const float decay = __builtin_fmaf(-s.lr, s.wd, 1.0f), omb1 = 1.0f - s.b1, omb2 = 1.0f - s.b2;
-  float mj, vj;
-  if (!tail) {
-    mj = __builtin_fmaf(omb1, gr, s.b1 * m);
-    vj = __builtin_fmaf(gr, omb2 * gr, s.b2 * v);
-  } else {
-    mj = __builtin_fmaf(s.b1, m, omb1 * gr);
-    vj = gr * (omb2 * gr) + s.b2 * v;
-  }
-  const float denom = __builtin_fmaf(sqrtf(vj), s.inv_sqrt_bc2, s.eps);
-  const float upd = s.inv_bc1_lr * (mj / denom);
-  p = tail ? decay * p - upd : __builtin_fmaf(decay, p, -upd);
-  m = mj;
-  v = vj;
+// dl_adamw_step's update of one element, bit for bit: the one body every AdamW kernel of the library calls (adamw_elem, common.h)
+__device__ __forceinline__ void mu_adamw_elem(float& p, const float g, float& m, float& v, const MuPre& s) {
+  adamw_elem(p, g, m, v, adamw_scalars(s.lr, s.b1, s.b2, s.eps, s.wd, s.inv_bc1_lr, s.inv_sqrt_bc2, s.gs));
 }
 // torch's rule for one element of a Muon matrix: buf.lerp_(grad, 1 - momentum); update = grad.lerp(buf, momentum) with Nesterov,
 // else buf -- lerp(start, end, w) is start + w (end - start) for w < 0.5 and end - (end - start) (1 - w) otherwise.  Returns
@@ -136,8 +118,7 @@ __device__ __forceinline__ float mu_muon_elem(const float g, float& b, const MuP
 __global__ __launch_bounds__(MU_THREADS) void muon_pre_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                           float* __restrict__ v, const int64_t* __restrict__ chunks,
                                                           const int64_t* __restrict__ mats, bf16_t* __restrict__ xws,
-                                                          float* __restrict__ partials, MuPre s, const float* __restrict__ coef,
-                                                          int64_t tail0) {
+                                                          float* __restrict__ partials, MuPre s, const float* __restrict__ coef) {
   __shared__ float wsum[MU_THREADS / DL_WAVE];
   if (coef) s.gs = s.gs * *coef;
   const int64_t* ck = chunks + (int64_t)blockIdx.x * DL_MUON_CHUNK_FIELDS;
@@ -156,11 +137,10 @@ __global__ __launch_bounds__(MU_THREADS) void muon_pre_k(float* __restrict__ p, 
       for (int i = t; i < n4; i += MU_THREADS) {
         float4 a = ((float4*)pp)[i], c = ((float4*)mm)[i], d = ((float4*)vv)[i];
         const float4 b = ((const float4*)gg)[i];
-        const int64_t at = start + 4 * i;
-        mu_adamw_elem(a.x, b.x, c.x, d.x, s, at >= tail0);
-        mu_adamw_elem(a.y, b.y, c.y, d.y, s, at + 1 >= tail0);
-        mu_adamw_elem(a.z, b.z, c.z, d.z, s, at + 2 >= tail0);
-        mu_adamw_elem(a.w, b.w, c.w, d.w, s, at + 3 >= tail0);
+        mu_adamw_elem(a.x, b.x, c.x, d.x, s);
+        mu_adamw_elem(a.y, b.y, c.y, d.y, s);
+        mu_adamw_elem(a.z, b.z, c.z, d.z, s);
+        mu_adamw_elem(a.w, b.w, c.w, d.w, s);
         ((float4*)pp)[i] = a;
         ((float4*)mm)[i] = c;
         ((float4*)vv)[i] = d;
@@ -169,7 +149,7 @@ __global__ __launch_bounds__(MU_THREADS) void muon_pre_k(float* __restrict__ p, 
     }
     for (int i = done + t; i < len; i += MU_THREADS) {
       float a = pp[i], c = mm[i], d = vv[i];
-      mu_adamw_elem(a, gg[i], c, d, s, start + i >= tail0);
+      mu_adamw_elem(a, gg[i], c, d, s);
       pp[i] = a;
       mm[i] = c;
       vv[i] = d;
@@ -255,7 +235,7 @@ extern "C" int dl_muon_pre(float* p, const float* g, float* m, float* v, int64_t
   s.inv_sqrt_bc2 = (float)(1.0 / sqrt((double)bias_corr2));
   s.w1 = (float)(1.0 - (double)momentum), s.mom = momentum, s.gs = grad_scale, s.nesterov = nesterov != 0;
   hipLaunchKernelGGL(muon_pre_k, (int)n_chunks, MU_THREADS, 0, (hipStream_t)stream, p, g, m, v, chunks_dev, mats_dev, (bf16_t*)xws,
-                     partials, s, coef, n / 4 * 4);
+                     partials, s, coef);
   DL_LAUNCH_CHECK();
   return DL_OK;
 }

@@ -364,22 +364,29 @@ __device__ __forceinline__ void ln_mod_bwd_body(const bf16_t* __restrict__ dout,
     }
   }
 
-  // cross-wave reduction of the three column sums: LDS float atomics into ONE [3][D] slab
+  // cross-wave reduction of the three column sums into ONE [3][D] slab, the waves taking turns in wave order (a lane owns its
+  // columns, so a turn is plain adds).  LDS float atomics met here in whatever order the waves arrived: with one workgroup per
+  // sample (split == 1, e.g. the 76 rows of a joint model's [context ; image] latents) that order was the only thing that varied
+  // between two runs, and a sum an f32 ulp either side of a bf16 tie flipped the rounded modulation gradient.
   __syncthreads();  // zero-fill above happened before the row loop
+  for (int turn = 0; turn < LNB1_WAVES; ++turn) {
+    if (wave == turn) {
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int c = lane + 64 * j;
-    if (c < D8) {
-      float* base = red + c * 8;
+      for (int j = 0; j < NJ; ++j) {
+        const int c = lane + 64 * j;
+        if (c < D8) {
+          float* base = red + c * 8;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        atomicAdd(base + e, a_s1[j][e]);
-        atomicAdd(base + D + e, a_s2[j][e]);
-        if (gt) atomicAdd(base + 2 * D + e, a_s3[j][e]);
+          for (int e = 0; e < 8; ++e) {
+            base[e] += a_s1[j][e];
+            base[D + e] += a_s2[j][e];
+            if (gt) base[2 * D + e] += a_s3[j][e];
+          }
+        }
       }
     }
+    __syncthreads();
   }
-  __syncthreads();
   // the `split` workgroups of one sample meet in global f32 accumulators (<= split-way contention per address): the
   // modulation gradients land in the f32 image of dmod, the affine gradients in the per-sample partial [groups, 2, D]
   for (int col = threadIdx.x; col < D; col += 256) {

@@ -1380,6 +1380,11 @@ class CastTable:
                         ("dst_swiglu", ctypes.c_void_p), ("ld_swiglu", ctypes.c_int64), ("tile_begin", ctypes.c_int64),
                         ("tiles_c", ctypes.c_int64)]
 
+        for i, (src, dst, dst_t, dst_g) in enumerate(entries):
+            # the kernel's SwiGLU row map works on whole 32-row groups (16 x1 rows, then the 16 x3 rows of the same hidden units): at
+            # F = R / 2 not a multiple of 16 it leaves the destination's 2 F rows (dl_cast_weight_swiglu refuses such an F too)
+            if dst_g is not None and (src.dim() != 2 or src.shape[0] % 32 != 0):
+                raise ValueError(f"CastTable: entry {i} has a SwiGLU destination, its source {tuple(src.shape)} needs rows % 32 == 0")
         arr = (Desc * len(entries))()
         tiles = 0
         self.keep = entries  # the table holds raw pointers: keep the tensors alive

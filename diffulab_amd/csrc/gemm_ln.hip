@@ -17,9 +17,10 @@
 // Epilogue = "the row kernel, fed from LDS": the accumulators are rounded to bf16 (exactly what the unfused GEMM would have
 // stored), dumped 64 rows at a time into the LDS slot the last k-step has just released (row pitch 784 B: consecutive rows
 // shift by four banks, the 16-byte writes of eight lanes cover 32 banks), and then every wave owns a ROW: lane c holds columns
-// [8c, 8c+8) -- the thread layout of norm.hip's kernels, the same DPP wave sums in the same order, so every per-row output is
-// BIT-IDENTICAL to the unfused launch sequence (tests/test_kernels_gpu.py checks equality), and per-sample column sums are
-// plain in-lane accumulators over the tile's rows.  Global operands of the row (x, dres, t / residual) are prefetched one row
+// [8c, 8c+8) -- the thread layout of norm.hip's kernels, the same DPP wave sums in the same order, so t, x and qkv are
+// BIT-IDENTICAL to the unfused launch sequence and the statistics and the rows computed from them agree with it to their last
+// bits (tests/test_row_gemm_gpu.py; tests/test_row_gemm_paths_gpu.py checks every output element against fp64), and per-sample
+// column sums are plain in-lane accumulators over the tile's rows.  Global operands of the row (x, dres, t / residual) are prefetched one row
 // ahead; their rows are contiguous 768-byte segments per wave instruction.
 #include <stdlib.h>
 

@@ -4,6 +4,12 @@
 // wavefront shuffles (no LDS); per-sample column reductions (adaLN gradients) are register accumulators
 // reduced across the workgroup's waves through LDS once per workgroup.  1024 < D <= 4096: the *_rows_k kernels give a row to a
 // whole 256-thread workgroup (rows_sum); a thread then owns its columns, so column sums need no cross-wave reduction.
+// Narrow and wide forms of one operation: the gated-residual backward has ONE row loop (gate_bwd_rows<S>, S = the threads that own
+// a row) under its two column reductions, and the RoPE rotation and its transpose are one helper each.  The LayerNorm-modulate
+// forward / backward / per-token backward and the QK-norm forward / backward keep a text per form ON PURPOSE: instantiated from a
+// shared body the compiler contracts their multiply-adds into FMAs differently (-ffp-contract=fast leaves that to the vectoriser's
+// grouping), and outputs move in the last bit against the kernels as they stand (scripts/row_kernel_bits.py shows it;
+// profiles/row_fold_resources.txt has the record).  A change to one of their formulas goes into both forms.
 #include <stdlib.h>
 
 #include "common.h"
@@ -242,8 +248,10 @@ extern "C" int dl_ln_modulate_fwd(const void* x, const float* w, const float* b,
 //   S1 = sum_rows d,  S2 = sum_rows d xh,  S3 = sum_rows dx_new t
 // so the row loop carries 3 accumulators and ONE constant vector g = (1 + scale) w instead of 5 + 3: 179 -> ~110 VGPRs.  That
 // matters beside the side-stream weight-gradient GEMM (152 VGPRs x 2 waves per SIMD): two of these waves fit into the 208
-// registers it leaves per SIMD instead of one.  PF: software prefetch of the next row (worth it only at one wave per SIMD).
-template <int NJ, bool PF>
+// registers it leaves per SIMD instead of one.
+// (A software prefetch of the next row, a two-row ring of these raw operands, measured +0.3 ms per step in round 1: removed.
+// Unpacking each operand where it is loaded instead of staging the raw words measured 52 -> 62 us at D = 1024: not done.)
+template <int NJ>
 __device__ __forceinline__ void ln_mod_bwd_body(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ x,
                                                     const float* __restrict__ w, const float* __restrict__ b,
                                                     const bf16_t* __restrict__ scale, int64_t ld_mod,
@@ -282,7 +290,7 @@ __device__ __forceinline__ void ln_mod_bwd_body(const bf16_t* __restrict__ dout,
 
   const int64_t row_begin = g * rows_per_mod + sp * rows_per_wg;
   const int64_t row_end = row_begin + rows_per_wg < M ? row_begin + rows_per_wg : M;
-  u32x4_t pd[NJ], px[NJ], pr[NJ], pt[NJ];
+  u32x4_t pd[NJ], px[NJ], pr[NJ], pt[NJ];  // a row's raw operands (pt: t of the fused gate), all requested before any is unpacked
   float pmu = 0.f, prs = 0.f;
   auto fetch = [&](int64_t row) {
 #pragma unroll
@@ -298,16 +306,12 @@ __device__ __forceinline__ void ln_mod_bwd_body(const bf16_t* __restrict__ dout,
     pmu = mean[row];
     prs = rstd[row];
   };
-  int64_t row = row_begin + wave;
-  if (PF && row < row_end) fetch(row);
-  for (; row < row_end; row += LNB1_WAVES) {
-    if (!PF) fetch(row);
+  for (int64_t row = row_begin + wave; row < row_end; row += LNB1_WAVES) {
+    fetch(row);
     float dv[NJ][8], xv[NJ][8], rv[NJ][8];
-    u32x4_t tq[NJ];  // this row's t (gate fusion), saved before the prefetch of the next row overwrites pt
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const bool on = (lane + 64 * j) < D8;
-      tq[j] = pt[j];
       if (on) {
         unpack8(pd[j], dv[j]);
         unpack8(px[j], xv[j]);
@@ -320,7 +324,6 @@ __device__ __forceinline__ void ln_mod_bwd_body(const bf16_t* __restrict__ dout,
       if (on && dres) unpack8(pr[j], rv[j]);
     }
     const float mu = pmu, rs = prs;
-    if (PF && row + LNB1_WAVES < row_end) fetch(row + LNB1_WAVES);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -352,7 +355,7 @@ __device__ __forceinline__ void ln_mod_bwd_body(const bf16_t* __restrict__ dout,
       for (int j = 0; j < NJ; ++j) {
         const bool on = (lane + 64 * j) < D8;
         float tv[8];
-        if (on) unpack8(tq[j], tv);
+        if (on) unpack8(pt[j], tv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float dxr = bf2f(f2bf(rv[j][e]));
@@ -410,14 +413,10 @@ __device__ __forceinline__ void ln_mod_bwd_body(const bf16_t* __restrict__ dout,
       const bf16_t *__restrict__ ggate, int64_t ld_gate, bf16_t *__restrict__ gdt, float *__restrict__ dgate, int split, int64_t M, int D
 #define LNB_PASS dout, x, w, b, scale, ld_mod, rows_per_mod, mean, rstd, dres, dx, dscale, dshift, ld_dmod, dwb, gt, ggate, ld_gate, gdt, dgate, split, M, D
 // D <= 512: capped at 104 VGPRs (two waves per SIMD beside the 152-register weight-gradient GEMM, four alone)
-template <bool PF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void ln_mod_bwd_k(LNB_ARGS) {
-  ln_mod_bwd_body<1, PF>(LNB_PASS);
+  ln_mod_bwd_body<1>(LNB_PASS);
 }
-template <bool PF>
-__global__ __launch_bounds__(256) void ln_mod_bwd_wide_k(LNB_ARGS) {
-  ln_mod_bwd_body<2, PF>(LNB_PASS);
-}
+__global__ __launch_bounds__(256) void ln_mod_bwd_wide_k(LNB_ARGS) { ln_mod_bwd_body<2>(LNB_PASS); }
 
 // 1024 < D <= 4096: a 256-thread workgroup takes the rows of its share of one sample one at a time (rows_sum for the two row
 // reductions).  Every thread owns its columns, so the three column sums stay in its registers until they go to the caller's f32
@@ -559,21 +558,14 @@ extern "C" int dl_ln_modulate_bwd(const void* dout, const void* x, const float* 
     return DL_OK;
   }
   const size_t lds = (size_t)3 * D * sizeof(float);
-  const bool pf = false;  // (the two-row prefetch ring of ln_mod_bwd_k<true> measured +0.3 ms per step: round 1)
-#define LAUNCH(NJ, PF)                                                                                                        \
-  hipLaunchKernelGGL((KERN_##NJ<PF>), groups * split, 256, lds, (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)x, \
-                     w, b, (const bf16_t*)scale, ld_mod, rows_per_mod, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx,          \
-                     dscale, dshift, ld_dmod, dwb_partial, (const bf16_t*)gate_t, (const bf16_t*)gate, ld_gate,              \
-                     (bf16_t*)dt, dgate, split, M, (int)D)
-#define KERN_1 ln_mod_bwd_k
-#define KERN_2 ln_mod_bwd_wide_k
-  if (nj == 1 && pf) LAUNCH(1, true);
-  else if (nj == 1) LAUNCH(1, false);
-  else if (pf) LAUNCH(2, true);
-  else LAUNCH(2, false);
+#define LAUNCH(K)                                                                                                      \
+  hipLaunchKernelGGL(K, groups * split, 256, lds, (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)x, w, b,     \
+                     (const bf16_t*)scale, ld_mod, rows_per_mod, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, dscale, \
+                     dshift, ld_dmod, dwb_partial, (const bf16_t*)gate_t, (const bf16_t*)gate, ld_gate, (bf16_t*)dt,   \
+                     dgate, split, M, (int)D)
+  if (nj == 1) LAUNCH(ln_mod_bwd_k);
+  else LAUNCH(ln_mod_bwd_wide_k);
 #undef LAUNCH
-#undef KERN_1
-#undef KERN_2
   DL_LAUNCH_CHECK();
   return DL_OK;
 }
@@ -819,27 +811,29 @@ extern "C" int dl_ln_modulate_bwd_tok(const void* dout, const void* x, const flo
 }
 
 // ======================================================================== gated residual, backward
-template <int NJ>
-__global__ __launch_bounds__(512) void gate_bwd_k(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ t,
-                                                  const bf16_t* __restrict__ gate, int64_t ld_mod,
-                                                  int64_t rows_per_mod, bf16_t* __restrict__ dt,
-                                                  float* __restrict__ dgate, int64_t ld_dmod, int64_t M, int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = (float*)smem;  // [LNB_WAVES][D]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#define GTB_ARGS                                                                                                               \
+  const bf16_t *__restrict__ dout, const bf16_t *__restrict__ t, const bf16_t *__restrict__ gate, int64_t ld_mod,                \
+      int64_t rows_per_mod, bf16_t *__restrict__ dt, float *__restrict__ dgate, int64_t ld_dmod, int64_t M, int D
+#define GTB_PASS dout, t, gate, ld_mod, rows_per_mod, dt, dgate, ld_dmod, M, D
+// The row loop of both forms, one 512-thread workgroup per sample: S threads own a row (64: a wave, D <= 1024; 256: four waves,
+// 1024 < D <= 4096), thread c0 of them holds chunks c0 + S j, and the workgroup's 512 / S row owners take every (512 / S)-th row.
+// dt = gate * dout is stored; the column sums of dout * t over this thread's rows are left in acc.
+template <int S, int NJ>
+__device__ __forceinline__ void gate_bwd_rows(GTB_ARGS, float (&acc)[NJ][8]) {
+  const int c0 = threadIdx.x & (S - 1), owner = threadIdx.x / S;
   const int D8 = D >> 3;
   const int64_t g = blockIdx.x;
-  float gv[NJ][8], acc[NJ][8];
-  load_row<NJ>(gate + g * ld_mod, D8, lane, gv);
+  float gv[NJ][8];
+  load_row<NJ, S>(gate + g * ld_mod, D8, c0, gv);
 #pragma unroll
   for (int j = 0; j < NJ; ++j)
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
   const int64_t row_end = (g + 1) * rows_per_mod < M ? (g + 1) * rows_per_mod : M;
-  for (int64_t row = g * rows_per_mod + wave; row < row_end; row += LNB_WAVES) {
+  for (int64_t row = g * rows_per_mod + owner; row < row_end; row += 512 / S) {
     float dv[NJ][8], tv[NJ][8];
-    load_row<NJ>(dout + row * D, D8, lane, dv);
-    load_row<NJ>(t + row * D, D8, lane, tv);
+    load_row<NJ, S>(dout + row * D, D8, c0, dv);
+    load_row<NJ, S>(t + row * D, D8, c0, tv);
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
@@ -847,12 +841,18 @@ __global__ __launch_bounds__(512) void gate_bwd_k(const bf16_t* __restrict__ dou
         acc[j][e] += dv[j][e] * tv[j][e];
         dv[j][e] *= gv[j][e];
       }
-    store_row<NJ>(dt + row * D, D8, lane, dv);
+    store_row<NJ, S>(dt + row * D, D8, c0, dv);
   }
+}
+
+// wave-owned rows: one [D] LDS slab per wave, added in wave order by the thread that stores the column (plain stores)
+template <int NJ>
+__device__ __forceinline__ void gate_bwd_cols_waves(float* red, const float (&acc)[NJ][8], float* __restrict__ out, int D) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int c = lane + 64 * j;
-    if (c < D8) {
+    if (c < (D >> 3)) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) red[(size_t)wave * D + c * 8 + e] = acc[j][e];
     }
@@ -862,43 +862,16 @@ __global__ __launch_bounds__(512) void gate_bwd_k(const bf16_t* __restrict__ dou
     float s = 0.f;
 #pragma unroll
     for (int wv_ = 0; wv_ < LNB_WAVES; ++wv_) s += red[(size_t)wv_ * D + i];
-    dgate[g * ld_dmod + i] = s;
+    out[i] = s;
   }
 }
-
-// 1024 < D <= 4096: two 256-thread row groups per sample (even / odd rows); thread t of a group owns chunks t + 256 j, so its
+// workgroup-owned rows, two 256-thread row groups per sample (even / odd rows): thread t of a group owns chunks t + 256 j, so its
 // column sums are complete in its registers.  Group 1 hands its sums to group 0 through ONE [D] LDS row (16 KiB at D = 4096), and
-// group 0 writes (own + other) in that fixed order: plain stores, deterministic like gate_bwd_k.
+// group 0 writes (own + other) in that fixed order: plain stores, deterministic like gate_bwd_cols_waves.
 template <int NJ>
-__global__ __launch_bounds__(512) void gate_bwd_rows_k(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ t,
-                                                       const bf16_t* __restrict__ gate, int64_t ld_mod, int64_t rows_per_mod,
-                                                       bf16_t* __restrict__ dt, float* __restrict__ dgate, int64_t ld_dmod, int64_t M,
-                                                       int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = (float*)smem;  // [D]
+__device__ __forceinline__ void gate_bwd_cols_pair(float* red, const float (&acc)[NJ][8], float* __restrict__ out, int D) {
   const int tid = threadIdx.x & 255, rg = threadIdx.x >> 8;
   const int D8 = D >> 3;
-  const int64_t g = blockIdx.x;
-  float gv[NJ][8], acc[NJ][8];
-  load_row<NJ, 256>(gate + g * ld_mod, D8, tid, gv);
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
-  const int64_t row_end = (g + 1) * rows_per_mod < M ? (g + 1) * rows_per_mod : M;
-  for (int64_t row = g * rows_per_mod + rg; row < row_end; row += 2) {
-    float dv[NJ][8], tv[NJ][8];
-    load_row<NJ, 256>(dout + row * D, D8, tid, dv);
-    load_row<NJ, 256>(t + row * D, D8, tid, tv);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        acc[j][e] += dv[j][e] * tv[j][e];
-        dv[j][e] *= gv[j][e];
-      }
-    store_row<NJ, 256>(dt + row * D, D8, tid, dv);
-  }
   if (rg == 1) {
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -915,11 +888,26 @@ __global__ __launch_bounds__(512) void gate_bwd_rows_k(const bf16_t* __restrict_
     for (int j = 0; j < NJ; ++j) {
       const int c = tid + 256 * j;
       if (c >= D8) continue;
-      float* o = dgate + g * ld_dmod + c * 8;
+      float* o = out + c * 8;
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = acc[j][e] + red[c * 8 + e];
     }
   }
+}
+template <int NJ>
+__global__ __launch_bounds__(512) void gate_bwd_k(GTB_ARGS) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [LNB_WAVES][D]
+  float acc[NJ][8];
+  gate_bwd_rows<64, NJ>(GTB_PASS, acc);
+  gate_bwd_cols_waves<NJ>((float*)smem, acc, dgate + (int64_t)blockIdx.x * ld_dmod, D);
+}
+// 1024 < D <= 4096
+template <int NJ>
+__global__ __launch_bounds__(512) void gate_bwd_rows_k(GTB_ARGS) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [D]
+  float acc[NJ][8];
+  gate_bwd_rows<256, NJ>(GTB_PASS, acc);
+  gate_bwd_cols_pair<NJ>((float*)smem, acc, dgate + (int64_t)blockIdx.x * ld_dmod, D);
 }
 
 extern "C" int dl_gate_bwd(const void* dout, const void* t, const void* gate, int64_t ld_mod, int64_t rows_per_mod,
@@ -944,6 +932,27 @@ extern "C" int dl_gate_bwd(const void* dout, const void* t, const void* gate, in
 }
 
 // ======================================================================== QK RMSNorm + RoPE + head split
+// the rotation of the four (even, odd) pairs of one 8-column chunk of q and of k by the table entries cc / ss, and its transpose
+__device__ __forceinline__ void rope_rotate(float (&q)[8], float (&k)[8], const f32x4_t cc, const f32x4_t ss) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float qa = q[2 * i], qb = q[2 * i + 1], ka = k[2 * i], kb = k[2 * i + 1];
+    q[2 * i] = qa * cc[i] - qb * ss[i];
+    q[2 * i + 1] = qa * ss[i] + qb * cc[i];
+    k[2 * i] = ka * cc[i] - kb * ss[i];
+    k[2 * i + 1] = ka * ss[i] + kb * cc[i];
+  }
+}
+__device__ __forceinline__ void rope_rotate_t(float (&q)[8], float (&k)[8], const f32x4_t cc, const f32x4_t ss) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float qa = q[2 * i], qb = q[2 * i + 1], ka = k[2 * i], kb = k[2 * i + 1];
+    q[2 * i] = qa * cc[i] + qb * ss[i];
+    q[2 * i + 1] = -qa * ss[i] + qb * cc[i];
+    k[2 * i] = ka * cc[i] + kb * ss[i];
+    k[2 * i + 1] = -ka * ss[i] + kb * cc[i];
+  }
+}
 // forward: one wave per token; lane c owns elements [8c, 8c+8) of the q, k and v thirds of the qkv row.
 template <int NJ>
 __global__ __launch_bounds__(256) void qk_norm_rope_fwd_k(const bf16_t* __restrict__ qkv, const float* __restrict__ sq,
@@ -990,14 +999,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_fwd_k(const bf16_t* __restri
       if (d0 < rot) {  // rot is a multiple of 8: a chunk is either fully rotary or fully pass-through
         const f32x4_t cc = *(const f32x4_t*)(cs + (int64_t)nt * (rot >> 1) + (d0 >> 1));
         const f32x4_t ss = *(const f32x4_t*)(sn + (int64_t)nt * (rot >> 1) + (d0 >> 1));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float qa = q[j][2 * i], qb = q[j][2 * i + 1], ka = k[j][2 * i], kb = k[j][2 * i + 1];
-          q[j][2 * i] = qa * cc[i] - qb * ss[i];
-          q[j][2 * i + 1] = qa * ss[i] + qb * cc[i];
-          k[j][2 * i] = ka * cc[i] - kb * ss[i];
-          k[j][2 * i + 1] = ka * ss[i] + kb * cc[i];
-        }
+        rope_rotate(q[j], k[j], cc, ss);
       }
       const int64_t o = (((int64_t)b * H + h) * n_dst + n_off + n) * dh + d0;
       *(u32x4_t*)(qo + o) = pack8(q[j]);
@@ -1060,14 +1062,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_fwd_rows_k(const bf16_t* __r
       if (d0 < rot) {
         const f32x4_t cc = *(const f32x4_t*)(cs + (int64_t)nt * (rot >> 1) + (d0 >> 1));
         const f32x4_t ss = *(const f32x4_t*)(sn + (int64_t)nt * (rot >> 1) + (d0 >> 1));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float qa = q[j][2 * i], qb = q[j][2 * i + 1], ka = k[j][2 * i], kb = k[j][2 * i + 1];
-          q[j][2 * i] = qa * cc[i] - qb * ss[i];
-          q[j][2 * i + 1] = qa * ss[i] + qb * cc[i];
-          k[j][2 * i] = ka * cc[i] - kb * ss[i];
-          k[j][2 * i + 1] = ka * ss[i] + kb * cc[i];
-        }
+        rope_rotate(q[j], k[j], cc, ss);
       }
       const int64_t o = (((int64_t)b * H + h) * n_dst + n_off + n) * dh + d0;
       *(u32x4_t*)(qo + o) = pack8(q[j]);
@@ -1171,14 +1166,7 @@ __device__ __forceinline__ void qk_norm_rope_bwd_body(const bf16_t* __restrict__
       if (d0 < rot) {  // transpose of the rotation
         const f32x4_t cc = *(const f32x4_t*)(cs + (int64_t)nt * (rot >> 1) + (d0 >> 1));
         const f32x4_t ss = *(const f32x4_t*)(sn + (int64_t)nt * (rot >> 1) + (d0 >> 1));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float qa = gq[j][2 * i], qb = gq[j][2 * i + 1], ka = gk[j][2 * i], kb = gk[j][2 * i + 1];
-          gq[j][2 * i] = qa * cc[i] + qb * ss[i];
-          gq[j][2 * i + 1] = -qa * ss[i] + qb * cc[i];
-          gk[j][2 * i] = ka * cc[i] + kb * ss[i];
-          gk[j][2 * i + 1] = -ka * ss[i] + kb * cc[i];
-        }
+        rope_rotate_t(gq[j], gk[j], cc, ss);
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -1275,14 +1263,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_rows_k(QKB_ARGS) {
       if (d0 < rot) {  // transpose of the rotation
         const f32x4_t cc = *(const f32x4_t*)(cs + (int64_t)nt * (rot >> 1) + (d0 >> 1));
         const f32x4_t ss = *(const f32x4_t*)(sn + (int64_t)nt * (rot >> 1) + (d0 >> 1));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float qa = gq[j][2 * i], qb = gq[j][2 * i + 1], ka = gk[j][2 * i], kb = gk[j][2 * i + 1];
-          gq[j][2 * i] = qa * cc[i] + qb * ss[i];
-          gq[j][2 * i + 1] = -qa * ss[i] + qb * cc[i];
-          gk[j][2 * i] = ka * cc[i] + kb * ss[i];
-          gk[j][2 * i + 1] = -ka * ss[i] + kb * cc[i];
-        }
+        rope_rotate_t(gq[j], gk[j], cc, ss);
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {

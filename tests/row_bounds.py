@@ -162,7 +162,7 @@ def run_ln_bwd(ops, D, B, N, affine, fused, dres_on, seed=0, check=True, init=Fa
     ops.ln_modulate_bwd(d, x, w, b, sc, N, mean, rstd, dres, dx.t, dsc.win, dsh.win, dwb.t if affine else None, gate_t=gt, gate=gg,
                         dt=dt.t if fused else None, dgate=dg.win if fused else None)
     torch.cuda.synchronize()
-    res = dict(dx=dx.t)
+    res = dict(dx=dx.t, dt=dt.t if fused else None)
     if not check:
         return res
     dx.check(f"ln bwd D={D} dx")
@@ -205,7 +205,7 @@ def run_ln_bwd(ops, D, B, N, affine, fused, dres_on, seed=0, check=True, init=Fa
 
 
 # ------------------------------------------------------------------------------------------------ per-token backward (DDT decoder)
-def run_ln_bwd_tok(ops, D, M, affine, fused, seed=0, n_part=3):
+def run_ln_bwd_tok(ops, D, M, affine, fused, seed=0, n_part=3, check=True):
     x = rnd(seed, M, D, scale=2.0) - 0.25
     d = rnd(seed + 1, M, D)
     w = (rnd(seed + 2, D, dtype=torch.float32) * 0.3 + 1.0) if affine else None
@@ -224,6 +224,9 @@ def run_ln_bwd_tok(ops, D, M, affine, fused, seed=0, n_part=3):
     ops.ln_modulate_bwd_tok(d, x, w, b, sc, mean, rstd, dres, dx.t, dsc, dsh, dwb.t if affine else None, gate_t=gt, gate=gg,
                             dt=dt.t if fused else None, dgate=dg if fused else None)
     torch.cuda.synchronize()
+    res = dict(dx=dx.t, dscale=dsc, dshift=dsh, dgate=dg if fused else None, dt=dt.t if fused else None)
+    if not check:
+        return res
     what = f"ln bwd tok D={D} M={M} affine={affine} fused={fused}"
     dx.check(what + " dx")
     hit = dmod.mask & ~eb.is_poison(dmod.buf)
@@ -250,11 +253,12 @@ def run_ln_bwd_tok(ops, D, M, affine, fused, seed=0, n_part=3):
         e_dw = (C * M + 4) * U * (dy * xh).abs().sum(0) + (dy.abs() * P["e_xh"]).sum(0)
         close(tot[0][None], (dy * xh).sum(0)[None], e_dw[None], what + " dw", bf16=False)
         close(tot[1][None], dy.sum(0)[None], ((C * M + 4) * U * dy.abs().sum(0))[None], what + " db", bf16=False)
+    return res
 
 
 
 # ------------------------------------------------------------------------------------------------ gated residual backward
-def run_gate_bwd(ops, D, B, N, seed=0):
+def run_gate_bwd(ops, D, B, N, seed=0, check=True):
     M = B * N
     d, t = rnd(seed, M, D), rnd(seed + 1, M, D)
     gate = strided(rnd(seed + 2, B, D, scale=0.5))
@@ -262,6 +266,9 @@ def run_gate_bwd(ops, D, B, N, seed=0):
     dg = guarded_cols(B, D, None)  # plain stores: the window starts poisoned and must be overwritten
     ops.gate_bwd(d, t, gate, N, dt.t, dg.win)
     torch.cuda.synchronize()
+    res = dict(dt=dt.t, dgate=dg.win)
+    if not check:
+        return res
     what = f"gate bwd D={D} rows={B}x{N}"
     dt.check(what + " dt")
     dg.check(what + " dgate")
@@ -269,7 +276,7 @@ def run_gate_bwd(ops, D, B, N, seed=0):
     close(dt.t, d.double() * gr, 2 * U * (d.double() * gr).abs(), what + " dt")
     p = d.double() * t.double()
     close(dg.win, colsum(p, N), (C * N + 4) * U * colsum(p.abs(), N), what + " dgate", bf16=False)
-    return dg.win.clone()
+    return res
 
 
 

@@ -1,6 +1,7 @@
 """The one-wave-per-row kernels of csrc/norm.hip (D <= 1024: ln_mod_fwd_k, ln_mod_bwd_k / _wide_k, ln_mod_bwd_tok_k, gate_bwd_k,
 qk_norm_rope_fwd_k, qk_norm_rope_bwd_k / _wide_k, qk_norm_rope_bwd_inplace_k + fold_rows_k) element by element against the fp64
-references and bounds of tests/row_bounds.py, in NaN-poisoned buffers with checked guards.
+references and bounds of tests/row_bounds.py, in NaN-poisoned buffers with checked guards.  (gate_bwd_k runs the row loop it shares
+with gate_bwd_rows_k, gate_bwd_rows<64>; the QK kernels rotate through rope_rotate / rope_rotate_t.)
 
 Widths: 64 (8 of a wave's 64 lanes hold a chunk), 384 (48 lanes: the benchmark), 512 (a full wave), 520 (two chunks per lane, one
 lane in the second), 576, 768, 1024.  Row counts reach every launch shape of the per-sample backward (rows_wg 32 and 64, split 1, 4,

@@ -15,8 +15,19 @@ parameter-free context embedder with one output (``context_embedder=``, ``transf
 self-attention, masked cross-attention to the context tokens, GEGLU feed-forward) wherever an ``AttentionBlock`` would go, the middle
 block included.  The context contract is the reference's: ``embeddings`` channel-first ``[B, C_ctx, L]`` (a ``[B, L, C]`` tensor raises
 ``ValueError``, nothing is transposed), ``attn_mask`` a boolean ``[B, L]`` (True = attend) or absent; a context model takes ``p = 0``
-only (unet.py:825-831), so guided sampling raises the reference's ``AssertionError``.  Dropout > 0, trainable or pooled-embedding
-context embedders raise ``NotImplementedError``.
+only (unet.py:825-831), so guided sampling raises the reference's ``AssertionError``.  Trainable or pooled-embedding context
+embedders raise ``NotImplementedError``.
+
+Dropout (``dropout=p``, 0 <= p < 1) is built for the unconditional and class-conditional UNet, at the reference's two sites:
+``ResBlock.out_layers`` (GroupNorm -> SiLU -> Dropout -> conv, unet.py:171) and ``AttentionBlock.to_out`` (Conv1d -> Dropout in front of
+the residual add, unet.py:272).  Masks are applied iff ``self.training and p > 0`` (``nn.Dropout``'s rule: a no-grad forward in
+training mode has them, every eval-mode path is untouched) by the stand-alone HIP kernel ``dl_dropout``: element i of a block's
+``[B * pixels, C]`` activation is dropped iff a 16-bit half of Philox4x32-10(counter (i >> 3, block index, step), key seed) is below
+``floor(p * 65536 + 0.5)`` -- p is quantised to 1 / 65536 -- and kept elements are scaled by ``float32(1 / (1 - p))``.  The backward
+regenerates the forward's masks; nothing is stored.  ``set_dropout_seed(seed, step=0)`` fixes the stream (otherwise the seed is
+drawn from torch's global CPU generator at the first active forward); every active forward advances ``step`` by one; a data-parallel
+rank uses ``seed + rank``.  With a context embedder ``dropout > 0`` raises ``NotImplementedError`` (the TransformerBlock's sites are not
+built).
 """
 
 from __future__ import annotations
@@ -24,6 +35,7 @@ from __future__ import annotations
 from typing import Any
 
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 from torch import Tensor
 
@@ -33,15 +45,20 @@ from ...diffuse.utils import to_device
 from .mmdit import _LabelEmbed
 
 
+def dropout_rank_seed(seed: int, rank: int) -> int:
+    """the seed a data-parallel rank's masks are drawn under: ranks see different samples and must not share masks"""
+    return (int(seed) + int(rank)) & ((1 << 64) - 1)
+
+
 class _ResBlock(nn.Module):  # parameter holder for unet.py:80-237
-    def __init__(self, cin: int, cout: int, emb: int, film: bool) -> None:
+    def __init__(self, cin: int, cout: int, emb: int, film: bool, dropout: float = 0.0) -> None:
         super().__init__()
         self.in_layers = nn.Sequential(nn.GroupNorm(32, cin), nn.SiLU(), nn.Conv2d(cin, cout, 3, padding=1))
         self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb, 2 * cout if film else cout))
         conv = nn.Conv2d(cout, cout, 3, padding=1)
         for p in conv.parameters():  # zero_module (unet.py:172)
             p.detach().zero_()
-        self.out_layers = nn.Sequential(nn.GroupNorm(32, cout), nn.SiLU(), nn.Dropout(0.0), conv)
+        self.out_layers = nn.Sequential(nn.GroupNorm(32, cout), nn.SiLU(), nn.Dropout(dropout), conv)
         self.skip_connection = nn.Identity() if cin == cout else nn.Conv2d(cin, cout, 1)
 
 
@@ -59,14 +76,14 @@ class _Upsample(nn.Module):  # parameter holder for nn.py:28-56
 
 
 class _AttentionBlock(nn.Module):  # parameter holder for unet.py:240-322
-    def __init__(self, c: int, context_channels: int | None = None) -> None:
+    def __init__(self, c: int, context_channels: int | None = None, dropout: float = 0.0) -> None:
         super().__init__()
         cc = context_channels or c
         self.norm_x = nn.GroupNorm(32, c)
         self.norm_context = nn.GroupNorm(32, cc)
         self.to_q = nn.Conv1d(c, c, 1)
         self.to_kv = nn.Conv1d(cc, 2 * c, 1)
-        self.to_out = nn.Sequential(nn.Conv1d(c, c, 1), nn.Dropout(0.0))
+        self.to_out = nn.Sequential(nn.Conv1d(c, c, 1), nn.Dropout(dropout))
 
 
 class _GEGLU(nn.Module):  # parameter holder for unet.py:325-336
@@ -130,8 +147,15 @@ class UNetModel(FlatArenaDenoiser):
                 "For UNet please provide a context embedder with n_output=1 (context and attention mask)")
             if any(True for _ in context_embedder.parameters()):
                 raise NotImplementedError("diffulab_amd.UNetModel: the context embedder must be parameter-free (precomputed embeddings)")
-        if dropout:
-            raise NotImplementedError("diffulab_amd.UNetModel: dropout > 0 is not built (every reference config uses 0)")
+        dropout = float(dropout)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"diffulab_amd.UNetModel: dropout must satisfy 0 <= p < 1 (got {dropout!r})")
+        if dropout and context_embedder is not None:
+            raise NotImplementedError("diffulab_amd.UNetModel: dropout > 0 is built for the unconditional and class-conditional UNet "
+                                      "only; the text-conditioned TransformerBlock's sites (the to_out Dropout of its self- and "
+                                      "cross-attention, FeedForward.net.1) are not built")
+        self._dropout_seed: int | None = None  # host-side mask state: set_dropout_seed, or drawn at the first active forward
+        self._dropout_step = 0
         self.image_size = list(image_size)
         self.in_channels = in_channels
         self.model_channels = model_channels
@@ -157,7 +181,7 @@ class UNetModel(FlatArenaDenoiser):
                              attention_resolutions=tuple(self.attention_resolutions), channel_mult=tuple(self.channel_mult),
                              num_heads=num_heads, use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown,
                              conv_resample=conv_resample, n_classes=n_classes, classifier_free=classifier_free,
-                             context_channels=self.context_channels, transformer_depth=transformer_depth)
+                             context_channels=self.context_channels, transformer_depth=transformer_depth, dropout=dropout)
         self.dims.validate()
 
         te = self.time_embed_dim
@@ -171,7 +195,7 @@ class UNetModel(FlatArenaDenoiser):
                 if b.kind == "conv":
                     mods.append(nn.Conv2d(b.cin, b.cout, 3, padding=1))
                 elif b.kind == "res":
-                    mods.append(_ResBlock(b.cin, b.cout, te, use_scale_shift_norm))
+                    mods.append(_ResBlock(b.cin, b.cout, te, use_scale_shift_norm, dropout))
                 elif b.kind == "down":
                     mods.append(_Downsample(b.cin, conv_resample))
                 elif b.kind == "up":
@@ -179,7 +203,7 @@ class UNetModel(FlatArenaDenoiser):
                 elif b.kind == "xf":
                     mods.append(_TransformerBlock(b.cin, self.context_channels, transformer_depth))
                 else:
-                    mods.append(_AttentionBlock(b.cin))
+                    mods.append(_AttentionBlock(b.cin, dropout=dropout))
             return nn.Sequential(*mods)
 
         self.input_blocks = nn.ModuleList([group(g) for g in plan.input_blocks])
@@ -228,7 +252,35 @@ class UNetModel(FlatArenaDenoiser):
             y_eff = self._effective_labels(y.to(device=dev, dtype=torch.int64), p).contiguous()  # (drop_labels nn.py:149)
         if self.context_embedder is not None:
             self.engine.context = self._context_inputs(context, p, x.shape[0], dev)
+        self._dropout_begin()
         return {"x": self._run(x, t, y_eff)}
+
+    # ------------------------------------------------------------------ dropout (unet.py:171, :272)
+    @property
+    def dropout_active(self) -> bool:
+        """the reference's rule: nn.Dropout follows ``module.training``, not grad mode"""
+        return bool(self.training and self.dropout > 0)
+
+    def set_dropout_seed(self, seed: int, step: int = 0) -> None:
+        """masks are a pure function of (seed + rank, step, block, element); every dropout-active forward uses the current step
+        (its backward the same one) and advances it by one"""
+        self._dropout_seed, self._dropout_step = int(seed), int(step)
+
+    def _dropout_begin(self) -> None:
+        """tell the engine whether this forward applies masks and, if so, hand it (seed, step): an asynchronous 16-byte copy in
+        front of the launch sequence, outside any recorded plan or captured graph; no device value is read back"""
+        eng = self.engine
+        eng.drop_active = self.dropout_active
+        if not eng.drop_active:
+            return
+        if self._dropout_seed is None:  # drawn once, from torch's global CPU generator: torch.manual_seed governs it
+            self._dropout_seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64, device="cpu").item())
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        eng.set_dropout_state(dropout_rank_seed(self._dropout_seed, rank), self._dropout_step)
+        self._dropout_step += 1
+
+    def _graph_key(self, eng) -> tuple | None:
+        return None if self.dropout_active else ()  # a no-grad forward in training mode runs eagerly, with masks: no hipGraph replay
 
     def _context_inputs(self, context: Any, p: float, B: int, dev: torch.device) -> tuple[Tensor, Tensor | None]:
         """unet.py:838-841: the embedder runs host-side; -> (embeddings f32 [B, C_ctx, L], key bias f32 [B, L] (0 / -inf) or None)"""

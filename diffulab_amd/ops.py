@@ -1658,6 +1658,35 @@ def copy2d_bf16(src, dst, rows, cols):
     _call("dl_copy2d_bf16", _p(src), src.stride(0), _p(dst), dst.stride(0), rows, cols, _s())
 
 
+def dropout_threshold(p: float) -> int:
+    """T of dl_dropout: an element is dropped iff its 16-bit Philox half is below T = floor(p * 65536 + 0.5), so p is quantised to
+    1 / 65536.  0 <= p < 1, anything else raises ValueError; T == 0 (p == 0, or below 2^-17) means no launch is needed."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability must satisfy 0 <= p < 1 (got {p!r})")
+    return min(int(math.floor(p * 65536.0 + 0.5)), 65535)
+
+
+def dropout_scale(p: float) -> float:
+    """scale of dl_dropout: float32(1 / (1 - p)) formed in double, as nn.Dropout does"""
+    dropout_threshold(p)
+    return float(np.float32(1.0 / (1.0 - float(p))))
+
+
+def dropout(x, out, rng_state, site: int, T: int, scale: float, resid=None, rows: int | None = None, cols: int | None = None):
+    """out[r, c] = x[r, c] * (keep ? scale : 0) + (resid[r, c] if resid is given) over the [rows, cols] window of pitched bf16 or f32
+    matrices of one dtype (out may be x); keep = the Philox mask of (rng_state = device int64[2] (seed, step), site, r * cols + c)"""
+    rows = x.shape[0] if rows is None else rows
+    cols = x.shape[1] if cols is None else cols
+    if x.dtype not in (torch.bfloat16, torch.float32) or out.dtype != x.dtype or (resid is not None and resid.dtype != x.dtype):
+        raise RuntimeError("dl_dropout takes bf16 or f32 tensors of one dtype")
+    if rng_state.dtype != torch.int64 or rng_state.numel() != 2:
+        raise RuntimeError("dl_dropout: rng_state is a device int64[2] tensor (seed, step)")
+    _call("dl_dropout", _p(x), x.stride(0), _p(resid), 0 if resid is None else resid.stride(0), _p(out), out.stride(0), rows, cols,
+          F32 if x.dtype == torch.float32 else BF16, _p(rng_state), site, T, scale, _s())
+    return out
+
+
 # ------------------------------------------------------------------ fp32-class regime (csrc/f32.hip, dl_f32_*)
 class _F32Gemm(ctypes.Structure):
     _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("C", ctypes.c_void_p), ("lda", ctypes.c_int64),

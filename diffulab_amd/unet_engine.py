@@ -48,9 +48,15 @@ class UNetDims:
     classifier_free: bool = False
     context_channels: int | None = None  # C_ctx of the context embedder: TransformerBlocks replace the AttentionBlocks (unet.py:611-627)
     transformer_depth: int = 1
+    dropout: float = 0.0  # unet.py:171 (ResBlock.out_layers) and :272 (AttentionBlock.to_out); quantised to 1 / 65536 (dl_dropout)
 
     def validate(self) -> None:
         mc = self.model_channels
+        if not 0.0 <= float(self.dropout) < 1.0:
+            raise ValueError(f"dropout must satisfy 0 <= p < 1 (got {self.dropout!r})")
+        if self.dropout and self.context_channels is not None:
+            raise NotImplementedError("dropout > 0 is built for the unconditional and class-conditional UNet only: the TransformerBlock's "
+                                      "sites (the to_out of its two attention blocks, FeedForward.net.1) are not")
         if mc % 32:
             raise NotImplementedError("model_channels must be a multiple of 32 (GroupNorm32)")
         if self.context_channels is not None and self.context_channels % 32:  # the reference's GroupNorm(32, C_ctx) raises this
@@ -146,6 +152,12 @@ def xf_subblocks(d: UNetDims, b: _Blk) -> list[tuple[_Blk, _Blk, str]]:
     return [(_Blk("attn", f"{b.prefix}attn_blocks.{j}.self_attn.", b.cin, b.cin),
              _Blk("xattn", f"{b.prefix}attn_blocks.{j}.cross_attn.", b.cin, b.cin), f"{b.prefix}attn_blocks.{j}.ff.")
             for j in range(d.transformer_depth)]
+
+
+def dropout_sites(plan: _Plan) -> dict[str, int]:
+    """block prefix -> mask site of dl_dropout: the block's index in plan.all_blocks(); each `res` (out_layers.2, unet.py:171) and each
+    `attn` block (to_out.1, unet.py:272) has exactly one"""
+    return {b.prefix: i for i, b in enumerate(plan.all_blocks()) if b.kind in ("res", "attn")}
 
 
 def resample_conv(b: _Blk) -> str:
@@ -264,7 +276,38 @@ class UNetEngine:
         self._zero = torch.zeros(64, device=self.dev, dtype=torch.bfloat16)  # out-of-image taps of the implicit-GEMM convs
         self.o = ops  # resampling / layout / attention entry points of the block orchestration (the fp32 engine swaps in f32 forms)
         self.context: tuple = (None, None)  # context models: (embeddings f32 [B, C_ctx, L], key bias f32 [B, L] or None) of the next forward
+        self._init_dropout()
         self._build_shadows()
+
+    # ------------------------------------------------------------------ dropout (unet.py:171, :272; dl_dropout)
+    def _init_dropout(self) -> None:
+        """one mask site per `res` / `attn` block: its index in plan.all_blocks().  `drop_active` is set by the caller before a forward
+        (UNetModel: training mode and p > 0); the pass in flight keeps its own copy (`_drop_on`), which the saved activations carry
+        to the backward.  (seed, step) live in a device int64[2] the kernels read, written by set_dropout_state."""
+        self.drop_active = False
+        self._drop_on = False
+        self._drop_T = ops.dropout_threshold(self.d.dropout)
+        self._drop_scale = ops.dropout_scale(self.d.dropout)
+        self._drop_state: Tensor | None = None
+        self.sites = dropout_sites(self.plan)
+
+    def set_dropout_state(self, seed: int, step: int) -> None:
+        """(seed, step) of the masks of the next forward and its backward: one asynchronous 16-byte copy from pinned memory on the
+        current stream, nothing is read back.  Never part of a recorded plan or a captured graph (a replay would reuse the step)."""
+        if ops.is_recording() or torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("UNetEngine.set_dropout_state inside a launch-plan recording / stream capture: the dropout state is "
+                               "written outside, so that a replay never reuses a step's masks")
+        signed = [v - (1 << 64) if v >= (1 << 63) else v for v in (seed & ((1 << 64) - 1), step & ((1 << 64) - 1))]
+        with torch.inference_mode(False):
+            if self._drop_state is None:
+                self._drop_state = torch.zeros(2, device=self.dev, dtype=torch.int64)
+            self._drop_state.copy_(torch.tensor(signed, dtype=torch.int64).pin_memory(), non_blocking=True)
+
+    def _drop(self, b: _Blk, x: Tensor, out: Tensor | None = None, resid: Tensor | None = None) -> Tensor:
+        """out (default: x, in place) = mask_site(b)(x) * 1 / (1 - p) [+ resid]"""
+        assert self._drop_state is not None, "dropout-active pass without set_dropout_state"
+        return ops.dropout(x, x if out is None else out, self._drop_state, self.sites[b.prefix], self._drop_T, self._drop_scale,
+                           resid=resid)
 
     # ------------------------------------------------------------------ parameters
     def bind(self, params: Tensor, grads: Tensor | None) -> None:
@@ -658,6 +701,8 @@ class UNetEngine:
             h2 = self._new(B * H2 * W2, b.cout)
             self.o.rowbias_add(pre, eo[:, b.emb_off : b.emb_off + b.cout], h2, B, H2 * W2, b.cout)
         h3, st2 = self._gn(h2, B, H2 * W2, b.cout, p + "out_layers.0.", film=film)
+        if self._drop_on:  # out_layers.2 (unet.py:171): h3 is the zero-conv's input and the operand of its weight gradient
+            self._drop(b, h3)
         skip = x2 if b.cin == b.cout else self._lin_fwd(x2, p + "skip_connection.weight", b.cout, b.cin)
         out = self._conv3(h3, B, H2, W2, b.cout, p + "out_layers.3.weight", b.cout, resid=skip)  # x + h fused (unet.py:237)
         if save is not None:
@@ -668,6 +713,8 @@ class UNetEngine:
         p = b.prefix
         x, st1, h, h2, st2, h3, x2, H, W, H2, W2 = saved
         dh3 = self._conv3_bwd(dout, h3, B, H2, W2, b.cout, p + "out_layers.3.weight", b.cout)
+        if self._drop_on:  # (the GroupNorm backward recomputes from h2 and the statistics: it never reads the masked h3)
+            self._drop(b, dh3)
         dx2 = dout if b.cin == b.cout else self._lin_bwd(dout, x2, p + "skip_connection.weight", b.cout, b.cin)
         o = b.emb_off
         if self.d.use_scale_shift_norm:
@@ -771,7 +818,10 @@ class UNetEngine:
         att = self._new(B * n, c)
         probs = self._new(B, nh, n, n, dtype=torch.float32)
         self._attn_core_fwd(q, kv, att, probs, B, n, nh, c)
-        out = self._lin_fwd(att, p + "to_out.0.weight", c, c, resid=x)
+        if self._drop_on:  # to_out.1 (unet.py:272) sits in front of the residual add: the GEMM loses its fused residual
+            out = self._drop(b, self._lin_fwd(att, p + "to_out.0.weight", c, c), resid=x)
+        else:
+            out = self._lin_fwd(att, p + "to_out.0.weight", c, c, resid=x)
         if save is not None:
             save.append((x, st, nx, nc, q, kv, att, probs, H, W))
         return out
@@ -781,7 +831,10 @@ class UNetEngine:
         nh = self.d.num_heads
         x, st, nx, nc, q, kv, att, probs, H, W = saved
         n = H * W
-        datt = self._lin_bwd(dout, att, p + "to_out.0.weight", c, c)
+        dy = dout
+        if self._drop_on:  # (a buffer of its own: dout continues as the gradient of the residual)
+            dy = self._drop(b, dout, out=self._new(B * n, c))
+        datt = self._lin_bwd(dy, att, p + "to_out.0.weight", c, c)
         dq, dkv = self._new(B * n, c), self._new(B * n, 2 * c)
         self._attn_core_bwd(q, kv, datt, probs, dq, dkv, B, n, nh, c)
         dnx, dnc = self._lin_bwd_pair(dq, nx, p + "to_q.weight", c, dkv, nc, p + "to_kv.weight", 2 * c, c)
@@ -999,7 +1052,8 @@ class UNetEngine:
         ctx = self.context if self.d.context_channels is not None else ()
         key = (tuple(x.shape), x.dtype, t.dtype, None if y_eff is None else y_eff.dtype, ops._s(), self.params.data_ptr(),
                0 if self.grads is None else self.grads.data_ptr(), id(self.reducer),
-               tuple(None if c is None else tuple(c.shape) for c in ctx))  # (context models: L and C_ctx, whether a mask is given)
+               tuple(None if c is None else tuple(c.shape) for c in ctx),  # (context models: L and C_ctx, whether a mask is given)
+               bool(self.drop_active))  # (a dropout-active pass has launches of its own; they read (seed, step) from device memory)
         plans = self.__dict__.setdefault("_launch_plans", {})
         ent = plans.get(key)
         if ent is None or ent is False:  # first pass of this shape: eager (scratch buffers, tables and stages come into being)
@@ -1071,6 +1125,7 @@ class UNetEngine:
         mc, te = d.model_channels, 4 * d.model_channels
         Bp = _rup(B, 64)
         save: list | None = [] if train else None
+        self._drop_on = bool(self.drop_active and self._drop_T > 0)
 
         eo, cs = self._cond_fwd(t, y_eff, B)
         self._xctx = self._context_rows(B)
@@ -1095,7 +1150,7 @@ class UNetEngine:
         pred = self._new(B, d.out_channels, H, W, dtype=torch.float32)
         self.o.nhwc_to_nchw(o, pred, B, d.out_channels, H * W)
         if train:
-            self._saved = dict(B=B, H=H, W=W, save=save, eo=eo, y=y_eff, h=h, stf=stf, hf=hf, xctx=self._xctx, **cs)
+            self._saved = dict(B=B, H=H, W=W, save=save, eo=eo, y=y_eff, h=h, stf=stf, hf=hf, xctx=self._xctx, drop=self._drop_on, **cs)
         return pred
 
     # ------------------------------------------------------------------ backward
@@ -1111,6 +1166,7 @@ class UNetEngine:
                 g.zero_()
         B, H, W, save, eo = s["B"], s["H"], s["W"], s["save"], s["eo"]
         self._xctx = s["xctx"]
+        self._drop_on = s["drop"]  # the backward makes the forward's choice, with the forward's (seed, step)
         mc, te = d.model_channels, 4 * d.model_channels
         Bp = _rup(B, 64)
         R = self.layout.emb_rows

@@ -87,6 +87,7 @@ class UNetEngineF32(UNetEngine):
         self.o = _F32Ops(self)
         self.sh = {}
         self.context: tuple = (None, None)
+        self._init_dropout()
 
     # ------------------------------------------------------------------ parameters: the GEMMs read the f32 arena directly
     def bind(self, params: Tensor, grads: Tensor | None) -> None:

@@ -1027,6 +1027,20 @@ DL_API int dl_add_bf16(const void* a, const void* b, void* out, int64_t n, dl_st
  * connections (torch.cat(dim=1) in NCHW == column blocks in NHWC) and zero-padding to the GEMM alignment */
 DL_API int dl_copy2d_bf16(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t rows, int64_t cols,
                           dl_stream_t stream);
+/* Dropout of the UNet: unet.py:171 (ResBlock.out_layers: GroupNorm -> SiLU -> Dropout -> conv) and unet.py:272 (AttentionBlock.to_out:
+ * Conv1d -> Dropout, in front of the residual add).  out[r, c] = fma(x[r, c], keep ? scale : 0, resid ? resid[r, c] : 0) in f32, rounded
+ * once to the output type, over the logical [rows, cols] view of pitched matrices (dtype DL_BF16 / DL_F32: x, resid and out share it;
+ * resid may be NULL; out may alias x).  keep is a pure function of (seed, step, site, i), i = r * cols + c (pad columns are not
+ * counted): Philox4x32-10 (multipliers D2511F53 / CD9E8D57, Weyl increments 9E3779B9 / BB67AE85) on the counter
+ * (g lo, g hi, site, step lo), g = i >> 3, under the key (seed lo, seed hi) gives four words = eight 16-bit halves; element i takes the
+ * half of word (i & 7) >> 1, low for even i, high for odd, and is DROPPED iff that half < T.  T = floor(p * 65536 + 0.5) (p is
+ * quantised to 1 / 65536) and scale = (float)(1 / (1 - p)) are formed by the host, static per launch site, like `site`.
+ * rng_state: DEVICE pointer to two uint64 (seed, step), read by the kernel: a recorded or captured launch sees the current step when
+ * it is replayed.  The backward of a site is the same call on the gradient (same state, same site).
+ * Contract: cols, ldx, ldr, ldo % 8 == 0, each pitch >= cols, x / resid / out 16-byte aligned, 0 <= T < 65536, rows * cols < 2^40;
+ * anything else is DL_ERR_INVALID before any device call. */
+DL_API int dl_dropout(const void* x, int64_t ldx, const void* resid, int64_t ldr, void* out, int64_t ldo, int64_t rows, int64_t cols,
+                      int dtype, const uint64_t* rng_state, int32_t site, int32_t T, float scale, dl_stream_t stream);
 
 /* ------------------------------------------------------------------ fp32-class regime (csrc/f32.hip)
  * The reference's DEFAULT precision (`precision_type="no"`: training/trainers/common.py:76,105, configs/trainer/default.yaml:4):

@@ -50,12 +50,13 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--graph", action="store_true", help="LAB: the whole step replayed as one hipGraph (scripts/lab/graph_step.py)")
+    ap.add_argument("--dropout", type=float, default=0.0, help="UNetModel(dropout=...): masks at every ResBlock / AttentionBlock site")
     a = ap.parse_args()
     dev = "cuda"
     torch.manual_seed(0)
     m = UNetModel(image_size=[32, 32], in_channels=1, model_channels=128, out_channels=1, num_res_blocks=2,
                   attention_resolutions=[4, 8, 16], num_heads=2, resblock_updown=True, n_classes=10,
-                  use_scale_shift_norm=True, classifier_free=False).to(dev)
+                  use_scale_shift_norm=True, classifier_free=False, dropout=a.dropout).to(dev)
     gd = Diffuser(m, sampling_method="ddpm", model_type="gaussian_diffusion", n_steps=1000)
     opt = FusedAdamW(m.parameters(), lr=1e-4)
     x0 = torch.randn(a.batch, 1, 32, 32, device=dev)

@@ -1501,6 +1501,41 @@ def ema_update(ema, p, beta):
     _call("dl_ema_update", _p(ema), _p(p), float(beta), p.numel(), _s())
 
 
+EMA_MAX_PROFILES, LINCOMB_MAX_SOURCES, LINCOMB_ACCUMULATE = 4, 256, 1
+
+
+def ema_update_multi(emas, p, weights):
+    """one launch: ema_k = fma(w_k, p - ema_k, ema_k) for up to four f32 buffers `emas` of p's size; `weights` are the w_k = 1 - beta_k
+    (formed in fp64 by the caller, rounded to f32 here)"""
+    K = len(emas)
+    if not 1 <= K <= EMA_MAX_PROFILES or len(weights) != K:
+        raise RuntimeError(f"dl_ema_update_multi takes 1 .. {EMA_MAX_PROFILES} profiles and one weight each (got {K} and {len(weights)})")
+    for e in emas:
+        if e.dtype != torch.float32 or p.dtype != torch.float32 or not e.is_contiguous() or not p.is_contiguous() or e.numel() != p.numel():
+            raise RuntimeError("dl_ema_update_multi takes contiguous f32 tensors of one size")
+    ptrs = [_p(e) for e in emas] + [None] * (EMA_MAX_PROFILES - K)
+    ws = [float(w) for w in weights] + [0.0] * (EMA_MAX_PROFILES - K)
+    _call("dl_ema_update_multi", *ptrs, _p(p), K, *ws, p.numel(), _s())
+
+
+def arena_lincomb(out, srcs, weights, accumulate: bool = False):
+    """one launch: out = [out +] sum_k weights[k] * srcs[k], one f32 multiply-add chain per element in the order of `srcs`; f32
+    contiguous tensors of out's size, 16-byte aligned.  The two tables (addresses, weights) are built here, host and device copy"""
+    K = len(srcs)
+    if not 1 <= K <= LINCOMB_MAX_SOURCES or len(weights) != K:
+        raise RuntimeError(f"dl_arena_lincomb takes 1 .. {LINCOMB_MAX_SOURCES} sources and one weight each (got {K} and {len(weights)})")
+    for s in (out, *srcs):
+        if s.dtype != torch.float32 or not s.is_contiguous() or s.numel() != out.numel():
+            raise RuntimeError("dl_arena_lincomb takes contiguous f32 tensors of one size")
+    ptr_host = torch.tensor([_p(s) for s in srcs], dtype=torch.int64)
+    w_host = torch.from_numpy(np.asarray(weights, dtype=np.float64).astype(np.float32))
+    ptr_dev, w_dev = keep(ptr_host.to(out.device)), keep(w_host.to(out.device))
+    keep(ptr_host), keep(w_host)
+    _call("dl_arena_lincomb", _p(out), ptr_host.data_ptr(), _p(ptr_dev), w_host.data_ptr(), _p(w_dev), K, out.numel(),
+          LINCOMB_ACCUMULATE if accumulate else 0, _s())
+    return out
+
+
 # ------------------------------------------------------------------ UNet kernels (NHWC bf16 token rows)
 def nchw_to_nhwc(x, out, B, C, HW):
     _call("dl_nchw_to_nhwc", _p(x), _p(out), B, C, HW, out.stride(0), _s())

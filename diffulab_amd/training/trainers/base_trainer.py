@@ -20,7 +20,7 @@ from torch.optim.lr_scheduler import LRScheduler
 from torch.optim.optimizer import Optimizer
 
 from ...datasets.base import BatchData
-from ..ema import EMA
+from ..ema import EMA, PowerEMA
 from ...diffuse.modelizations.flow import NO_VARIATIONAL_BOUND
 from ...diffuse.modelizations.gaussian_diffusion import NO_ODE_LIKELIHOOD
 from ...diffuse.utils import to_device
@@ -75,7 +75,16 @@ class BaseTrainer(Trainer):
                 scheduler.step()
         if ema_denoiser is not None:
             ema_denoiser.update()  # counts micro-steps: update_after_step / update_every were scaled in __init__ (common.py:97-98)
+            if self.ema_type == "power":
+                self._snapshot_power_ema(ema_denoiser)
         self.end_micro_step()
+
+    def _snapshot_power_ema(self, ema: PowerEMA) -> None:
+        """rank 0 writes every profile under save_path/phema once per `ema_snapshot_every` profile updates"""
+        every = self.ema_snapshot_every
+        if every and self.is_main_process and ema.t > 0 and ema.t % every == 0 and ema.t != self.__dict__.get("_phema_t"):
+            ema.snapshot(self.save_path / "phema")
+            self._phema_t = ema.t  # (update() calls between two profile updates leave t where it was)
 
     @torch.no_grad()
     def validation_step(self, diffuser: "Diffuser", val_batch: BatchData, tracker: AverageMeter) -> None:
@@ -176,7 +185,7 @@ class BaseTrainer(Trainer):
 
     # ---- the pieces of train() (reference: one function, base_trainer.py:277-399; same order of effects)
     def _setup_run(self, diffuser: "Diffuser", optimizer: Optimizer, train_embedder: bool, optimizer_ckpt: str | None,
-                   denoiser_ckpt: str | None, ema_ckpt: str | None) -> EMA | None:
+                   denoiser_ckpt: str | None, ema_ckpt: str | None) -> EMA | PowerEMA | None:
         """checkpoints in, device placement / rank-0 broadcast / reducer (``prepare``), the EMA copy, auxiliary loss heads hooked
         onto the denoiser, a frozen context embedder unless it is trained"""
         if denoiser_ckpt:
@@ -185,7 +194,12 @@ class BaseTrainer(Trainer):
         if optimizer_ckpt:  # after prepare(): the state follows the parameters' device (and the arena exists)
             optimizer.load_state_dict(torch.load(optimizer_ckpt, weights_only=False))
         ema = None
-        if self.use_ema:
+        if self.use_ema and self.ema_type == "power":
+            ema = PowerEMA(diffuser.denoiser, sigma_rels=self.ema_sigma_rels, update_every=self.ema_update_every,
+                           eval_sigma_rel=self.ema_eval_sigma_rel).to(self.device)
+            if ema_ckpt:  # ema_state.pt of save_model: t, the call counter and every profile
+                ema.load_state_dict(torch.load(ema_ckpt, weights_only=True))
+        elif self.use_ema:
             ema = EMA(diffuser.denoiser, beta=self.ema_rate, update_after_step=self.ema_update_after_step,
                       update_every=self.ema_update_every).to(self.device)
             if ema_ckpt:

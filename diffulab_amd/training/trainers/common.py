@@ -44,7 +44,7 @@ from torch.optim.optimizer import Optimizer
 from ...datasets.base import BatchData
 from ...diffuse.utils import to_device
 from ..dp import GradReducer, broadcast_arena
-from ..ema import EMA
+from ..ema import EMA, PowerEMA
 
 if TYPE_CHECKING:
     from ...diffuse import Diffuser
@@ -67,6 +67,10 @@ class Trainer(ABC):
         compile: bool = False,
         dynamo_plugin_kwargs: dict[str, Any] = {},
         max_grad_norm: float | None = None,
+        ema_type: str = "classic",
+        ema_sigma_rels: tuple[float, ...] = (0.05, 0.10),
+        ema_eval_sigma_rel: float | None = None,
+        ema_snapshot_every: int = 0,
     ) -> None:
         if precision_type not in ("no", "bf16"):
             raise NotImplementedError(
@@ -80,6 +84,21 @@ class Trainer(ABC):
         self.gradient_accumulation_step = max(1, int(gradient_accumulation_step))
         self.ema_update_after_step = ema_update_after_step * self.gradient_accumulation_step
         self.ema_update_every = ema_update_every * self.gradient_accumulation_step
+        # ema_type="power" (this project's): power-function profiles with snapshots for post-hoc EMA (training/posthoc_ema.py) instead
+        # of the one classic EMA; "classic" makes exactly the calls it always made
+        if ema_type not in ("classic", "power"):
+            raise ValueError(f"ema_type must be 'classic' or 'power', got {ema_type!r}")
+        if int(ema_snapshot_every) < 0:
+            raise ValueError(f"ema_snapshot_every must be >= 0, got {ema_snapshot_every!r}")
+        if ema_type == "power" and ema_update_after_step != 0:
+            raise ValueError(f"ema_update_after_step = {ema_update_after_step!r} with ema_type='power': a power-function profile has no "
+                             "warm-up (its first update is a copy), so only 0 is accepted")
+        self.ema_type = ema_type
+        self.ema_sigma_rels = tuple(float(s) for s in ema_sigma_rels)
+        self.ema_eval_sigma_rel = ema_eval_sigma_rel
+        self.ema_snapshot_every = int(ema_snapshot_every)  # in EMA updates; 0: no snapshots
+        if ema_type == "power":  # (refuse bad widths now, not after the data has been loaded)
+            PowerEMA.check_arguments(self.ema_sigma_rels, self.ema_eval_sigma_rel)
         self.compile = compile
         # clip by global gradient norm on the synchronising micro-step (where accelerator.clip_grad_norm_ acts); None = no clipping
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -295,7 +314,7 @@ class Trainer(ABC):
             dist.barrier()
 
     # ------------------------------------------------------------------ checkpoints (file names of common.py:156-176)
-    def save_model(self, optimizer: Optimizer, diffuser: "Diffuser", ema_denoiser: EMA | None = None,
+    def save_model(self, optimizer: Optimizer, diffuser: "Diffuser", ema_denoiser: EMA | PowerEMA | None = None,
                    scheduler: LRScheduler | None = None) -> None:
         if not self.is_main_process:
             return
@@ -304,6 +323,9 @@ class Trainer(ABC):
         torch.save(optimizer.state_dict(), self.save_path / "optimizer.pt")
         if ema_denoiser is not None:
             torch.save(cpu(ema_denoiser.ema_model.state_dict()), self.save_path / "ema.pt")
+            if isinstance(ema_denoiser, PowerEMA):  # ema.pt: the evaluation profile, for every loader of ema.pt; the rest to resume
+                state = ema_denoiser.state_dict()
+                torch.save({**state, "profiles": [cpu(sd) for sd in state["profiles"]]}, self.save_path / "ema_state.pt")
         if scheduler is not None:
             torch.save(scheduler.state_dict(), self.save_path / "scheduler.pt")
         for extra_loss in diffuser.extra_losses:

@@ -54,6 +54,10 @@ def train(cfg: DictConfig):
         use_ema=cfg.trainer.use_ema,
         ema_update_after_step=cfg.trainer.get("ema_update_after_step", 0),
         ema_update_every=cfg.trainer.get("ema_update_every", 10),
+        ema_type=cfg.trainer.get("ema_type", "classic"),
+        ema_sigma_rels=tuple(cfg.trainer.get("ema_sigma_rels", (0.05, 0.10))),
+        ema_eval_sigma_rel=cfg.trainer.get("ema_eval_sigma_rel", None),
+        ema_snapshot_every=cfg.trainer.get("ema_snapshot_every", 0),
         run_config=OmegaConf.to_container(cfg, resolve=True),
         compile=cfg.trainer.get("compile", False),
         init_kwargs={"wandb": cfg.trainer.get("wandb", {})},

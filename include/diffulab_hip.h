@@ -874,6 +874,30 @@ DL_API int dl_cast2d_f32_to_bf16(const float* src, int64_t ld_src, void* dst, in
 
 /* ema = ema + (1 - beta) (p - ema)  == lerp used by ema_pytorch (base_trainer.py:152-153) */
 DL_API int dl_ema_update(float* ema, const float* p, float beta, int64_t n, dl_stream_t stream);
+/* Post-hoc EMA (Karras et al. 2024, sec. 3.2 / app. C; csrc/ema.hip; this project's, the reference has none).
+ *
+ * dl_ema_update_multi (1 launch): ema_k = fma(w_k, p - ema_k, ema_k) for the first K of the four profile buffers, 1 <= K <= 4, in one
+ * pass that reads p once and never writes it.  The WEIGHTS w_k = 1 - beta_k travel, not the decays: the host forms them in fp64
+ * (a power-function profile's 1 - beta_t ~ (gamma + 1) / t loses ~0.3 % at t = 1e6 when it is formed as 1.0f - float(beta_t)).
+ * w_k == 1 gives p's bits, w_k == 0 leaves ema_k's bits; for 0 < w < 1, K = 1 gives dl_ema_update(beta)'s bits where w = 1.0f - beta
+ * (same expression, same contraction).  Profile pointers beyond K are not looked at.  Any 4-byte aligned pointers and any n > 0:
+ * float4 with a scalar tail where every pointer is 16-byte aligned, one element at a time otherwise, with the same bits.
+ * Refused with DL_ERR_INVALID before any launch: K outside 1..4, a NULL among the first K profiles or p, n <= 0, a non-finite
+ * weight among the first K, two of the first K profiles equal, a profile equal to p.
+ *
+ * dl_arena_lincomb (1 launch): out[i] = sum_k w[k] * src_k[i] over K f32 buffers of n elements, 1 <= K <= 256, as ONE chain
+ * acc = fma(w[k], src_k[i], acc) in the order k = 0 .. K-1, starting from 0, or from out[i] with DL_LINCOMB_ACCUMULATE: consecutive
+ * groups of sources, the first without the flag and the rest with it, give the bits of one launch over all of them.  Two tables,
+ * the source addresses (int64[K]) and the weights (f32[K]), each given as a HOST copy (validated before any launch) and an identical
+ * DEVICE copy (read by the kernel), as dl_muon_pre takes its tables.  out and every source 16-byte aligned; any n > 0 (scalar
+ * tail); out aliases no source; sources are never written.  HBM traffic (K + 1) * 4n bytes (+ 4n with ACCUMULATE).
+ * Refused with DL_ERR_INVALID before any launch: K out of range, a NULL table or out, a NULL or misaligned pointer in the host
+ * table, out equal to a source, n <= 0, unknown flag bits. */
+enum { DL_LINCOMB_ACCUMULATE = 1 };
+DL_API int dl_ema_update_multi(float* ema0, float* ema1, float* ema2, float* ema3, const float* p, int K, float w0, float w1, float w2,
+                               float w3, int64_t n, dl_stream_t stream);
+DL_API int dl_arena_lincomb(float* out, const int64_t* srcs_host, const int64_t* srcs_dev, const float* w_host, const float* w_dev,
+                            int K, int64_t n, int flags, dl_stream_t stream);
 
 /* ------------------------------------------------------------------ UNet (networks/denoisers/unet.py, networks/utils/nn.py)
  * Activations inside the library are NHWC bf16 token rows [B*H*W, C]; a 3x3 convolution (nn.Conv2d padding=1, unet.py:187,

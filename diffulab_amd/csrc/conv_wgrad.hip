@@ -30,6 +30,12 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_wgrad_paths.h"
+
+// the path code of the last weight-gradient launch (conv_wgrad_paths.h): one relaxed host-side store per call, read by the tests
+static std::atomic<int> g_last_wgrad_path{WG_NONE};
+void dl_note_wgrad_path(int path) { g_last_wgrad_path.store(path, std::memory_order_relaxed); }
+extern "C" __attribute__((visibility("default"))) int dl_lab_last_wgrad_path() { return g_last_wgrad_path.load(std::memory_order_relaxed); }
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
@@ -362,6 +368,7 @@ int launch_conv_wgrad_halo(const void* x, int64_t ldx, int64_t Bn, int64_t H, in
     a.xcd_major = 0;
     grid = splits * a.ntile;
   }
+  dl_note_wgrad_path(W == 32 ? WG_HALO_W32 : W == 16 ? WG_HALO_W16 : W == 8 ? WG_HALO_W8 : WG_HALO_W4);
   if (W == 32) return launch_cw<5, 2>(a, grid, stream);
   if (W == 16) return launch_cw<4, 4>(a, grid, stream);
   if (W == 8) return launch_cw<3, 8>(a, grid, stream);

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "gemm_paths.h"
+#include "conv_wgrad_paths.h"
 
 // the path code of the last GEMM-family launch (gemm_paths.h): one relaxed host-side store per call, read by the tests
 static std::atomic<int> g_last_path{DL_PATH_NONE};
@@ -2062,6 +2063,7 @@ static int conv_wgrad_launch(const void* x, int64_t ldx, int64_t Bn, int64_t H, 
   if (part_stride > 0)
     DL_CHECK_ARG(p.splits <= max_parts && part_stride >= M * ldg, "%s: %d partial images of %lld floats needed, room for %lld of %lld", who,
                  p.splits, (long long)(M * ldg), (long long)max_parts, (long long)part_stride);
+  dl_note_wgrad_path(p.big ? WG_IGEMM_BIG : WG_IGEMM_SMALL);
   if (p.big) {
     const int units = (p.tiles_m * p.splits + 7) & ~7;
     hipLaunchKernelGGL(gemm_tn_big_k<true>, units * p.tiles_n, BIG_THREADS, 2 * W_STAGE, (hipStream_t)stream, (const bf16_t*)x, ldx,
